@@ -2,10 +2,15 @@
 """bench.py -- BASELINE.json's metric on MI355X: train patches/s of EquiUnet width 48 on synthetic
 4x128^3 patches, batch 2 per GPU, bf16 (configs[1]); one "step" = forward + deep-supervision Dice
 loss + backward + gradient all-reduce (N > 1) + fused Ranger2020 step (the reference's default optimizer; --optimizer adam for
-torch's Adam).  Prints ONE JSON line on rank 0; at N = 1 the line also carries the other stated configurations as short legs
-(configs2_per_gpu, configs4_per_gpu, fp16_mode, inference*, parity_mode) measured AFTER the headline's timed region.
+torch's Adam).  Prints ONE JSON line on rank 0.
 
-  python bench.py --gpus 1 --steps 5 --warmup 2
+A plain run sets up, warms up, times the steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.  With
+--full the line also carries everything else, measured AFTER the headline's timed region: the box probe, the dominant kernel's
+roofline (per-kernel HIP events in two of the timed steps) and live HBM traffic, the host-enqueue time and `ddp` accounting, at
+N = 1 the other stated configurations as short legs (configs2_per_gpu, configs4_per_gpu, fp16_mode, inference*, parity_mode) and
+the CPU baseline, at N > 1 the graph leg (graph_ddp).
+
+  python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W
 """
@@ -31,6 +36,32 @@ PEAK_FP8_TFLOPS = 5000.0    # dense MX-scaled e4m3 MFMA (--fp8 only)
 
 def conv_flops(cin, cout, k, n, d, h, w):
     return 2.0 * cin * k ** 3 * cout * n * d * h * w
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # parameters + gradients together; the loss adds 4 bytes (cap: 64 MB)
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float32 .npy files -- loss.npy (the step's return
+    value) and, per parameter of the model it updated, param.<name>.npy (the weights after the optimizer step) and
+    grad.<name>.npy (the step's gradient).  A tensor larger than the per-tensor share of DUMP_BUDGET_BYTES is reduced to a
+    fixed sample: flat indices drawn from a CPU generator seeded with the parameter's position, sorted -- the same elements in
+    every run of the same configuration, so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy())
+    params = list(model.named_parameters())
+    per_tensor = DUMP_BUDGET_BYTES // (2 * 4 * len(params))
+    for i, (name, p) in enumerate(params):
+        idx = None
+        if p.numel() > per_tensor:
+            g = torch.Generator().manual_seed(i)
+            idx = torch.randint(p.numel(), (per_tensor,), generator=g).sort().values.to(p.device)
+        for kind, v in (("param", p), ("grad", p.grad)):
+            if v is None:
+                continue
+            flat = v.detach().reshape(-1)
+            np.save(os.path.join(out_dir, f"{kind}.{name}.npy"), (flat if idx is None else flat[idx]).float().cpu().numpy())
 
 
 def cpu_baseline(width, cores):
@@ -540,7 +571,7 @@ def graph_ddp_leg(n, argv, base_env):
 def launch_ranks(n, argv, dry_run=False):
     """Started bare with --gpus N: run the N ranks as CHILD processes of this one, which never touches the GPU.
     Leg 1 (the headline) is the eager data-parallel step; its JSON line is the line of this run.  Leg 2 (graph_ddp_leg) runs only
-    after leg 1 succeeded and only for the default eager headline, and lands on the line as "graph_ddp"."""
+    under --full, after leg 1 succeeded and only for the default eager headline, and lands on the line as "graph_ddp"."""
     if not dry_run and os.environ.get("BRATS_DIST_BACKEND") != "gloo":  # (gloo: the debugging set-up with ranks sharing a GPU)
         have = gpu_count_without_hip()  # (sysfs; unknown -> the ranks' own device / WORLD_SIZE checks fail loudly instead)
         if have is not None and have < n:
@@ -549,7 +580,8 @@ def launch_ranks(n, argv, dry_run=False):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "8")  # (each rank narrows its own torch pool to its CPU slice: pin_rank_to_cpus)
-    want_graph_leg = not dry_run and "--graph" not in argv and "--no-graph-leg" not in argv and env.get("BRATS_DIST_BACKEND") != "gloo"
+    want_graph_leg = not dry_run and "--full" in argv and "--graph" not in argv and "--no-graph-leg" not in argv \
+        and env.get("BRATS_DIST_BACKEND") != "gloo"
     rc, js, other = run_ranks(n, list(argv) + (["--no-graph-leg"] if want_graph_leg else []), env,
                               float(env.get("BRATS_LEG_TIMEOUT", "1800")))
     for line in other:
@@ -620,12 +652,19 @@ def main():
                     help="NOT the headline configuration: run the 3x3x3 convolutions forward (fwd) or forward + input "
                          "gradients (all) on the e4m3 MFMA kernel (BASELINE.json configs[4]); weight gradients stay bf16")
     ap.add_argument("--dropout", type=float, default=0.0, help="NOT the headline configuration: --dropout p of the reference's CLI")
-    ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel time table (rank 0)")
+    ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel time table (rank 0; needs --full)")
     ap.add_argument("--no-pmc-traffic", action="store_true",
                     help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child processes after the timed region)")
     ap.add_argument("--pmc-leg", action="store_true", help="(internal) only the dominant kernel's launch, for a rocprofv3 --pmc pass")
     ap.add_argument("--no-graph-leg", action="store_true",
                     help="bare --gpus N > 1: do not run the second leg (the step incl. its RCCL all-reduces as one hipGraph, fresh ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline (box probe, roofline + live PMC traffic, host-enqueue / ddp "
+                         "accounting, inference, parity mode, other configurations, CPU baseline, the N > 1 graph leg); the "
+                         "--no-* switches above narrow it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and the updated parameters / gradients (fixed sample of the large "
+                         "ones) as float32 .npy files under DIR (rank 0)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous check only: every rank joins the process group (gloo on CPU), one all-reduce, rank 0 "
                          "prints {n_gpus, dry_run}; no GPU is touched (tests/test_bench_launch_cpu.py)")
@@ -720,11 +759,11 @@ def main():
         step()
     # what THIS box delivers right now (dense bf16 MFMA rate with every SIMD issuing, bf16 read + write stream): ~50 ms of
     # probes right before the timed region, so that a reader can tell a slower box from slower code (roofline.frac_of_box)
-    box = ops.probe_box(dev) if rank == 0 else None
-    timer = ops.KernelTimer() if rank == 0 and not args.graph and not os.environ.get("BRATS_BENCH_NO_TIMER") else None
+    box = ops.probe_box(dev) if args.full and rank == 0 else None
+    timer = ops.KernelTimer() if args.full and rank == 0 and not args.graph and not os.environ.get("BRATS_BENCH_NO_TIMER") else None
     # per-kernel HIP events cost GPU time themselves (0.28 ms per step when every conv launch of every step is bracketed):
-    # they are recorded in two of the timed steps only (at 1/3 and 2/3 of the run), inside the timed region
-    sample_at = sorted({args.steps // 3, (2 * args.steps) // 3})
+    # they are recorded in two of the timed steps only (at 1/3 and 2/3 of the run), inside the timed region, and only under --full
+    sample_at = sorted({args.steps // 3, (2 * args.steps) // 3}) if args.full else []
     sampled = len(sample_at)
     def barrier():  # (RCCL: name the device, or ProcessGroupNCCL guesses it from the rank and warns)
         if dist.get_backend() == "nccl":
@@ -751,19 +790,23 @@ def main():
         el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = float(el.item())
+    if args.dump_outputs and rank == 0:  # (before anything below runs another step)
+        dump_outputs(args.dump_outputs, loss, model)
     # host side of a step, measured AFTER the timed region on an empty queue: how long this rank's Python / launch path needs to
     # enqueue three steps while the GPU is still busy with the first (inside the 50-step region the enqueue thread runs into the
     # full HIP queue and its time converges to the GPU's).  host_enqueue_ms close to ms_per_step = the eager step is bound by the
     # host, and eight ranks on one host scale by their CPUs, not by their GPUs -- the case the graph leg (one launch per step) is for
     if buckets is not None:
         buckets.measure = False
-    th = time.perf_counter()
-    for _ in range(3):
-        step()
-    host_enqueue_ms = (time.perf_counter() - th) / 3 * 1e3
-    torch.cuda.synchronize()
+    host_enqueue_ms = None
+    if args.full:
+        th = time.perf_counter()
+        for _ in range(3):
+            step()
+        host_enqueue_ms = (time.perf_counter() - th) / 3 * 1e3
+        torch.cuda.synchronize()
     ddp_info = None
-    if buckets is not None:
+    if buckets is not None and args.full:
       try:  # (accounting only: whatever goes wrong here must not cost the line its headline)
           # data-parallel accounting: per-rank step time, the collectives' stand-alone cost, and how much of it the overlap
           # with the backward kernels hid (exposed = GPU time finish() waited for them in the sampled steps)
@@ -880,7 +923,7 @@ def main():
     res = {
         "metric": f"train patches/sec (4x{args.patch}^3, width-{args.width})", "value": round(patches / elapsed, 4), "unit": "patches/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2),
-        "host_enqueue_ms": round(host_enqueue_ms, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": args.precision + (f"+e4m3 conv ({args.fp8})" if args.fp8 else ""), "data": "synthetic",
         "config": {"workload": f"{args.model} width={args.width}, batch={args.batch}/GPU of 4x{args.patch}^3 synthetic patches, "
                                f"fwd + deep-supervision Dice + bwd + {args.optimizer}" + (" as one hipGraph" if args.graph else "") +
@@ -889,13 +932,15 @@ def main():
                                 " (BASELINE.json configs[2], per-GPU share)" if (args.model, args.width, args.fp8) == ("equiunet_assp_evo", 48, None) else
                                 f" (BASELINE.json configs[4], per-GPU share at {args.batch} patches, {args.precision} storage)" if (args.model, args.width) == ("equiunet_assp_evo", 64) and args.fp8 else ""),
                    "global_batch": world * args.batch, "parallelism": f"dp{world}", "loss": round(float(loss.item()), 5)},
-        "roofline": roofline, "box": box,
     }
+    if args.full:
+        res.update({"host_enqueue_ms": round(host_enqueue_ms, 2), "roofline": roofline, "box": box})
     if ddp_info is not None:
         res["ddp"] = ddp_info
-    if world == 1 and not args.no_infer:
+    legs = args.full and world == 1  # (the legs below run after the headline, on this process's GPU)
+    if legs and not args.no_infer:
         res.update(inference_bench(model, dev, args))
-    if world == 1 and not args.no_parity_leg and args.precision == "bf16" and not args.fp8:
+    if legs and not args.no_parity_leg and args.precision == "bf16" and not args.fp8:
         res["parity_mode"] = parity_mode_leg(args, dev, x, t)
         res["dtype_note"] = ("value is measured in bf16 storage / f32 accumulate: logits NOT within 1e-3 (max ~0.3 on |logits| <= 28; the 1e-3-logit "
                              "configuration is parity_mode).  Hard Dice against the CPU oracle on TRAINED weights (tests/test_trained_gpu.py, six weight sets "
@@ -903,18 +948,18 @@ def main():
                              "1.3e-4, < 5e-5 stitched over a configs[3] volume -- asserted for every weight set; on stress volumes (half / a third of the "
                              "training contrast, where the network itself is unsure) fp16 stays <= 6.1e-4 on all 20, bf16 exceeds 1e-3 on 6 of 20 (max "
                              "4.3e-3): fp16_mode, the reference's own autocast dtype, is the configuration that holds the bar there")
-    if world == 1 and not args.no_other_configs and (args.model, args.width, args.precision, args.fp8, args.batch, args.dropout) == ("equiunet", 48, "bf16", None, 2, 0.0) \
+    if legs and not args.no_other_configs and (args.model, args.width, args.precision, args.fp8, args.batch, args.dropout) == ("equiunet", 48, "bf16", None, 2, 0.0) \
             and (args.patch == 128 or args.other_configs_patch):
         del train_step, opt
         model.zero_grad(set_to_none=True)
         torch.cuda.empty_cache()
         res.update(other_configs_legs(dev, rank, args.other_configs_patch or 128))
-    if world == 1 and not args.no_cpu_baseline:
+    if legs and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args.width, os.cpu_count() or 1)
     if live:
         backend = dist.get_backend()
         dist.destroy_process_group()  # (the other ranks have returned already; nothing below is collective)
-        if backend == "nccl" and not args.graph and not args.no_graph_leg and not os.environ.get("BRATS_NO_GRAPH_LEG"):
+        if args.full and backend == "nccl" and not args.graph and not args.no_graph_leg and not os.environ.get("BRATS_NO_GRAPH_LEG"):
             # started as a rank of somebody else's torch.distributed.run (the driver's launch form): the graph + RCCL leg runs as a
             # CHILD torch.distributed.run of rank 0 -- fresh rank processes -- after this rank gave its memory back
             train_step = opt = model = buckets = x = t = loss = crit = None  # noqa: F841 (drop every reference to device memory)

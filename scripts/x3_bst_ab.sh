@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_headline_gpu.py -m gpu -x -q -s -k "vs_o
 for model in equiunet equiunet_assp_evo; do
 for f in 0 1 0 1 0 1; do
   echo "=== bench x3 $model, BRATS_FOLD_BWD_STATS=$f" >> $out/log.txt
-  BRATS_FOLD_BWD_STATS=$f python3 bench.py --model $model --precision x3 --steps 10 --warmup 3 --no-infer --no-cpu-baseline --no-parity-leg --no-other-configs 2>/dev/null | tail -1 | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); print(r['ms_per_step'], r['config']['loss'], r['roofline']['families'])" >> $out/log.txt 2>&1
+  BRATS_FOLD_BWD_STATS=$f python3 bench.py --full --model $model --precision x3 --steps 10 --warmup 3 --no-infer --no-cpu-baseline --no-parity-leg --no-other-configs 2>/dev/null | tail -1 | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); print(r['ms_per_step'], r['config']['loss'], r['roofline']['families'])" >> $out/log.txt 2>&1
 done
 done
 cat $out/log.txt

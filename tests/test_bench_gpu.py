@@ -20,7 +20,7 @@ def _bench(*args, env=None):
 
 
 def test_bench_line_contract_small_configuration():
-    r = _bench("--width", "8", "--patch", "32", "--steps", "4", "--warmup", "2", "--no-infer", "--no-cpu-baseline", "--no-parity-leg")
+    r = _bench("--full", "--width", "8", "--patch", "32", "--steps", "4", "--warmup", "2", "--no-infer", "--no-cpu-baseline", "--no-parity-leg")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "box"):
         assert k in r, k
@@ -36,8 +36,35 @@ def test_bench_line_contract_small_configuration():
     assert 1000.0 < box["mfma_TFLOPs"] < 2600.0 and 3.0 < box["stream_TBps"] < 8.0 and 1000 < box["sclk_MHz"] < 2500
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --dump-outputs writes what the last timed
+    step computed (its loss, the updated parameters and their gradients, float32), and two runs with the same arguments start
+    from the same inputs."""
+    import numpy as np
+    args = ("--width", "8", "--patch", "32", "--steps", "5", "--warmup", "2", "--dump-outputs")
+    runs = [(_bench(*args, str(tmp_path / d)), tmp_path / d) for d in ("a", "b")]
+    r, out = runs[0]
+    assert r["steps"] == 5 and r["warmup"] == 2 and r["n_gpus"] == 1 and r["dtype"] == "bf16" and r["higher_is_better"] is True
+    assert r["metric"].startswith("train patches/sec") and r["unit"] == "patches/s"
+    assert abs(r["value"] - 2 / (r["ms_per_step"] * 1e-3)) < 0.02 * r["value"]
+    for k in ("roofline", "box", "host_enqueue_ms", "inference", "parity_mode", "configs2_per_gpu", "fp16_mode", "cpu_baseline"):
+        assert k not in r, k
+    files = sorted(os.listdir(out))
+    arrays = {f: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    params = [f[len("param."):] for f in files if f.startswith("param.")]
+    assert params and all(f"grad.{p}" in arrays for p in params)
+    assert abs(float(arrays["loss.npy"]) - r["config"]["loss"]) < 1e-4  # the dump is the last TIMED step's
+    r2, out2 = runs[1]
+    assert sorted(os.listdir(out2)) == files
+    for f, a in arrays.items():
+        b = np.load(out2 / f)
+        assert a.shape == b.shape and np.linalg.norm(a - b) <= 1e-3 * np.linalg.norm(a) + 1e-6, f
+
+
 def test_bench_x3_precision_runs_the_split_kernels():
-    r = _bench("--width", "8", "--patch", "32", "--steps", "3", "--warmup", "1", "--precision", "x3", "--no-infer", "--no-cpu-baseline",
+    r = _bench("--full", "--width", "8", "--patch", "32", "--steps", "3", "--warmup", "1", "--precision", "x3", "--no-infer", "--no-cpu-baseline",
                "--no-parity-leg")
     assert r["dtype"] == "x3" and r["roofline"]["peak"] < 1000.0  # a third of the 16-bit peak: three MFMAs per product
 
@@ -46,7 +73,7 @@ def test_bench_roofline_stays_on_the_plain_kernel_beside_the_backward_statistics
     """Width 48: the blocks' second input-gradient launches carry a GroupNorm-backward pass (family conv_igemm_bst).  The
     roofline line must name a plain implicit-GEMM launch (whole work = the FLOPs in its numerator) and list the fused form
     beside it; with BRATS_FOLD_BWD_STATS=0 the family is absent."""
-    args = ("--width", "48", "--patch", "32", "--steps", "3", "--warmup", "1", "--no-infer", "--no-cpu-baseline", "--no-parity-leg")
+    args = ("--full", "--width", "48", "--patch", "32", "--steps", "3", "--warmup", "1", "--no-infer", "--no-cpu-baseline", "--no-parity-leg")
     r = _bench(*args)
     rf = r["roofline"]
     assert rf["kernel"].startswith("conv_igemm ") and "conv_igemm_bst" in rf["families"]
@@ -67,7 +94,7 @@ def test_bench_roofline_stays_on_the_plain_kernel_beside_the_backward_statistics
 def test_bench_other_stated_configurations_are_on_the_line():
     """configs[2] (ASSP-48 bf16, eager + graph), the reference's fp16 + GradScaler loop and configs[4] (ASSP-64 fp16 + e4m3) ride
     the default line as short legs; here at a 32^3 patch."""
-    r = _bench("--width", "48", "--patch", "32", "--steps", "3", "--warmup", "1", "--no-infer", "--no-cpu-baseline", "--no-parity-leg",
+    r = _bench("--full", "--width", "48", "--patch", "32", "--steps", "3", "--warmup", "1", "--no-infer", "--no-cpu-baseline", "--no-parity-leg",
                "--other-configs-patch", "32")
     for leg, dtype in (("configs2_per_gpu", "bf16"), ("fp16_mode", "fp16"), ("configs4_per_gpu", "fp16+e4m3 conv (all)")):
         assert leg in r, leg
@@ -84,7 +111,7 @@ def test_bench_two_ranks_on_one_gpu_exercise_the_ddp_block():
     patient sharding, the bucketed gradient all-reduce overlapped with the backward program and the `ddp` block of the JSON line
     (allreduce_ms, exposed_ms, overlap_frac, per-rank step times) run every round, not only on the day an 8-GPU node appears
     (VERDICT r4 item 8).  The numbers mean nothing as a scaling result: two ranks share one GPU and gloo reduces on the host."""
-    r = _bench("--gpus", "2", "--width", "8", "--patch", "32", "--steps", "6", "--warmup", "2", "--no-infer", "--no-cpu-baseline",
+    r = _bench("--full", "--gpus", "2", "--width", "8", "--patch", "32", "--steps", "6", "--warmup", "2", "--no-infer", "--no-cpu-baseline",
                "--no-parity-leg", "--no-other-configs", env={"BRATS_DIST_BACKEND": "gloo", "OMP_NUM_THREADS": "4"})
     assert r["n_gpus"] == 2 and r["config"]["global_batch"] == 4 and r["config"]["parallelism"] == "dp2" and r["scaling"] == "weak"
     assert abs(r["value"] - 4 / (r["ms_per_step"] * 1e-3)) < 0.02 * r["value"]  # whole-job patches/s = 2 ranks x 2 patches / step time
@@ -100,7 +127,7 @@ def test_bench_rccl_rehearsal_eager_headline_then_graph_leg_in_fresh_ranks():
     world-1 communicator, every bucket's all-reduce a real asynchronous RCCL launch): the eager step is the headline and carries
     the host-enqueue budget and ranks_seen in its `ddp` block; the whole step incl. the collectives as one hipGraph runs afterwards
     in a FRESH rank process started by rank 0 and lands as `graph_ddp` with its exit code (VERDICT r5 item 1 a, b, e)."""
-    r = _bench("--width", "8", "--patch", "32", "--steps", "6", "--warmup", "3", "--no-infer", "--no-cpu-baseline", "--no-parity-leg",
+    r = _bench("--full", "--width", "8", "--patch", "32", "--steps", "6", "--warmup", "3", "--no-infer", "--no-cpu-baseline", "--no-parity-leg",
                "--no-other-configs", env={"BRATS_FORCE_DDP": "rccl"})
     d = r["ddp"]
     assert d["backend"] == "nccl" and d["world_size"] == 1 and d["ranks_seen"] == 1 and d["graph_captured_collectives"] is False
@@ -117,7 +144,7 @@ def test_bench_measures_the_dominant_kernels_hbm_traffic_in_its_own_run():
     """roofline.traffic is measured by the run that prints the line -- two rocprofv3 --pmc child processes
     (FETCH_SIZE, WRITE_SIZE: separate passes) over `bench.py --pmc-leg`, the dominant kernel's launch -- and says so; the committed
     record is only the labelled fallback.  The headline's own shape (width 48, 2 x 128^3), a short run."""
-    r = _bench("--steps", "4", "--warmup", "2", "--no-infer", "--no-cpu-baseline", "--no-parity-leg", "--no-other-configs")
+    r = _bench("--full", "--steps", "4", "--warmup", "2", "--no-infer", "--no-cpu-baseline", "--no-parity-leg", "--no-other-configs")
     rf = r["roofline"]
     assert rf["kernel"] == "conv_igemm cin=48 cout=48 k=3 dil=1 @2x128x128x128"
     tp = rf["traffic_profiled"]
