@@ -4,7 +4,7 @@
 #include "conv_igemm_x3.hpp"
 
 // ---- chunk selection ---------------------------------------------------------------------------
-int g_conv_vs8_mode = -1;
+static int g_conv_vs8_mode = -1;  // -1 = BRATS_CONV_VS8 (default on), 0 / 1 = brats_conv3d_set_vs8
 extern "C" int BRATS_API(brats_conv3d_set_vs8)(int mode) {
   const int old = g_conv_vs8_mode;
   g_conv_vs8_mode = mode < 0 ? -1 : (mode ? 1 : 0);  // 0 the 4x4x16-tile kernels, 1 conv_igemm_vs8 (4x8x16 tile)
@@ -16,11 +16,11 @@ extern "C" int BRATS_API(brats_conv3d_set_kp)(int mode) {
   g_conv_kp_mode = mode < 0 ? -1 : (mode ? 1 : 0);
   return old;
 }
-static int conv_vs8_enabled() {
-  if (g_conv_vs8_mode >= 0) return g_conv_vs8_mode;
+bool conv_vs8_enabled() {
+  if (g_conv_vs8_mode >= 0) return g_conv_vs8_mode != 0;
   static int v = -1;
   if (v < 0) { const char* e = getenv("BRATS_CONV_VS8"); v = e ? atoi(e) : 1; }
-  return v;
+  return v != 0;
 }
 
 extern "C" int BRATS_API(brats_conv3d_chunk)(int dtype, int ksize, int dil, int c1, int c2, int cout) {
@@ -38,13 +38,10 @@ extern "C" int BRATS_API(brats_conv3d_chunk)(int dtype, int ksize, int dil, int 
     return 0;
   }
   // Cout = 48 (mod 96), bf16, 3x3x3 dilation 1: 24-channel chunks for the 4x8x16-tile kernel (conv_igemm_vs8.hpp)
-  if (dtype == BRATS_BF16 && ksize == 3 && dil == 1 && cout > 0 && conv_vs8_enabled() && conv_vsplit_enabled()) {
+  if (dtype == BRATS_BF16 && ksize == 3 && dil == 1 && cout > 0 && conv_vs8_enabled()) {
     const int rows16 = ceil_div(cout, 16);
     if (rows16 % 3 == 0 && rows16 % 6 != 0 && c1 % 24 == 0 && (c2 <= 0 || c2 % 24 == 0)) return 24;
   }
-  static int pref16 = -1;  // experiment switch: smaller K chunks -> smaller LDS tile -> more workgroups per CU
-  if (pref16 < 0) { const char* e = getenv("BRATS_CONV_CK16"); pref16 = e ? atoi(e) : 0; }
-  if (pref16 && dtype == BRATS_BF16 && c1 % 16 == 0 && (c2 <= 0 || c2 % 16 == 0)) return 16;
   static const int bf[] = {48, 32, 16, 8};
   static const int f32[] = {16, 8, 4};
   const int* cand = dtype == BRATS_BF16 ? bf : f32;

@@ -15,7 +15,7 @@
 // LDS; HBM/L2 sees only the ~2x halo amplification).  2 workgroups/CU overlap staging with MFMA.
 // Relatives: conv_igemm_vs8.hpp (y-split roles on a 4x8x16 tile, the default for bf16 layers with 48 mod 96 couts),
 // conv_igemm_f8.hpp (e4m3 operands), conv_igemm_x3.hpp (f32 tensors, three 16-bit MFMA products).  (Experiments that did not
-// pay -- two persistent forms, the loader-wave kernel, three workgroups per CU -- live in scripts/probes/experiments/.)
+// pay -- two persistent forms, the loader-wave kernel, three workgroups per CU -- are in scripts/probes/experiments/ at 46a6b8c.)
 #pragma once
 #include <stdlib.h>
 #include "common.hpp"
@@ -694,30 +694,20 @@ static inline bool conv_kp_enabled() {
   if (v < 0) { const char* e = getenv("BRATS_CONV_KP"); v = e ? atoi(e) : 1; }
   return v != 0;
 }
-static inline long conv_kp_max_grid() {
-  static long v = -1;
-  if (v < 0) { const char* e = getenv("BRATS_CONV_KP_GRID"); v = e ? atol(e) : 256; }
-  return v;
-}
+constexpr long CONV_KP_MAX_GRID = 256;  // workgroups
 template <typename T, int KS, int CK, int DIL, bool VS, bool PRE = false, bool BST = false>
 int conv_launch_nf3(const ConvParams& p, hipStream_t st) {
   if constexpr (std::is_same<T, bf16_t>::value && CK == 48 && KS == 3 && VS) {
     const long wgs = (long)p.N * p.tz * p.ty * p.tx * (p.rows16 / 3);
-    if (conv_kp_enabled() && wgs <= conv_kp_max_grid()) return conv_launch_one<T, KS, CK, DIL, 3, false, true, PRE, BST, true>(p, st);
+    if (conv_kp_enabled() && wgs <= CONV_KP_MAX_GRID) return conv_launch_one<T, KS, CK, DIL, 3, false, true, PRE, BST, true>(p, st);
   }
   return conv_launch_one<T, KS, CK, DIL, 3, false, VS, PRE, BST, false>(p, st);
 }
 
-static inline bool conv_vsplit_enabled() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("BRATS_CONV_VSPLIT"); v = e ? atoi(e) : 1; }
-  return v != 0;
-}
-static inline long conv_small_grid_threshold() {
-  static long v = -1;
-  if (v < 0) { const char* e = getenv("BRATS_CONV_SMALLGRID"); v = e ? atol(e) : 200; }
-  return v;
-}
+// the 4x8x16-tile kernel (conv_igemm_vs8.hpp) for the layers of its shape: BRATS_CONV_VS8 / brats_conv3d_set_vs8 (conv_host.hip)
+bool conv_vs8_enabled();
+// the 96-cout tiles of a 16-bit layer give fewer workgroups than this: the y-split roles instead (conv_launch_ck)
+constexpr long CONV_SMALL_GRID = 200;
 struct ConvTileChoice { int nf; bool ksplit; int nfw; };
 static inline ConvTileChoice conv_choose_tile(int rows16) {
   if (rows16 % 6 == 0) return {3, false, 6};
@@ -733,14 +723,13 @@ int conv_launch_ck(const ConvParams& p, hipStream_t st) {
   if (t.nf == 3 && !t.ksplit) {
     // small volumes (16^3 levels): 96-cout tiles give fewer workgroups than CUs; the y-split roles (48 couts per
     // workgroup) double the grid at the price of staging each halo tile twice
-    if (std::is_same<T, bf16_t>::value && conv_vsplit_enabled() &&
-        (long)p.N * p.tz * p.ty * p.tx * (p.rows16 / 6) < conv_small_grid_threshold())
+    if (std::is_same<T, bf16_t>::value && (long)p.N * p.tz * p.ty * p.tx * (p.rows16 / 6) < CONV_SMALL_GRID)
       return conv_launch_nf3<T, KS, CK, DIL, true, PRE>(p, st);
     return conv_launch_one<T, KS, CK, DIL, 3, false, false, PRE>(p, st);
   }
   if (t.nf == 3 && t.ksplit) {
-    // Cout = 48 (mod 96): the y-split roles (no K reduction, shared epilogue) for bf16; K-split stays for f32 / opt-out
-    if (std::is_same<T, bf16_t>::value && conv_vsplit_enabled()) return conv_launch_nf3<T, KS, CK, DIL, true, PRE>(p, st);
+    // Cout = 48 (mod 96): the y-split roles (no K reduction, shared epilogue) for bf16; K-split stays for f32
+    if (std::is_same<T, bf16_t>::value) return conv_launch_nf3<T, KS, CK, DIL, true, PRE>(p, st);
     return conv_launch_one<T, KS, CK, DIL, 3, true, false, PRE>(p, st);
   }
   if (t.nf == 2 && !t.ksplit) return conv_launch_one<T, KS, CK, DIL, 2, false, false, PRE>(p, st);

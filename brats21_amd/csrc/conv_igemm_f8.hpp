@@ -331,7 +331,7 @@ template <int CK, int DIL>
 int conv_f8_launch_ck(const ConvF8Params& p, hipStream_t st) {
   const int r16 = p.c.rows16;
   if (r16 % 6 == 0) {
-    if ((long)p.c.N * p.c.tz * p.c.ty * p.c.tx * (r16 / 6) < conv_small_grid_threshold()) return conv_f8_launch_one<CK, DIL, 3, true>(p, st);
+    if ((long)p.c.N * p.c.tz * p.c.ty * p.c.tx * (r16 / 6) < CONV_SMALL_GRID) return conv_f8_launch_one<CK, DIL, 3, true>(p, st);
     return conv_f8_launch_one<CK, DIL, 3, false>(p, st);
   }
   if (r16 % 3 == 0) return conv_f8_launch_one<CK, DIL, 3, true>(p, st);

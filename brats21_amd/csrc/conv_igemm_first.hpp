@@ -199,9 +199,7 @@ __global__ __launch_bounds__(256, 2) void conv_first_kernel(const ConvParams p, 
 
 // the layer this kernel is built for: one 8-channel chunk, exactly 48 output channels in a dense tensor, whole 4x4x16 tiles
 static inline bool conv_first_ok(const ConvParams& p, int ck) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("BRATS_CONV_FIRST"); on = e ? atoi(e) : 1; }
-  return on && ck == 8 && p.nchunks == 1 && p.c2 == 0 && p.stats && p.cout == 48 && p.rows16 == 3 && p.ypitch == 48 && !p.y2 && p.D % 4 == 0 &&
+  return ck == 8 && p.nchunks == 1 && p.c2 == 0 && p.stats && p.cout == 48 && p.rows16 == 3 && p.ypitch == 48 && !p.y2 && p.D % 4 == 0 &&
          p.H % 4 == 0 && p.W % 16 == 0 && ((size_t)p.y & 15) == 0 && (!p.bias || ((size_t)p.bias & 15) == 0) &&
          (long)p.N * p.tz * p.ty * p.tx >= 2048;
 }

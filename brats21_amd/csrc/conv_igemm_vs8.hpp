@@ -195,7 +195,7 @@ DEVI void vs8_epilogue_stats(const ConvParams& p, int ty4, const float* sred, in
 }
 
 // (Three workgroups per CU -- a 168-register build on a ring form of the MMA loop -- measured 0.39 -> 0.57 ms in round 3:
-// scripts/probes/experiments/conv_igemm_ld.hpp keeps that loop.)
+// scripts/probes/experiments/conv_igemm_ld.hpp at 46a6b8c has that loop.)
 // PRE: normalise + activate on load (inference; conv_igemm.hpp: conv_pre_apply)
 // BST: backward statistics in the epilogue (ConvParams::by / bss; training, the input gradient of a block's second unit)
 template <int CK, int DIL, int NF, bool PRE = false, bool BST = false>
@@ -333,14 +333,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_vs8_kernel(const ConvParams
     __syncthreads();
     vs8_epilogue_stats<NF>(p, ty4, sred, tid, n, tzi, tyi, txi, ct);
   }
-}
-
-extern int g_conv_vs8_mode;  // conv_host.hip: -1 = BRATS_CONV_VS8 (default on), 0 / 1 = brats_conv3d_set_vs8
-static inline int conv_vs8_mode() {
-  if (g_conv_vs8_mode >= 0) return g_conv_vs8_mode;
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("BRATS_CONV_VS8"); v = e ? atoi(e) : 1; }
-  return v;
 }
 
 template <int CK, int DIL, int NF, bool PRE = false, bool BST = false>

@@ -385,22 +385,15 @@ int conv_x3_launch_one(const ConvParams& p0, hipStream_t st) {
   return 0;
 }
 
-inline int conv_x3_ty8_enabled() {
-  static int ty8 = -1;
-  if (ty8 < 0) { const char* e = getenv("BRATS_X3_TY8"); ty8 = e ? atoi(e) : 1; }
-  return ty8;
-}
-
 // tile choice: the cout-half roles where the layer has an even number of NF-fragment groups, the y-split roles otherwise
 // (and for small grids, as conv_launch_ck does); conv_choose_tile()'s nf, so brats_conv3d_split_granule() holds here too
 template <int KS, int CK, int DIL>
 int conv_x3_launch_ck(const ConvParams& p, hipStream_t st) {
   const ConvTileChoice t = conv_choose_tile(p.rows16);
-  const bool small = (long)p.N * p.tz * p.ty * p.tx * (p.rows16 / (2 * t.nf) > 0 ? p.rows16 / (2 * t.nf) : 1) < conv_small_grid_threshold();
+  const bool small = (long)p.N * p.tz * p.ty * p.tx * (p.rows16 / (2 * t.nf) > 0 ? p.rows16 / (2 * t.nf) : 1) < CONV_SMALL_GRID;
   if constexpr (CK == 16 && DIL == 1) {
-    // Cout = 48 (mod 96), big volumes: the y-split roles on the 4x8x16 tile (BRATS_X3_TY8=0: the 4x4x16 tile, for A/B runs)
-    const int ty8 = conv_x3_ty8_enabled();
-    if (ty8 && t.nf == 3 && t.ksplit && (long)p.N * p.tz * p.ty * p.tx >= 2048) return conv_x3_launch_one<KS, CK, DIL, 3, true, 8>(p, st);
+    // Cout = 48 (mod 96), big volumes: the y-split roles on the 4x8x16 tile
+    if (t.nf == 3 && t.ksplit && (long)p.N * p.tz * p.ty * p.tx >= 2048) return conv_x3_launch_one<KS, CK, DIL, 3, true, 8>(p, st);
   }
   if (t.nf == 3) return (t.ksplit || small) ? conv_x3_launch_one<KS, CK, DIL, 3, true>(p, st) : conv_x3_launch_one<KS, CK, DIL, 3, false>(p, st);
   if (t.nf == 2) return (t.ksplit || small) ? conv_x3_launch_one<KS, CK, DIL, 2, true>(p, st) : conv_x3_launch_one<KS, CK, DIL, 2, false>(p, st);
@@ -416,7 +409,7 @@ inline bool conv_x3_bst_supported(int ck, int dil, int rows16) {
 }
 template <int DIL>
 int conv_x3_bst_launch_ck24(const ConvParams& p, hipStream_t st) {  // conv_x3_launch_ck's choice among the NF = 3 roles
-  const bool small = (long)p.N * p.tz * p.ty * p.tx * (p.rows16 / 6) < conv_small_grid_threshold();
+  const bool small = (long)p.N * p.tz * p.ty * p.tx * (p.rows16 / 6) < CONV_SMALL_GRID;
   return small ? conv_x3_launch_one<3, 24, DIL, 3, true, CONV_TY, true>(p, st) : conv_x3_launch_one<3, 24, DIL, 3, false, CONV_TY, true>(p, st);
 }
 int conv_x3_bst_launch(const ConvParams& p, int ck, int dil, hipStream_t st);  // conv_x3_k3_bst.hip

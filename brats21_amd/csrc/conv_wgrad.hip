@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
 // (11 pairs x 3 co-fragments = 132 accumulator registers per lane, kept across all tiles of the workgroup);
 // the next tile's 87 KB are prefetched into registers (11 x 16 B per lane) during the MFMA phase.
 // CIF = ci fragments of the channel block: 3 (48 input channels) or 1 (the first layer: <= 16 input channels, 16-channel
-// LDS rows of which only the real ones are fetched)
+// LDS rows of which only the real ones are fetched).  Only CIF = 1 launches: the 48 x 48 block runs on the second form below
 // COF = co fragments of the block: 3 (48 output channels), or 4 for the FIRST layer of the width-64 networks (8 -> 64: round 5; the
 // dY voxel stride is then padded from 128 to 160 bytes, the next conflict-free value for the transposing reads)
 template <int CIF, int COF = 3> struct Wg3 {
@@ -1192,23 +1192,16 @@ static int wgrad_mfma(const void* x1, int c1, int pitch1, const void* x2, int c2
   if (alltaps) {
     p.nsplit = p.nlane * g8a;
     constexpr int lds_48 = Wg3b<3, 3>::LDS, lds_wide = Wg3b<4, 2>::LDS;
-    static std::atomic<uint64_t> attr_a{0}, attr_b{0}, attr_c{0}, attr_d{0};
-    BRATS_ENSURE_LDS_ATTR(conv_wgrad_alltaps_kernel<3>, Wg3<3>::LDS, attr_a);
+    static std::atomic<uint64_t> attr_b{0}, attr_c{0}, attr_d{0}, attr_e{0};
     BRATS_ENSURE_LDS_ATTR(conv_wgrad_alltaps_kernel<1>, Wg3<1>::LDS, attr_b);
-    static std::atomic<uint64_t> attr_e{0};
     BRATS_ENSURE_LDS_ATTR((conv_wgrad_alltaps_kernel<1, 4>), (Wg3<1, 4>::LDS), attr_e);
     BRATS_ENSURE_LDS_ATTR((conv_wgrad_alltaps2_kernel<3, 3>), lds_48, attr_c);
     BRATS_ENSURE_LDS_ATTR((conv_wgrad_alltaps2_kernel<4, 2>), lds_wide, attr_d);
-    static int form = -1;  // BRATS_WGRAD_ALLTAPS=1: the round-1 form (register staging, one X buffer) for same-box A/B runs
-    if (form < 0) {
-      const char* e = getenv("BRATS_WGRAD_ALLTAPS");
-      form = (e && atoi(e) == 1) ? 1 : 2;
-    }
     if (wide && c2 <= 0 && c1 <= 16) {
       hipLaunchKernelGGL((conv_wgrad_alltaps_kernel<1, 4>), dim3(p.nsplit, cout / 64, 1), dim3(512), (Wg3<1, 4>::LDS), st, p);
     } else if (wide) {
       hipLaunchKernelGGL((conv_wgrad_alltaps2_kernel<4, 2>), dim3(p.nsplit, cout / 64, p.cin / 32), dim3(512), lds_wide, st, p);
-    } else if (c2 <= 0 && c1 <= 16 && form != 1 && c1 % 8 == 0) {
+    } else if (c2 <= 0 && c1 <= 16 && c1 % 8 == 0) {
       // the first layer on the LDS-DMA form (round 6): two X buffers of 16-channel rows, the next tile's loads in flight behind
       // the MFMA phase -- this layer is all loads (dY: 24 KB per tile against 1.5 k cycles of MFMA per wave)
       static std::atomic<uint64_t> attr_f{0};
@@ -1217,8 +1210,6 @@ static int wgrad_mfma(const void* x1, int c1, int pitch1, const void* x2, int c2
     } else if (c2 <= 0 && c1 <= 16) {
       // the slab columns of the padded ci lanes (c1 < 16) are never written and never read (cin = c1)
       hipLaunchKernelGGL(conv_wgrad_alltaps_kernel<1>, dim3(p.nsplit, cout / 48, 1), dim3(512), Wg3<1>::LDS, st, p);
-    } else if (form == 1) {
-      hipLaunchKernelGGL(conv_wgrad_alltaps_kernel<3>, dim3(p.nsplit, cout / 48, p.cin / 48), dim3(512), Wg3<3>::LDS, st, p);
     } else {
       hipLaunchKernelGGL((conv_wgrad_alltaps2_kernel<3, 3>), dim3(p.nsplit, cout / 48, p.cin / 48), dim3(512), lds_48, st, p);
     }

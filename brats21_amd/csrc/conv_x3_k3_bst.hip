@@ -10,7 +10,7 @@ int conv_x3_bst_launch(const ConvParams& p, int ck, int dil, hipStream_t st) {
   if (!conv_x3_bst_supported(ck, dil, p.rows16))
     BRATS_FAIL(BRATS_E_UNSUPPORTED, "conv3d_x3_fwd_bstats: chunk %d, dilation %d, %d output rows", ck, dil, p.rows16 * 16);
   if (ck == 16) {  // conv_x3_launch_ck's choice for Cout = 48 (mod 96)
-    if (conv_x3_ty8_enabled() && (long)p.N * p.tz * p.ty * p.tx >= 2048) return conv_x3_launch_one<3, 16, 1, 3, true, 8, true>(p, st);
+    if ((long)p.N * p.tz * p.ty * p.tx >= 2048) return conv_x3_launch_one<3, 16, 1, 3, true, 8, true>(p, st);
     return conv_x3_launch_one<3, 16, 1, 3, true, CONV_TY, true>(p, st);
   }
   return dil == 1 ? conv_x3_bst_launch_ck24<1>(p, st) : conv_x3_bst_launch_ck24<2>(p, st);

@@ -9,9 +9,6 @@
 // beyond the Infinity Cache (256 MB): non-temporal streaming on more, shorter-lived blocks (common.hpp stream_nt); f32 tensors are
 // the split-precision mode's (2 x 128^3 x 48 x 4 B = 805 MB)
 static inline bool big_tensor(int dtype, size_t elems) {
-#ifdef BRATS_NO_F32_NT  // (A/B builds)
-  if (dtype != BRATS_BF16) return false;
-#endif
   return stream_nt(elems * (dtype == BRATS_BF16 ? 2 : 4));
 }
 #include "se.hpp"

@@ -358,7 +358,7 @@ def _cgr_fwd(unit, x, dtype, act, out=None, x2=None, fp8=None, slots=None, no_ac
     return z, (unit, x, x2, y, mean_rstd, scale_shift)
 
 
-def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=None, slots=None, side=None, dest=None, head=None,
+def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=None, slots=None, dest=None, head=None,
              pool=None, bst=None, drop=None):
     """Returns dx, or (dx1, dx2) -- two dense tensors from one dgrad launch -- for a two-source unit.
     bst: the record of the unit that PRODUCED this unit's input (the first unit of the block).  Where the kernel form is built,
@@ -427,22 +427,14 @@ def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=Non
                                            slope_t=slope_t)
     # data-parallel: the weight gradient is written straight into its slice of the all-reduce bucket
     wdst = dest(names[unit.conv.weight]) if dest is not None else None
-    # (model.wgrad_stream = "small": only the 16^3 / 32^3 levels, whose weight-gradient grids are <= 1 workgroup per CU and leave
-    #  most of the chip idle beside the next layer's equally small input-gradient launch)
-    if side is not None and getattr(unit, "_side_small_only", False) and x.shape[1] > 32:
-        side = None
-    with ops.side_stream(side, dy, x, x2) as on_side:
-        # (the weight gradient depends only on dy and the saved input and nobody but the optimizer waits for it: on the
-        # side stream it fills the CUs that the tail of the input-gradient kernel and the small GroupNorm launches leave idle)
-        if w8 and amax is not None:
-            dw = ops.conv3d_wgrad_f8(x, dy, ax, amax, x2=x2, amax2=ax2, out=wdst)
-        elif x2 is not None and x.shape[-1] % 16:  # narrow test widths only: the wgrad ci tile (16) would straddle x | x2
-            dw, db = ops.conv3d_wgrad(torch.cat([x, x2], -1), dy, 3, unit.dilation, amax_dy=amax if x3s else None, want_dbias=unit.bcn)
-        else:
-            dw, db = ops.conv3d_wgrad(x, dy, 3, unit.dilation, x2=x2, out=None if unit.bcn else wdst, amax_dy=amax if x3s else None,
-                                      want_dbias=unit.bcn)
-        dw = dw[:, :cin].contiguous() if dw.shape[1] != cin else dw
-        on_side(dw)
+    if w8 and amax is not None:
+        dw = ops.conv3d_wgrad_f8(x, dy, ax, amax, x2=x2, amax2=ax2, out=wdst)
+    elif x2 is not None and x.shape[-1] % 16:  # narrow test widths only: the wgrad ci tile (16) would straddle x | x2
+        dw, db = ops.conv3d_wgrad(torch.cat([x, x2], -1), dy, 3, unit.dilation, amax_dy=amax if x3s else None, want_dbias=unit.bcn)
+    else:
+        dw, db = ops.conv3d_wgrad(x, dy, 3, unit.dilation, x2=x2, out=None if unit.bcn else wdst, amax_dy=amax if x3s else None,
+                                  want_dbias=unit.bcn)
+    dw = dw[:, :cin].contiguous() if dw.shape[1] != cin else dw
     if unit.bcn:
         pg = _bcn_param_grads(unit, dw, db, dgamma, dbeta)  # dw / db are the gradients of a_c * W and b_c
     else:
@@ -602,12 +594,6 @@ class _EquiUnetFn(torch.autograd.Function):
         fp8 = m.conv_fp8 if ops.is16(dtype) else None
         slots = _AmaxSlots(32, douts[0].device) if (fp8 == "all" or ops.x3_mode() == ops.X3F) else None
 
-        # weight gradients on a side stream (model.wgrad_stream); with gradient buckets they stay on the main stream: the
-        # buckets' copies and collectives are ordered against it
-        side = ops.get_side_stream(douts[0].device) if (m.wgrad_stream and m._grad_sink is None) else None
-        for u in rec:
-            u._side_small_only = m.wgrad_stream == "small"
-
         drop_state = ctx.drop_state  # dropout: the folds that never materialise a unit's output gradient are off
 
         def cbw(unit, dz, need_dx=True, head=None, pool=None, first=None):
@@ -615,7 +601,7 @@ class _EquiUnetFn(torch.autograd.Function):
             # in this unit's input-gradient launch (model.fold_bwd_stats)
             bst = rec[first] if (first is not None and m.fold_bwd_stats and drop_state is None) else None
             drop = (m.dropout_p, drop_state, m._unit_ids[unit]) if drop_state is not None else None
-            return _cgr_bwd(rec[unit], dz, dtype, act, grads, names, need_dx, m._grad_sink, fp8, slots, side, m._grad_dest, head, pool, bst,
+            return _cgr_bwd(rec[unit], dz, dtype, act, grads, names, need_dx, m._grad_sink, fp8, slots, m._grad_dest, head, pool, bst,
                             drop)
 
         def level_bwd(unit, down, d_pooled, d_skip, need_dx=True, first=None):
@@ -680,8 +666,6 @@ class _EquiUnetFn(torch.autograd.Function):
         d_p1 = cbw(c1, level_bwd(c2, down2, d_p2, d_skip2, first=c1))
         c1, c2 = blk(m.encoder1)
         cbw(c1, level_bwd(c2, down1, d_p1, d_skip1, first=c1), need_dx=False)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)  # every weight gradient is complete before autograd hands them on
         ctx.tape = ctx.bufs = None
         return (None, None, None) + tuple(grads.get(i) for i in range(ctx.nparams))
 
@@ -720,11 +704,6 @@ class EquiUnet(_PackedWeightsModule):
         # inference (no_grad, 16-bit): the activation between the two convolutions of a block is applied on load by the second
         # one and never stored (ops.Pending / brats_conv3d_fwd_pre); BRATS_NORM_ON_LOAD=0: the two-pass path, for A/B runs
         self.norm_on_load = os.environ.get("BRATS_NORM_ON_LOAD", "1") != "0"
-        # weight gradients on a second HIP stream (they depend only on dy and the saved input).  Off: measured 16.40 ->
-        # 16.63 ms / step same-box -- the all-taps kernel owns a CU's whole LDS, so the two streams only take CUs from
-        # each other, and the tails they could fill are shorter than the interference they add
-        ws = os.environ.get("BRATS_WGRAD_STREAM", "0")
-        self.wgrad_stream = "small" if ws == "small" else ws != "0"
         self._grad_sink = None  # set by brats21_amd.ddp.GradientBuckets
         self._grad_dest = None  # (ditto: parameter index -> its slice of an all-reduce bucket, or None)
         # training: one multi-tensor weight-packing launch per step (ops.PackPlan).  Off by default here: this network's

@@ -50,7 +50,7 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
 /* THE version: brats_abi_version() returns this define, the Python binding (brats21_amd/_lib.py) and tests/test_abi_cpu.py parse
  * it.  History: 2 since round 3 (a changed signature, brats_maxpool2_fwd); 3 in round 4 (additions only); 4 in round 4 (the block
  * table of brats_conv3d_pack_weights_multi changed meaning); 5 in round 5 (additions only: brats_conv3d_set_x3_wgrad_fused,
- * brats_dropout, brats_evonorm_bwd_tiles + its workspace query). */
+ * brats_dropout, brats_evonorm_bwd_tiles + its workspace query); 6 in round 6 (additions only: brats_conv3d_set_kp). */
 #define BRATS_ABI_VERSION 6
 int brats_abi_version(void);
 const char* brats_last_error(void);
@@ -115,7 +115,7 @@ int brats_conv3d_split_granule(int cout);
  * (conv_igemm_vs8.hpp), 0 = 48-channel chunks + the 4x4x16-tile kernels, -1 = default (BRATS_CONV_VS8, on).  The setting
  * changes brats_conv3d_chunk(), i.e. the packed-weight layout: weights must be packed under the same setting they are
  * used with (the Python side offers ops.set_vs8(), which also drops its packed-weight caches).  Returns the previous setting.
- * (Round 3's mode 2, the loader-wave kernel, measured slower and left the library: scripts/probes/experiments/.) */
+ * (Round 3's mode 2, the loader-wave kernel, measured slower and left the library: scripts/probes/experiments/ at 46a6b8c.) */
 int brats_conv3d_set_vs8(int mode);
 /* 16-bit 3x3x3 launches of at most one workgroup per CU (the 16^3 level: 32 tiles) with 48-channel chunks and the 48-cout
  * y-split roles: 1 = the 8-wave form (two K-parity teams of four waves per workgroup on one LDS tile and one output tile, team 1's

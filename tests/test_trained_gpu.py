@@ -23,7 +23,7 @@ those weights and on volumes the training never saw:
     bf16 / fp16 against the same chain in f32, whose network arithmetic the stitched-logit check has just pinned.
 The 320-step training runs reproduce BIT FOR BIT across runs and boxes (every reduction of the step is ordered; checked: two
 runs on one box and a third on another print identical loss curves and Dice values), so the margins below are properties of the tree,
-not of the lease.  The numbers land in profiles/ through scripts/r5_final.sh (pytest -s)."""
+not of the lease.  The numbers land in profiles/ through a `pytest -s` run of this module."""
 import argparse
 import contextlib
 import io
@@ -156,7 +156,7 @@ def test_trained_patch_logits_and_dice_vs_oracle(model):
             assert res[prec][0] <= DICE_ATOL, (contrast, prec, res[prec])
 
 
-# the whole sweep (five weight sets per network, ~7 minutes) runs with BRATS_SWEEP_FULL=1 -- scripts/r6_final.sh, whose output is
+# the whole sweep (five weight sets per network, ~7 minutes) runs with BRATS_SWEEP_FULL=1 -- round 6's output of it is
 # profiles/r06_final_trained_weights_parity.txt; the default GPU suite takes the first two weight sets (the same asserts)
 SWEEP_SEEDS = (1, 2, 3, 4, 5) if os.environ.get("BRATS_SWEEP_FULL", "0") == "1" else (1, 2)
 SWEEP_STEPS = {"equiunet": 560, "equiunet_assp_evo": 320}
