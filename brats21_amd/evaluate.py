@@ -7,12 +7,26 @@ label map / metric scalars leave the GPU.
 
 Function names and argument meaning follow utils/transforms.py (shape_to_divisible :482, shape_to_original :515,
 remove_background_voxels :536) so Engine.evaluate can import them unchanged.
+
+The reference's optional label post-processing (--cleaning_areas / --replace_value, src/definer.py:679-694) is here too:
+KeepLargestConnectedComponent and ReplaceWithClosestValue (utils/transforms.py:209-268) run as HIP kernels
+(csrc/postproc.hip), and get_post_transforms / Evaluator(cleaning_areas_threshold=, replace_value_threshold=) chain them
+like the reference does.  Where the GPU form differs from the reference:
+  1. ReplaceWithClosestValue: of several pixels of DIFFERENT values at the same nearest distance, the reference's pick
+     depends on scipy's KD-tree; here the one first in the slice's row-major order wins (deterministic).
+  2. KeepLargestConnectedComponent(None) on a map without foreground returns it unchanged (the reference raises ValueError).
+  3. Both always return a float32 tensor on the input's device (the reference returns a uint8 numpy array when it replaced
+     something).
+  4. A volume without a single background voxel is outside the contract (the reference assumes label 0 exists).
 """
+import numbers
+
 import numpy as np
 import torch
 
 from . import _lib
 from .inferers import GraphedPredictor, _first, sliding_window_inference
+from .transforms import convert_to_multichannel
 
 
 def _stream():
@@ -114,6 +128,120 @@ def hard_dice_metric(pred, target):
     return dice.float()
 
 
+_INT_MAX = 2 ** 31 - 1
+
+
+def _check_int(value, what, allow_none=False):
+    if value is None and allow_none:
+        return
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral):
+        raise TypeError(f"{what} must be an int{' or None' if allow_none else ''}, got {value!r}")
+
+
+def _clean_labels_(lab, threshold):
+    """In place on uint8 [N, D, H, W] (cuda, contiguous): keep the 26-connected components of more than `threshold`
+    voxels, or only the largest one when threshold is None."""
+    n, d, h, w = lab.shape
+    ws = torch.empty(_lib.lib().brats_cc_ws_bytes(n, d, h, w), dtype=torch.uint8, device=lab.device)
+    min_size = -1 if threshold is None else min(max(int(threshold), 0), _INT_MAX)
+    _lib.check(_lib.lib().brats_cc_filter(lab.data_ptr(), n, d, h, w, min_size, ws.data_ptr(), _stream()), "cc_filter")
+
+
+def _replace_rare_labels_(lab, threshold, axis):
+    """In place on uint8 [N, D, H, W] (cuda, contiguous): values with at most `threshold` voxels take the nearest
+    non-rare value of their slice along `axis`."""
+    n, d, h, w = lab.shape
+    ws = torch.empty(_lib.lib().brats_rare_fill_ws_bytes(n, d, h, w), dtype=torch.uint8, device=lab.device)
+    max_count = min(max(int(threshold), -1), _INT_MAX)
+    _lib.check(_lib.lib().brats_rare_fill(lab.data_ptr(), n, d, h, w, int(axis), max_count, ws.data_ptr(), _stream()),
+               "rare_fill")
+
+
+def _on_label_map(data, fn):
+    """[1, 1, D, H, W] / [N, 1, D, H, W] / [D, H, W] label map (float or uint8, CPU or CUDA) -> fn(uint8 [N, D, H, W] copy
+    on the GPU) -> float32 in the input's shape on the input's device."""
+    if not torch.is_tensor(data):
+        raise TypeError(f"expected a torch.Tensor label map, got {type(data).__name__}")
+    if not (data.dim() == 3 or (data.dim() == 5 and data.shape[1] == 1)):
+        raise ValueError(f"label map must be [N, 1, D, H, W] or [D, H, W], got {tuple(data.shape)}")
+    x = data if data.is_cuda else data.to(torch.device("cuda", torch.cuda.current_device()))
+    with torch.cuda.device(x.device):
+        lab = x.reshape((-1,) + tuple(x.shape[-3:])).to(torch.uint8, copy=True).contiguous()
+        fn(lab)
+        out = lab.float().reshape(data.shape)
+    return out if data.is_cuda else out.to(data.device)
+
+
+class KeepLargestConnectedComponent:
+    """utils/transforms.py:209-230 (get_largest_component, :579-600) on the GPU, per sample: the 26-connected components
+    of labels != 0 with more than `threshold` voxels are kept (threshold <= 0 keeps all), or only the largest one when
+    threshold is None (ties: the component whose first voxel comes first in C order); kept voxels keep their value.
+    Differs from the reference only where the module docstring says (items 2-4)."""
+
+    def __init__(self, threshold=None):
+        _check_int(threshold, "threshold", allow_none=True)
+        self.threshold = threshold
+
+    def __call__(self, data):
+        return _on_label_map(data, lambda lab: _clean_labels_(lab, self.threshold))
+
+
+class ReplaceWithClosestValue:
+    """utils/transforms.py:233-268 (replace_w_closest_value_3d, :603-647) on the GPU, per sample: values occurring at most
+    `thresh` times (0 included) are rare; if a non-zero value is rare, every rare pixel of each slice along `axis`
+    (2 = W: the (D, H) planes) takes the value of the nearest non-rare pixel of that slice (exact Euclidean distance),
+    or 0 where the slice has none.  `labels` is accepted and ignored, as by the reference.  Ties between different values
+    at the same distance: the pixel first in the slice's row-major order (module docstring, item 1)."""
+
+    def __init__(self, labels=None, thresh=20, axis=2):
+        _check_int(thresh, "thresh")
+        if isinstance(axis, bool) or not isinstance(axis, numbers.Integral) or not 0 <= axis <= 2:
+            raise ValueError(f"axis must be 0, 1 or 2, got {axis!r}")
+        self.labels, self.thresh, self.axis = labels, thresh, int(axis)
+
+    def __call__(self, data):
+        return _on_label_map(data, lambda lab: _replace_rare_labels_(lab, self.thresh, self.axis))
+
+
+def _post_chain(prob, passes, thresh, cleaning_threshold=None, clean=False, replace_threshold=None, replace=False):
+    """get_post_transforms (src/definer.py:679-694) on [N, 3, D, H, W] probability sums (cuda): mean over `passes` ->
+    AsDiscrete(>= thresh) -> BraTS labels -> [KeepLargestConnectedComponent] -> [ReplaceWithClosestValue(axis=2)] ->
+    TC / WT / ET channels, f32 0/1.  Without either step it is the threshold alone.  No background removal: Engine.evaluate
+    applies it after this chain (learning/engine.py:259), so cleaning sees the predictions on zero-image voxels too."""
+    if not (clean or replace):
+        return finalize_segmentation(prob, passes, None, thresh)
+    _, labels = finalize_segmentation(prob, passes, None, thresh, want_labels=True)
+    lab = labels[:, 0]
+    if clean:
+        _clean_labels_(lab, cleaning_threshold)
+    if replace:
+        _replace_rare_labels_(lab, replace_threshold, 2)
+    return convert_to_multichannel(labels.float(), order="monai")
+
+
+def get_post_transforms(args):
+    """Drop-in for src/definer.py:671-698 (same attributes, same hasattr defaults): returns a callable mapping the mean
+    probability [N, 3, D, H, W] (CPU or CUDA) to 0/1 float32 TC / WT / ET maps on the input's device.  The work runs on
+    the GPU; a CPU input is copied there and back."""
+    thresh = 0.5 if not hasattr(args, "logit_threshold") else args.logit_threshold
+    clean = hasattr(args, "cleaning_areas") and args.cleaning_areas
+    replace = hasattr(args, "replace_value") and args.replace_value
+    kw = {}
+    if clean:
+        _check_int(args.cleaning_areas_threshold, "cleaning_areas_threshold", allow_none=True)
+        kw.update(clean=True, cleaning_threshold=args.cleaning_areas_threshold)
+    if replace:
+        _check_int(args.replace_value_threshold, "replace_value_threshold")
+        kw.update(replace=True, replace_threshold=args.replace_value_threshold)
+
+    def post(mean):
+        x = mean if mean.is_cuda else mean.to(torch.device("cuda", torch.cuda.current_device()))
+        with torch.cuda.device(x.device):
+            out = _post_chain(x, 1, float(thresh), **kw)
+        return out if mean.is_cuda else out.to(mean.device)
+    return post
+
+
 class Evaluator:
     """The per-case body of Engine.evaluate (learning/engine.py:205-285) for one or several models:
     pad to k -> [TTA x] (sliding window | whole volume) -> on-GPU mean of sigmoid -> threshold ->
@@ -123,10 +251,20 @@ class Evaluator:
     captured into a hipGraph once and replayed; the graphs follow the models' weights (GraphedPredictor re-captures when
     a parameter's address / version or ops' packed-weight generation changed).  Whole-volume evaluation
     (sliding_window_size=None, the reference's default path) sees a different padded shape for almost every case, so
-    it runs eagerly unless use_graph=True is passed explicitly (then at most ``max_graphs`` shapes stay captured)."""
+    it runs eagerly unless use_graph=True is passed explicitly (then at most ``max_graphs`` shapes stay captured).
+
+    ``cleaning_areas_threshold`` / ``replace_value_threshold`` (default None = off) are the reference's
+    ``--cleaning_areas --cleaning_areas_threshold T`` / ``--replace_value --replace_value_threshold T``: with either set,
+    the chain is threshold -> labels -> KeepLargestConnectedComponent(T) -> ReplaceWithClosestValue(T, axis=2) ->
+    channels -> background removal -> Dice / labels / crop, in the reference's order (get_post_transforms runs before
+    remove_background_voxels, learning/engine.py:244-259)."""
 
     def __init__(self, models, tta_transforms=None, sliding_window_size=None, sw_batch_size=1, overlap=0.25,
-                 k_divisible=8, thresh=0.5, amp=True, use_graph=None, max_graphs=4, amp_dtype=torch.bfloat16):
+                 k_divisible=8, thresh=0.5, amp=True, use_graph=None, max_graphs=4, amp_dtype=torch.bfloat16,
+                 cleaning_areas_threshold=None, replace_value_threshold=None):
+        _check_int(cleaning_areas_threshold, "cleaning_areas_threshold", allow_none=True)
+        _check_int(replace_value_threshold, "replace_value_threshold", allow_none=True)
+        self.clean_t, self.replace_t = cleaning_areas_threshold, replace_value_threshold
         self.models = list(models) if isinstance(models, (list, tuple)) else [models]
         self.tta, self.roi, self.swb, self.overlap = tta_transforms, sliding_window_size, sw_batch_size, overlap
         self.k, self.thresh, self.amp, self.amp_dtype = k_divisible, thresh, amp, amp_dtype
@@ -172,7 +310,12 @@ class Evaluator:
         _need_cuda(image, "Evaluator")
         padded, p_b, p_a = shape_to_divisible(image, k=self.k)
         acc, passes = self.probability_sum(padded)
-        res = finalize_segmentation(acc, passes, padded, self.thresh, want_labels)
+        if self.clean_t is None and self.replace_t is None:
+            res = finalize_segmentation(acc, passes, padded, self.thresh, want_labels)
+        else:
+            seg = _post_chain(acc, passes, self.thresh, cleaning_threshold=self.clean_t, clean=self.clean_t is not None,
+                              replace_threshold=self.replace_t, replace=self.replace_t is not None)
+            res = finalize_segmentation(seg, 1, padded, 0.5, want_labels)
         seg, labels = res if want_labels else (res, None)
         out = {}
         if target is not None:

@@ -50,8 +50,9 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
 /* THE version: brats_abi_version() returns this define, the Python binding (brats21_amd/_lib.py) and tests/test_abi_cpu.py parse
  * it.  History: 2 since round 3 (a changed signature, brats_maxpool2_fwd); 3 in round 4 (additions only); 4 in round 4 (the block
  * table of brats_conv3d_pack_weights_multi changed meaning); 5 in round 5 (additions only: brats_conv3d_set_x3_wgrad_fused,
- * brats_dropout, brats_evonorm_bwd_tiles + its workspace query); 6 in round 6 (additions only: brats_conv3d_set_kp). */
-#define BRATS_ABI_VERSION 6
+ * brats_dropout, brats_evonorm_bwd_tiles + its workspace query); 6 in round 6 (additions only: brats_conv3d_set_kp); 7: additions
+ * only (brats_cc_filter, brats_rare_fill + their workspace queries). */
+#define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
 const char* brats_last_error(void);
 
@@ -525,6 +526,24 @@ int brats_post_threshold(const float* prob, const float* img, float* seg, uint8_
                          int C, size_t voxels, float scale, float thresh, brats_stream_t s);
 int brats_overlap_counts(const float* pred, const float* target, unsigned long long* counts, int NK,
                          size_t voxels, brats_stream_t s);
+
+/* ---- label-map post-processing of get_post_transforms (src/definer.py:679-694; --cleaning_areas / --replace_value,
+ * src/arguments_inference.py:61-70), applied by Engine.evaluate to the thresholded mean (learning/engine.py:244-259).
+ * Both work in place on uint8 labels [N][D][H][W], each sample on its own, with every decision taken on the device.
+ * cc_filter: KeepLargestConnectedComponent (utils/transforms.py:209-230, get_largest_component :579-600): 26-connected
+ *   components of labels != 0; min_size >= 0 keeps the components of more than min_size voxels, -1 keeps only the largest
+ *   (ties: the one whose first voxel comes first in C order; a sample without foreground stays unchanged); dropped voxels
+ *   become 0, kept ones keep their value.  ws: brats_cc_ws_bytes() device bytes.  N*D*H*W < 2^31.
+ * rare_fill: ReplaceWithClosestValue (utils/transforms.py:233-268, replace_w_closest_value_3d :603-647): values that occur
+ *   at most max_count times in the sample are rare; when one of them is non-zero, every rare pixel of each slice along
+ *   `axis` (0 = D, 1 = H, 2 = W) takes the value of the nearest non-rare pixel of that slice (exact Euclidean distance;
+ *   ties: the first such pixel in the slice's row-major order), 0 in a slice without one.  ws: brats_rare_fill_ws_bytes()
+ *   device bytes.  D, H, W <= 32767. */
+size_t brats_cc_ws_bytes(int N, int D, int H, int W);
+int brats_cc_filter(uint8_t* labels, int N, int D, int H, int W, int min_size, void* ws, brats_stream_t s);
+size_t brats_rare_fill_ws_bytes(int N, int D, int H, int W);
+int brats_rare_fill(uint8_t* labels, int N, int D, int H, int W, int axis, int max_count, void* ws,
+                    brats_stream_t s);
 
 /* ---- multi-tensor Ranger2020 step (learning/optimizer.py:136-255: RAdam with the
  * N_sma threshold, gradient centralisation :11-20, lookahead :233-240).  All tensors f32, contiguous.
