@@ -257,13 +257,22 @@ class Evaluator:
     ``--cleaning_areas --cleaning_areas_threshold T`` / ``--replace_value --replace_value_threshold T``: with either set,
     the chain is threshold -> labels -> KeepLargestConnectedComponent(T) -> ReplaceWithClosestValue(T, axis=2) ->
     channels -> background removal -> Dice / labels / crop, in the reference's order (get_post_transforms runs before
-    remove_background_voxels, learning/engine.py:244-259)."""
+    remove_background_voxels, learning/engine.py:244-259).
+
+    ``metrics`` (default None: only ``dice``, as before) is a tuple of names of brats21_amd.metrics.METRICS (the
+    reference's ``--key_metric`` / ``--additional_metrics``): with a target, ``out`` also holds ``hausdorff_distance95`` /
+    ``sensitivity`` / ``specificity`` as device float32 [N, K], computed like ``dice`` on the padded segmentation and
+    target after background removal and before cropping (learning/engine.py:259-268)."""
 
     def __init__(self, models, tta_transforms=None, sliding_window_size=None, sw_batch_size=1, overlap=0.25,
                  k_divisible=8, thresh=0.5, amp=True, use_graph=None, max_graphs=4, amp_dtype=torch.bfloat16,
-                 cleaning_areas_threshold=None, replace_value_threshold=None):
+                 cleaning_areas_threshold=None, replace_value_threshold=None, metrics=None):
         _check_int(cleaning_areas_threshold, "cleaning_areas_threshold", allow_none=True)
         _check_int(replace_value_threshold, "replace_value_threshold", allow_none=True)
+        if metrics is not None:
+            from .metrics import _check_names
+            metrics = tuple(m for m in _check_names(metrics) if m != "dice")  # dice is always there with a target
+        self.metrics = metrics
         self.clean_t, self.replace_t = cleaning_areas_threshold, replace_value_threshold
         self.models = list(models) if isinstance(models, (list, tuple)) else [models]
         self.tta, self.roi, self.swb, self.overlap = tta_transforms, sliding_window_size, sw_batch_size, overlap
@@ -321,6 +330,9 @@ class Evaluator:
         if target is not None:
             tp = shape_to_divisible(target, k=self.k)[0]
             out["dice"] = hard_dice_metric(seg, tp)
+            if self.metrics:
+                from .metrics import brats_metrics
+                out.update(brats_metrics(seg, tp, self.metrics))
         if return_original_shape:
             seg = shape_to_original(seg, p_b, p_a)
             if labels is not None:

@@ -51,7 +51,8 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * it.  History: 2 since round 3 (a changed signature, brats_maxpool2_fwd); 3 in round 4 (additions only); 4 in round 4 (the block
  * table of brats_conv3d_pack_weights_multi changed meaning); 5 in round 5 (additions only: brats_conv3d_set_x3_wgrad_fused,
  * brats_dropout, brats_evonorm_bwd_tiles + its workspace query); 6 in round 6 (additions only: brats_conv3d_set_kp); 7: additions
- * only (brats_cc_filter, brats_rare_fill + their workspace queries). */
+ * only (brats_cc_filter, brats_rare_fill + their workspace queries).  Still 7 after further additions only (brats_hausdorff +
+ * its workspace query): an older library lacks them and says so when they are called (brats21_amd/_lib.py). */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
 const char* brats_last_error(void);
@@ -544,6 +545,20 @@ int brats_cc_filter(uint8_t* labels, int N, int D, int H, int W, int min_size, v
 size_t brats_rare_fill_ws_bytes(int N, int D, int H, int W);
 int brats_rare_fill(uint8_t* labels, int N, int D, int H, int W, int axis, int max_count, void* ws,
                     brats_stream_t s);
+
+/* ---- Hausdorff distance of the validation metrics (utils/metrics.py:35-134: MONAI 0.6.0 HausdorffDistanceMetric,
+ * compute_hausdorff_distance, get_mask_edges(crop=True), get_surface_distance) on 0/1 f32 masks pred, target [NK][D][H][W].
+ * Edges: fg = (value == 1), cropped to the bounding box of the union; fg ^ erosion(fg) with the 6-neighbour cross, outside
+ * = 0, not along an axis where the box is one voxel thick (MONAI's np.squeeze of the crop).  out[nk] (f32) = max over the
+ * two directions (directed != 0: pred -> target only) of np.percentile(d, percentile) (linear method) of the Euclidean
+ * distances d from each edge voxel of one map to the nearest edge voxel of the other, or of max(d) for percentile < 0;
+ * NaN when neither map has an edge, inf / NaN (max / percentile) when exactly one has none -- MONAI's raw values.
+ * Squared distances are exact integers, order statistics exact, the interpolation numpy's _lerp in double, one rounding.
+ * ws: brats_hausdorff_ws_bytes() device bytes.  Everything is decided on the device (graph-capturable, deterministic).
+ * D, H, W <= 2048. */
+size_t brats_hausdorff_ws_bytes(int NK, int D, int H, int W);
+int brats_hausdorff(const float* pred, const float* target, int NK, int D, int H, int W, double percentile, int directed,
+                    float* out, void* ws, brats_stream_t s);
 
 /* ---- multi-tensor Ranger2020 step (learning/optimizer.py:136-255: RAdam with the
  * N_sma threshold, gradient centralisation :11-20, lookahead :233-240).  All tensors f32, contiguous.
