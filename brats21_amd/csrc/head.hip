@@ -6,6 +6,7 @@
 #include "common.hpp"
 
 int brats_lerp_adjoint_f32_planes(const float* in, float* out, size_t outer, int Lout, int Lin, size_t inner, hipStream_t st);
+int brats_planes_adjoint_f32(const float* in, float* out, size_t P, int D, int H, int W, int sc, hipStream_t st);
 
 static inline int sgrid(size_t total, int block) {
   size_t b = (total + block - 1) / block;
@@ -191,32 +192,63 @@ DEVI Lerp lerp_coef(int o, int in_len, float scale) {
 }
 static inline float ac_scale(int in_len, int out_len) { return out_len > 1 ? (float)(in_len - 1) / (float)(out_len - 1) : 0.f; }
 
-// grid = (chunks of the (yo, xo / 4) plane, Do, planes): z coefficients are scalar, a thread writes 4 consecutive x (one
-// 16-byte store) -- the first form computed one f32 per thread behind three 64-bit div / mod chains and wrote the deep
-// heads' 50 MB planes at 0.85 TB/s.  Same weights and summation order (w = wz * wy * wx, k = 0..7): bit-identical.
+// Up-sampling of the low-resolution logit planes to full size as a store stream.  grid = (chunks of UPL_ROWS output rows,
+// Do, planes): the z coefficients are scalar per workgroup, the y coefficients are derived once per row item, and the x
+// coefficients of the whole row (i0, w0, w1 per output x) and the low-resolution rows the chunk reads (two planes x the rows
+// between i0(first row) and i1(last row), each padded with a copy of its last element so that i1 is always i0 + 1) are put into
+// LDS once.  A thread writes 4 consecutive x (one 16-byte store) from two neighbouring LDS values per row and plane.  The gather
+// form it replaces derived three lerp_coef per output float and fetched its 8 sources from global memory one by one (0.8 - 1.6
+// TB/s on the 50 MB planes).  Same weights and summation order (w = (wz * wy) * wx, k = 0..7): bit-identical.
+constexpr int UPL_ROWS = 32;
+static inline int upl_nlow(int sc) { return UPL_ROWS / sc + 3; }  // low-resolution rows a chunk can touch
 __global__ void __launch_bounds__(256) upsample_planes_kernel(const float* __restrict__ low, float* __restrict__ out, int D, int H, int W, int sc,
-                                                              float sd, float sh, float sw) {
-  const int Ho = H * sc, Wo = W * sc, Do = D * sc, W4 = Wo / 4;
-  const int zo = blockIdx.y;
+                                                              int nlow, float sd, float sh, float sw) {
+  extern __shared__ __attribute__((aligned(16))) float upl[];
+  const int Ho = H * sc, Wo = W * sc, Do = D * sc, W4 = Wo / 4, Wp = W + 1;
+  float* lows = upl;                                        // [2][nlow][Wp]
+  int* xi = (int*)(upl + (2 * nlow * Wp + 3) / 4 * 4);      // [Wo] i0, then w0, w1
+  float* xw0 = (float*)(xi + Wo);
+  float* xw1 = xw0 + Wo;
+  const int zo = blockIdx.y, y0 = blockIdx.x * UPL_ROWS;
+  const int rows = Ho - y0 < UPL_ROWS ? Ho - y0 : UPL_ROWS;
   const size_t pl = blockIdx.z;
   const Lerp lz = lerp_coef(zo, D, sd);
-  const float* p0 = low + pl * D * H * W + (size_t)lz.i0 * H * W;
-  const float* p1 = low + pl * D * H * W + (size_t)lz.i1 * H * W;
+  const int ylo = lerp_coef(y0, H, sh).i0;
+  int cnt = lerp_coef(y0 + rows - 1, H, sh).i1 - ylo + 1;
+  if (cnt > nlow) cnt = nlow;  // (cannot happen: nlow covers rows * scale + 2; keeps LDS in bounds)
+  const float* p0 = low + pl * D * H * W + (size_t)lz.i0 * H * W + (size_t)ylo * W;
+  const float* p1 = low + pl * D * H * W + (size_t)lz.i1 * H * W + (size_t)ylo * W;
+  for (int idx = threadIdx.x; idx < 2 * cnt * Wp; idx += blockDim.x) {
+    const int pz = idx / (cnt * Wp), rem = idx % (cnt * Wp), r = rem / Wp, x = rem % Wp;
+    lows[(pz * nlow + r) * Wp + x] = (pz ? p1 : p0)[r * W + (x < W ? x : W - 1)];
+  }
+  for (int x = threadIdx.x; x < Wo; x += blockDim.x) {
+    const Lerp lx = lerp_coef(x, W, sw);
+    xi[x] = lx.i0;
+    xw0[x] = lx.w0;
+    xw1[x] = lx.w1;
+  }
+  __syncthreads();
   float* o = out + (pl * Do + zo) * (size_t)Ho * Wo;
-  for (int it = blockIdx.x * blockDim.x + threadIdx.x; it < Ho * W4; it += gridDim.x * blockDim.x) {
-    const int yo = it / W4, x0 = (it % W4) * 4;
+  typedef __attribute__((ext_vector_type(4))) int i32x4;
+  for (int it = threadIdx.x; it < rows * W4; it += blockDim.x) {
+    const int yo = y0 + it / W4, x0 = (it % W4) * 4;
     const Lerp ly = lerp_coef(yo, H, sh);
+    const float wzy[4] = {lz.w0 * ly.w0, lz.w0 * ly.w1, lz.w1 * ly.w0, lz.w1 * ly.w1};
+    int r0 = ly.i0 - ylo, r1 = ly.i1 - ylo;
+    r0 = r0 < cnt ? r0 : cnt - 1;
+    r1 = r1 < cnt ? r1 : cnt - 1;
+    const float* rp[4] = {lows + r0 * Wp, lows + r1 * Wp, lows + (nlow + r0) * Wp, lows + (nlow + r1) * Wp};
+    const i32x4 i0 = *(const i32x4*)(xi + x0);
+    const f32x4 w0 = *(const f32x4*)(xw0 + x0), w1 = *(const f32x4*)(xw1 + x0);
     f32x4 r;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const Lerp lx = lerp_coef(x0 + j, W, sw);
       float acc = 0.f;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const float* p = (k & 4) ? p1 : p0;
-        const int yy = (k & 2) ? ly.i1 : ly.i0, xx = (k & 1) ? lx.i1 : lx.i0;
-        const float wgt = ((k & 4) ? lz.w1 : lz.w0) * ((k & 2) ? ly.w1 : ly.w0) * ((k & 1) ? lx.w1 : lx.w0);
-        acc += wgt * p[yy * W + xx];
+        const float wgt = wzy[k >> 1] * ((k & 1) ? w1[j] : w0[j]);
+        acc += wgt * rp[k >> 1][i0[j] + (k & 1)];
       }
       r[j] = acc;
     }
@@ -279,9 +311,12 @@ extern "C" int BRATS_API(brats_head_fwd)(const void* x, int xpitch, const float*
   if (int rc = head_conv_launch<false>(x, xpitch, w, b, low, dtype, N, C, K, vox, HeadPre{nullptr, 0.f, 0}, st)) return rc;
   if (scale > 1) {
     if ((W * scale) % 4) BRATS_FAIL(BRATS_E_UNSUPPORTED, "head_fwd: up-sampled width %d must be a multiple of 4", W * scale);
-    const int items = H * scale * (W * scale / 4);
-    hipLaunchKernelGGL(upsample_planes_kernel, dim3((unsigned)((items + 255) / 256), (unsigned)(D * scale), (unsigned)(N * K)), dim3(256), 0, st,
-                       (const float*)low, out, D, H, W, scale, ac_scale(D, D * scale), ac_scale(H, H * scale), ac_scale(W, W * scale));
+    const int nlow = upl_nlow(scale);
+    const size_t lds = ((size_t)(2 * nlow * (W + 1) + 3) / 4 * 4 + (size_t)3 * W * scale) * sizeof(float);
+    if (lds > 64 * 1024 || D * scale > 65535 || N * K > 65535) BRATS_FAIL(BRATS_E_UNSUPPORTED, "head_fwd: planes of width %d x scale %d are too large", W, scale);
+    hipLaunchKernelGGL(upsample_planes_kernel, dim3((unsigned)((H * scale + UPL_ROWS - 1) / UPL_ROWS), (unsigned)(D * scale), (unsigned)(N * K)),
+                       dim3(256), lds, st, (const float*)low, out, D, H, W, scale, nlow, ac_scale(D, D * scale), ac_scale(H, H * scale),
+                       ac_scale(W, W * scale));
   }
   BRATS_CHECK_LAUNCH();
   return 0;
@@ -410,10 +445,15 @@ extern "C" int BRATS_API(brats_head_bwd)(const void* x, int xpitch, const float*
     float* dl = ws;
     float* t1 = dl + p * vox;
     float* t2 = t1 + p * D * (H * scale) * (W * scale);
-    int rc;
-    if ((rc = brats_lerp_adjoint_f32_planes(dout, t1, p, D * scale, D, (size_t)H * scale * W * scale, st))) return rc;
-    if ((rc = brats_lerp_adjoint_f32_planes(t1, t2, p * D, H * scale, H, (size_t)W * scale, st))) return rc;
-    if ((rc = brats_lerp_adjoint_f32_planes(t2, dl, p * D * H, W * scale, W, 1, st))) return rc;
+    // one launch for the three axes (the 50 MB of dout are read once, nothing goes through t1 / t2) where the tile form
+    // applies, else an HBM round trip per axis
+    int rc = brats_planes_adjoint_f32(dout, dl, p, D, H, W, scale, st);
+    if (rc < 0) return rc;
+    if (rc > 0) {
+      if ((rc = brats_lerp_adjoint_f32_planes(dout, t1, p, D * scale, D, (size_t)H * scale * W * scale, st))) return rc;
+      if ((rc = brats_lerp_adjoint_f32_planes(t1, t2, p * D, H * scale, H, (size_t)W * scale, st))) return rc;
+      if ((rc = brats_lerp_adjoint_f32_planes(t2, dl, p * D * H, W * scale, W, 1, st))) return rc;
+    }
     dlow = dl;
   }
   const int cv = C / vw, vl = 256 / cv;

@@ -486,7 +486,8 @@ __global__ void lerp_adjoint_kernel(const TI* __restrict__ in, int in_pitch, TO*
   }
 }
 
-// exported for head.hip: f32 planes [outer][L][inner] adjoint
+// exported for head.hip: f32 planes [outer][L][inner] adjoint along one axis (the three-pass form, for what the tile form
+// below does not take)
 int brats_lerp_adjoint_f32_planes(const float* in, float* out, size_t outer, int Lout, int Lin, size_t inner,
                                   hipStream_t st) {
   const size_t total = outer * Lin * inner;
@@ -504,6 +505,386 @@ int brats_lerp_adjoint_f32_planes(const float* in, float* out, size_t outer, int
   return 0;
 }
 
+// ---- the three axes of the adjoint in ONE launch --------------------------------------------------------------------------
+// The three-pass form moves every tensor through HBM again between the axes (x2 at 2 x 48 x 128^3: 403 -> 201 -> 100 -> 50 MB,
+// 1.06 GB for 0.45 GB of input and output; each pass is at bandwidth, the structure is the cost).  Here a workgroup owns a
+// coarse tile, walks the fine planes that feed it once in ascending z with the D reduction in registers, and does the H and W
+// reductions of every finished coarse plane out of LDS; only the coarse tile is written.
+// Bit-identity with the three-pass form: per axis the same f32 sum over ascending fine index l of w(l) * v(l) with
+// w = [i0 == i] w0 + [i1 == i] w1 from the forward's own lerp_coef (zero weights skipped), and the value is rounded to the
+// storage type between the axes exactly where that form stores t1 and t2.
+// A fine plane l feeds the coarse planes i0(l) and i1(l) <= i0 + 1 only, so the walk keeps two accumulators per column: `cur`
+// (coarse plane i) and `nxt` (i + 1).  Step i takes the planes with i0 == i: they end cur's sum (w0, plus w1 at a clamped end)
+// and begin nxt's (w1) -- for every coarse plane that is ascending l, the planes with i1 == i first.  A z chunk starts one
+// step early (the planes with i0 == za - 1 carry w1 into za); that step's own plane is dropped.
+// (Earlier forms that kept the temporaries in HBM or gathered again from it did not pay: profiles/r03_lerp_adjoint_two_axis_negative.txt,
+//  profiles/r04_upsample_adjoint_stream_negative.txt.)
+
+// first / last fine index that can carry weight into the coarse range [a, a + cnt): found with the forward's own expression,
+// starting from a conservative estimate
+DEVI void lerp_fine_range(int a, int cnt, int Lin, int Lout, float scale, int& lo, int& hi) {
+  const float inv = scale > 0.f ? 1.f / scale : 0.f;
+  lo = (int)floorf((float)(a - 1) * inv) - 2;
+  hi = (int)ceilf((float)(a + cnt) * inv) + 2;
+  if (scale <= 0.f) { lo = 0; hi = Lout - 1; }
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > Lout - 1 ? Lout - 1 : hi;
+  while (lo < hi && lerp_coef(lo, Lin, scale).i1 < a) ++lo;
+  while (hi > lo && lerp_coef(hi, Lin, scale).i0 > a + cnt - 1) --hi;
+}
+// w(l) for coarse index i (the three-pass kernel's expression)
+DEVI float lerp_weight_to(int l, int i, int Lin, float scale) {
+  const Lerp c = lerp_coef(l, Lin, scale);
+  float w = 0.f;
+  if (c.i0 == i) w += c.w0;
+  if (c.i1 == i) w += c.w1;
+  return w;
+}
+
+// 16-bit NDHWC, scale 2: coarse tile = (cd planes) x 4 rows x 8 columns on a slice of 48 channels, 512 threads, two workgroups
+// per CU (31 KB of LDS, <= 128 VGPRs each) so that one loads while the other reduces.  The fine rows / columns that reach c
+// coarse ones lie in a closed interval of (c + 1) / scale: <= 19.3 for c = 8 (extents >= 16; the whole axis, 16, at extent 8)
+// and <= 11.7 for c = 4, hence the 12 x 20 footprint.  Re-read of the input: 11 / 8 x 19 / 16 x (2 cd + 2) / (2 cd) = 1.7 at
+// cd = 16; the workgroup ids are dealt out so that the tiles of one z chunk run on one XCD and share their halo lines in its L2
+// (measured: 449 MB fetched from HBM for the 403 MB of a 2 x 48 x 128^3 gradient, profiles/memory_passes_pmc.txt).
+// The loads of step i + 1 are issued before the LDS passes of step i, so they are in flight while the workgroup is there.
+constexpr int UBF_TH = 4, UBF_TW = 8, UBF_FH = 12, UBF_FW = 20, UBF_CS = 48, UBF_CV = UBF_CS / 8, UBF_THREADS = 512, UBF_KC = 3, UBF_MAXP = 2;
+static_assert(UBF_FH * UBF_FW * UBF_CV <= UBF_THREADS * UBF_KC, "every column of the fine footprint needs a thread slot");
+// acc[0..7] += w * (8 x 16-bit at p)
+DEVI void ubf_add(float* acc, float w, const bf16_t* p) {
+  float a[8];
+  Vec<bf16_t, 8>::load(p, a);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] += w * a[j];
+}
+struct UbfStep { int l[UBF_MAXP]; float wc[UBF_MAXP], wn[UBF_MAXP]; int np; };
+__global__ void __launch_bounds__(UBF_THREADS, 4) upsample2_bwd_fused_kernel(const bf16_t* __restrict__ dy, int dypitch, bf16_t* __restrict__ dx,
+                                                                          int dxpitch, int C, int D, int H, int W, int cd, float sd,
+                                                                          float sh, float sw) {
+  __shared__ __attribute__((aligned(16))) bf16_t slab[UBF_FH * UBF_FW * UBF_CS];  // the finished coarse plane, D-reduced: [fh][fw][48]
+  __shared__ __attribute__((aligned(16))) bf16_t t2s[UBF_TH * UBF_FW * UBF_CS];   // ... H-reduced: [4][fw][48]
+  __shared__ float wys[UBF_TH][UBF_FH], wxs[UBF_TW][UBF_FW];
+  __shared__ int yrng[UBF_TH][2], xrng[UBF_TW][2];
+  const int Do = 2 * D, Ho = 2 * H, Wo = 2 * W;
+  const int nsl = C / UBF_CS, tiles_x = W / UBF_TW, tiles_y = H / UBF_TH, nz = D / cd;
+  // workgroup ids go round the 8 XCDs: give every XCD a contiguous run of tiles (one z chunk's tiles are neighbours there)
+  int bid = blockIdx.x;
+  if (gridDim.x % 8 == 0) bid = (bid % 8) * (gridDim.x / 8) + bid / 8;
+  const int sl = bid % nsl, tx = (bid / nsl) % tiles_x, ty = (bid / (nsl * tiles_x)) % tiles_y;
+  const int zc = (bid / (nsl * tiles_x * tiles_y)) % nz, n = bid / (nsl * tiles_x * tiles_y * nz);
+  const int za = zc * cd, ya = ty * UBF_TH, xa = tx * UBF_TW;
+  const int tid = threadIdx.x;
+  int yl, yh, xl, xh;
+  lerp_fine_range(ya, UBF_TH, H, Ho, sh, yl, yh);
+  lerp_fine_range(xa, UBF_TW, W, Wo, sw, xl, xh);
+  if (yh - yl + 1 > UBF_FH) yh = yl + UBF_FH - 1;  // (cannot happen for the extents the host admits; keeps LDS in bounds)
+  if (xh - xl + 1 > UBF_FW) xh = xl + UBF_FW - 1;
+  const int fh = yh - yl + 1, fw = xh - xl + 1;
+  // weight tables of the H and W reductions
+  if (tid < UBF_TH * UBF_FH) {
+    const int t = tid / UBF_FH, f = tid % UBF_FH;
+    wys[t][f] = f < fh ? lerp_weight_to(yl + f, ya + t, H, sh) : 0.f;
+  } else if (tid >= 64 && tid < 64 + UBF_TW * UBF_FW) {
+    const int t = (tid - 64) / UBF_FW, f = (tid - 64) % UBF_FW;
+    wxs[t][f] = f < fw ? lerp_weight_to(xl + f, xa + t, W, sw) : 0.f;
+  }
+  __syncthreads();
+  if (tid < UBF_TH + UBF_TW) {  // first / last fine index with weight, per coarse row / column
+    const int ax = tid >= UBF_TH, t = ax ? tid - UBF_TH : tid, fn = ax ? fw : fh;
+    const float* wt = ax ? wxs[t] : wys[t];
+    int a = 0, b = fn - 1;
+    while (a < b && wt[a] == 0.f) ++a;
+    while (b > a && wt[b] == 0.f) --b;
+    (ax ? xrng : yrng)[t][0] = a;
+    (ax ? xrng : yrng)[t][1] = b;
+  }
+  // this thread's columns (fine y, fine x, channel vector) of the footprint
+  const int ncol = fh * fw * UBF_CV;
+  const bf16_t* src = dy + (size_t)n * Do * Ho * Wo * dypitch + (size_t)sl * UBF_CS;
+  const size_t plane = (size_t)Ho * Wo * dypitch;
+  size_t coloff[UBF_KC];
+  bool colok[UBF_KC];
+#pragma unroll
+  for (int k = 0; k < UBF_KC; ++k) {
+    const int col = tid + k * UBF_THREADS;
+    colok[k] = col < ncol;
+    const int cvi = col % UBF_CV, xx = (col / UBF_CV) % fw, yy = colok[k] ? col / (UBF_CV * fw) : 0;
+    coloff[k] = ((size_t)(yl + yy) * Wo + (xl + xx)) * dypitch + cvi * 8;
+  }
+  // the z walk
+  const int i_first = za > 0 ? za - 1 : 0, i_last = za + cd - 1;
+  int lcur, lend;
+  lerp_fine_range(i_first, 1, D, Do, sd, lcur, lend);
+  while (lcur < Do && lerp_coef(lcur, D, sd).i0 < i_first) ++lcur;
+  auto plan = [&](int i, UbfStep& st) {  // up to UBF_MAXP planes with i0 == i, from lcur on
+    st.np = 0;
+#pragma unroll
+    for (int p = 0; p < UBF_MAXP; ++p) {
+      st.l[p] = 0; st.wc[p] = 0.f; st.wn[p] = 0.f;
+      if (st.np == p && lcur < Do) {
+        const Lerp c = lerp_coef(lcur, D, sd);
+        if (c.i0 == i) {
+          st.l[p] = lcur;
+          st.wc[p] = c.i1 == i ? c.w0 + c.w1 : c.w0;
+          st.wn[p] = c.i1 == i + 1 ? c.w1 : 0.f;
+          st.np = p + 1;
+          ++lcur;
+        }
+      }
+    }
+  };
+  u32x4 raw[UBF_MAXP][UBF_KC];
+  auto issue = [&](const UbfStep& st) {
+#pragma unroll
+    for (int p = 0; p < UBF_MAXP; ++p)
+      if (p < st.np) {
+#pragma unroll
+        for (int k = 0; k < UBF_KC; ++k)
+          raw[p][k] = colok[k] ? *(const u32x4*)(src + (size_t)st.l[p] * plane + coloff[k]) : u32x4{0u, 0u, 0u, 0u};
+      }
+  };
+  // (scalar f32 multiplies and adds on purpose: the same sums as f32x2 pairs -- v_pk_mul_f32 + v_pk_add_f32 -- measured
+  //  slower, 190 -> 215 us at 2 x 48 x 128^3, for the register pairing they need)
+  float cur[UBF_KC][8], nxt[UBF_KC][8];
+#pragma unroll
+  for (int k = 0; k < UBF_KC; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { cur[k][j] = 0.f; nxt[k][j] = 0.f; }
+  auto accumulate = [&](const UbfStep& st) {
+#pragma unroll
+    for (int p = 0; p < UBF_MAXP; ++p)
+      if (p < st.np) {
+#pragma unroll
+        for (int k = 0; k < UBF_KC; ++k) {
+          float a[8];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) unpack2(raw[p][k][q], a[2 * q], a[2 * q + 1]);
+          if (st.wc[p] != 0.f) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) cur[k][j] += st.wc[p] * a[j];
+          }
+          if (st.wn[p] != 0.f) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) nxt[k][j] += st.wn[p] * a[j];
+          }
+        }
+      }
+  };
+  UbfStep st;
+  plan(i_first, st);
+  issue(st);
+  bf16_t* dst = dx + (size_t)n * D * H * W * dxpitch + (size_t)sl * UBF_CS;
+  for (int i = i_first; i <= i_last; ++i) {
+    accumulate(st);
+    while (st.np == UBF_MAXP) {  // more planes with the same i0 than one batch holds
+      plan(i, st);
+      issue(st);
+      accumulate(st);
+    }
+    if (i >= za) {
+#pragma unroll
+      for (int k = 0; k < UBF_KC; ++k)
+        if (colok[k]) Vec<bf16_t, 8>::store(slab + (size_t)(tid + k * UBF_THREADS) * 8, cur[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < UBF_KC; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { cur[k][j] = nxt[k][j]; nxt[k][j] = 0.f; }
+    if (i < i_last) {  // the next step's planes: in flight during the LDS passes below
+      plan(i + 1, st);
+      issue(st);
+    } else {
+      st.np = 0;
+    }
+    __syncthreads();
+    if (i < za) continue;
+    // H: [fh][fw][48] -> [4][fw][48], rounded to the storage type
+    const int rowv = fw * UBF_CV;
+    for (int it = tid; it < UBF_TH * rowv; it += UBF_THREADS) {
+      const int h = it / rowv, r = it % rowv;
+      float acc[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+      for (int f = yrng[h][0]; f <= yrng[h][1]; ++f) {
+        const float w = wys[h][f];
+        if (w != 0.f) ubf_add(acc, w, slab + ((size_t)f * rowv + r) * 8);
+      }
+      Vec<bf16_t, 8>::store(t2s + (size_t)it * 8, acc);
+    }
+    __syncthreads();
+    // W: [4][fw][48] -> the coarse tile's plane i
+    for (int it = tid; it < UBF_TH * UBF_TW * UBF_CV; it += UBF_THREADS) {
+      const int cvi = it % UBF_CV, xc = (it / UBF_CV) % UBF_TW, h = it / (UBF_CV * UBF_TW);
+      float acc[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+      for (int f = xrng[xc][0]; f <= xrng[xc][1]; ++f) {
+        const float w = wxs[xc][f];
+        if (w != 0.f) ubf_add(acc, w, t2s + ((size_t)(h * fw + f) * UBF_CV + cvi) * 8);
+      }
+      Vec<bf16_t, 8>::store(dst + (((size_t)i * H + ya + h) * W + xa + xc) * dxpitch + cvi * 8, acc);
+    }
+  }
+}
+
+static int g_upsample_bwd_fused = -1;  // brats_upsample_bwd_set_fused(): -1 = default (on where the tile form applies), 0 = off, 1 = on
+extern "C" int BRATS_API(brats_upsample_bwd_set_fused)(int mode) {
+  const int old = g_upsample_bwd_fused;
+  g_upsample_bwd_fused = mode < 0 ? -1 : (mode ? 1 : 0);
+  return old;
+}
+// the z chunk of the tile form, 0 = this problem goes through the three passes (scale 4 / 8, f32, extents that do not tile)
+static int upsample_bwd_fused_cd(int N, int C, int D, int H, int W, int sc) {
+  if (g_upsample_bwd_fused == 0 || sc != 2 || C % UBF_CS || H % UBF_TH || W % UBF_TW || D % 4) return 0;
+  const size_t per_z = (size_t)N * (H / UBF_TH) * (W / UBF_TW) * (C / UBF_CS);
+  int cd = 16;
+  while (cd > 4 && (D % cd || per_z * (D / cd) < 1024)) cd /= 2;  // two rounds of two workgroups per CU where the tensor is large enough
+  if (per_z * (D / cd) > 0x7fffffffull) return 0;
+  return cd;
+}
+
+// ---- f32 planes [P][Do][Ho][Wo] -> [P][D][H][W] (the deep-supervision heads, scale 2 / 4 / 8; head.hip) in one launch ------
+// The same walk on planes without a channel axis: a workgroup owns cd coarse planes x th coarse rows of one plane stack over
+// the full width, a thread's columns are (fine y, four fine x).  f32 throughout, so there is no rounding between the axes and
+// the D-reduced tile stays in LDS for all cd planes: the fine planes are streamed B at a time (KC x B 16-byte loads in flight
+// per thread), a coarse plane is put down when the walk passes it, and the H and W reductions run once per workgroup.  The
+// order of the additions per axis is that of lerp_adjoint_kernel, with its weights derived on the fly over its conservative
+// candidate range.  LDS: cd x (fmax + th) x Wo floats.
+constexpr int PAF_THREADS = 256;
+template <int KC, int B>
+__global__ void __launch_bounds__(PAF_THREADS) planes_adjoint_fused_kernel(const float* __restrict__ in, float* __restrict__ out, int D, int H, int W,
+                                                                           int sc, int cd, int th, int fmax, float sd, float sh, float sw) {
+  extern __shared__ __attribute__((aligned(16))) float paf_lds[];
+  const int Do = D * sc, Ho = H * sc, Wo = W * sc, W4 = Wo / 4;
+  float* t1s = paf_lds;                            // [cd][fmax][Wo]
+  float* t2s = paf_lds + (size_t)cd * fmax * Wo;   // [cd][th][Wo]
+  const int ya = blockIdx.x * th, za = blockIdx.y * cd;
+  const size_t pl = blockIdx.z;
+  const int tid = threadIdx.x;
+  int yl, yh;
+  lerp_fine_range(ya, th, H, Ho, sh, yl, yh);
+  if (yh - yl + 1 > fmax) yh = yl + fmax - 1;  // (the host sizes fmax for the closed interval of (th + 1) / scale; keeps LDS in bounds)
+  const int fh = yh - yl + 1;
+  const int ncol = fh * W4;
+  const float* src = in + pl * Do * Ho * Wo + (size_t)yl * Wo;
+  const size_t plane = (size_t)Ho * Wo;
+  // the planes with i0 in [i_first, i_last]; i_first = za - 1 carries its w1 into za and is itself dropped
+  const int i_first = za > 0 ? za - 1 : 0, i_last = za + cd - 1;
+  int lstart, lend;
+  lerp_fine_range(i_first, i_last - i_first + 1, D, Do, sd, lstart, lend);
+  while (lstart < lend && lerp_coef(lstart, D, sd).i0 < i_first) ++lstart;
+  f32x4 cur[KC], nxt[KC];
+#pragma unroll
+  for (int k = 0; k < KC; ++k) { cur[k] = f32x4{0.f, 0.f, 0.f, 0.f}; nxt[k] = cur[k]; }
+  int i = i_first;  // the coarse plane `cur` belongs to
+  auto flush = [&]() {
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+      const int col = tid + k * PAF_THREADS;
+      if (i >= za && col < ncol) *(f32x4*)(t1s + ((size_t)(i - za) * fmax * W4 + col) * 4) = cur[k];
+      cur[k] = nxt[k];
+      nxt[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    ++i;
+  };
+  for (int l0 = lstart; l0 <= lend; l0 += B) {
+    f32x4 raw[B][KC];
+#pragma unroll
+    for (int b = 0; b < B; ++b)
+      if (l0 + b <= lend) {
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+          const int col = tid + k * PAF_THREADS;
+          raw[b][k] = col < ncol ? *(const f32x4*)(src + (size_t)(l0 + b) * plane + (size_t)col * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+#pragma unroll
+    for (int b = 0; b < B; ++b)
+      if (l0 + b <= lend) {
+        const Lerp c = lerp_coef(l0 + b, D, sd);
+        while (i < c.i0 && i <= i_last) flush();
+        const float wc = c.i1 == i ? c.w0 + c.w1 : c.w0, wn = c.i1 == i + 1 ? c.w1 : 0.f;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+          if (wc != 0.f) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cur[k][j] += wc * raw[b][k][j];
+          }
+          if (wn != 0.f) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) nxt[k][j] += wn * raw[b][k][j];
+          }
+        }
+      }
+  }
+  while (i <= i_last) flush();
+  __syncthreads();
+  const float invh = sh > 0.f ? 1.f / sh : 0.f, invw = sw > 0.f ? 1.f / sw : 0.f;
+  // H: [cd][fh][Wo] -> [cd][th][Wo]
+  for (int it = tid; it < cd * th * W4; it += PAF_THREADS) {
+    const int x4 = it % W4, h = (it / W4) % th, z = it / (W4 * th), ic = ya + h;
+    int lo = (int)floorf((float)(ic - 1) * invh) - 1, hi = (int)ceilf((float)(ic + 1) * invh) + 1;
+    if (sh <= 0.f) { lo = 0; hi = Ho - 1; }
+    lo = lo < yl ? yl : lo;
+    hi = hi > yh ? yh : hi;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int l = lo; l <= hi; ++l) {
+      const float w = lerp_weight_to(l, ic, H, sh);
+      if (w != 0.f) {
+        const f32x4 a = *(const f32x4*)(t1s + ((size_t)(z * fmax + l - yl) * W4 + x4) * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += w * a[j];
+      }
+    }
+    *(f32x4*)(t2s + (size_t)it * 4) = acc;
+  }
+  __syncthreads();
+  // W: [cd][th][Wo] -> [cd][th][W] of the coarse planes za..
+  for (int it = tid; it < cd * th * W; it += PAF_THREADS) {
+    const int xc = it % W, h = (it / W) % th, z = it / (W * th);
+    int lo = (int)floorf((float)(xc - 1) * invw) - 1, hi = (int)ceilf((float)(xc + 1) * invw) + 1;
+    if (sw <= 0.f) { lo = 0; hi = Wo - 1; }
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > Wo - 1 ? Wo - 1 : hi;
+    float acc = 0.f;
+    for (int l = lo; l <= hi; ++l) {
+      const float w = lerp_weight_to(l, xc, W, sw);
+      if (w != 0.f) acc += w * t2s[(size_t)(z * th + h) * Wo + l];
+    }
+    out[((pl * D + za + z) * H + ya + h) * (size_t)W + xc] = acc;
+  }
+}
+
+// exported for head.hip: the three axes of the f32 plane adjoint, [P][D sc][H sc][W sc] -> [P][D][H][W], one launch.
+// Returns 1 without launching where the tile form does not apply (width no multiple of 4, rows too wide for LDS): the caller
+// runs the three passes (brats_lerp_adjoint_f32_planes) then.
+int brats_planes_adjoint_f32(const float* in, float* out, size_t P, int D, int H, int W, int sc, hipStream_t st) {
+  const int Wo = W * sc;
+  if (Wo % 4 || (((size_t)in | (size_t)out) & 15) || P > 65535 || D > 65535) return 1;
+  // tile: 2 - 4 coarse planes x 2 - 4 coarse rows (about 16 x 8 fine planes x rows per workgroup): small enough for
+  // several workgroups per CU and a grid of many hundreds, the halo re-read ((cd + 1) / cd x (th + 1) / th = 1.6 at scale
+  // 2, 2.25 at scale 8) comes out of the caches the producer of the 50 MB planes has just filled
+  int cd = 16 / sc < 2 ? 2 : (16 / sc > 4 ? 4 : 16 / sc), th = 8 / sc < 2 ? 2 : (8 / sc > 4 ? 4 : 8 / sc);
+  while (cd > 1 && D % cd) cd /= 2;
+  while (th > 1 && H % th) th /= 2;
+  // fine rows that reach th coarse ones: the closed interval of (th + 1) / scale, scale = (H - 1) / (H sc - 1)
+  const float scale_h = H > 1 ? (float)(H - 1) / (float)(H * sc - 1) : 0.f;
+  int fmax = scale_h > 0.f ? (int)ceilf((float)(th + 1) / scale_h) + 2 : H * sc;
+  if (fmax > H * sc) fmax = H * sc;
+  const size_t lds = (size_t)cd * (fmax + th) * Wo * sizeof(float);
+  const int kc = (fmax * (Wo / 4) + PAF_THREADS - 1) / PAF_THREADS;
+  if (lds > 64 * 1024 || kc > 6) return 1;
+  const dim3 grid(H / th, D / cd, (unsigned)P);
+#define PAF_LAUNCH(KC, B) hipLaunchKernelGGL((planes_adjoint_fused_kernel<KC, B>), grid, dim3(PAF_THREADS), lds, st, in, out, D, H, W, sc, cd, th, \
+                                             fmax, ac_scale(D, D * sc), ac_scale(H, H * sc), ac_scale(W, W * sc))
+  if (kc <= 2) PAF_LAUNCH(2, 8);
+  else if (kc <= 4) PAF_LAUNCH(4, 4);
+  else PAF_LAUNCH(6, 2);
+#undef PAF_LAUNCH
+  BRATS_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" size_t BRATS_API(brats_upsample_bwd_ws_bytes)(int dtype, int N, int C, int D, int H, int W, int scale) {
   const size_t esz = dtype == BRATS_BF16 ? 2 : 4;
   const size_t a = (size_t)N * D * (H * scale) * (W * scale) * C;  // after the D pass
@@ -516,6 +897,15 @@ static int upsample_bwd_t(const T* dy, int dypitch, T* dx, int dxpitch, char* tm
                           hipStream_t st) {
   constexpr int VW = 16 / sizeof(T);
   const int Do = D * sc, Ho = H * sc, Wo = W * sc;
+  if constexpr (sizeof(T) == 2) {
+    if (const int cd = upsample_bwd_fused_cd(N, C, D, H, W, sc)) {  // one launch, nothing through tmp
+      const dim3 grid((unsigned)((size_t)N * (H / UBF_TH) * (W / UBF_TW) * (C / UBF_CS) * (D / cd)));
+      hipLaunchKernelGGL(upsample2_bwd_fused_kernel, grid, dim3(UBF_THREADS), 0, st, dy, dypitch, dx, dxpitch, C, D, H, W, cd,
+                         ac_scale(D, Do), ac_scale(H, Ho), ac_scale(W, Wo));
+      BRATS_CHECK_LAUNCH();
+      return 0;
+    }
+  }
   const size_t a_elems = (size_t)N * D * Ho * Wo * C;
   T* t1 = (T*)tmp;
   T* t2 = (T*)(tmp + ((a_elems * sizeof(T) + 255) / 256 * 256));

@@ -935,6 +935,12 @@ def upsample(x, scale=2, out=None):
     return out
 
 
+def set_upsample_bwd_fused(mode):
+    """brats_upsample_bwd_set_fused: 1 / 0 = the one-launch x2 adjoint of 16-bit tensors on / off (off: three passes through the
+    workspace everywhere), -1 = default (on where it tiles).  Bit-identical results.  Returns the previous setting."""
+    return _lib.lib().brats_upsample_bwd_set_fused(mode)
+
+
 def upsample_bwd(dy, scale=2):
     dptr, c, dp = _desc(dy)
     n, do, ho, wo, _ = dy.shape

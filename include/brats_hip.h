@@ -448,6 +448,10 @@ int brats_upsample_fwd(const void* x, int xpitch, void* y, int ypitch, int dtype
 size_t brats_upsample_bwd_ws_bytes(int dtype, int N, int C, int D, int H, int W, int scale);
 int brats_upsample_bwd(const void* dy, int dypitch, void* dx, int dxpitch, void* tmp, int dtype,
                        int N, int C, int D, int H, int W, int scale, brats_stream_t s);
+/* Test knob: 1 / -1 (default) = scale 2 on 16-bit tensors runs the three axes of the adjoint in one launch (a coarse tile per
+ * workgroup, the fine box read once, H and W reductions out of LDS) where it tiles: C a multiple of 48, W of 8, D and H of 4;
+ * 0 = the three passes through tmp everywhere.  Bit-identical results; returns the previous setting. */
+int brats_upsample_bwd_set_fused(int mode);
 
 /* ---- segmentation heads: 1x1x1 conv C -> K (K <= 4) + bias (conv1x1 equiunet2020.py:37-41,441)
  * followed by trilinear x`scale` up-sampling (deep heads :443-458); output NCDHW f32 logits. */
