@@ -1,6 +1,7 @@
 """The reference's ``--model`` factory for the accelerated models (src/definer.py:37-174):
 ``get_model(args) -> torch.nn.Module`` with the same Namespace fields (model, width, norm, act,
-num_classes, dropout) and the same error behaviour (NameError for an unknown model)."""
+num_classes, dropout) and the same error behaviour (NameError for an unknown model), and its ``--criterion`` factory
+(src/definer.py:177-288): ``make_criterion(args)`` with the Namespace fields criterion and num_classes."""
 import argparse
 
 import torch
@@ -25,3 +26,59 @@ def get_model(args: argparse.Namespace) -> torch.nn.Module:
 
         return EquiUnetASSPEvo(**kwargs)
     raise NameError("Not Supported Model")
+
+
+_MONAI_ONLY_CRITERIA = ("generalized_dice", "focal", "tversky", "dice_ce", "dice_focal")
+
+
+def make_criterion(args: argparse.Namespace) -> torch.nn.Module:
+    """src/definer.py:177-288 for the criteria built here, with the reference's own keyword sets: dice / jaccard (monai
+    DiceLoss(sigmoid, squared_pred, batch=True) = losses.DiceLoss) and hd / dice_hd / boundary / dice_boundary
+    (learning/losses.py).  The boundary criteria take the pair [target, distance_map] as their target."""
+    from . import losses
+
+    if args.criterion in ("dice", "jaccard"):
+        return losses.DiceLoss(jaccard=args.criterion == "jaccard")
+    if args.criterion == "hd":
+        criterion_function = losses.HausdorffLoss
+        kwargs = {
+            "idc": list(range(args.num_classes)),
+            "sigmoid": True,
+            "softmax": False,
+            "alpha": 2,
+        }
+    elif args.criterion == "dice_hd":
+        criterion_function = losses.DiceHDLoss
+        kwargs = {
+            "idc_hd": list(range(args.num_classes)),
+            "alpha_hd": 2,
+            "hybrid": False,
+            "include_background": True,
+            "sigmoid": True,
+            "softmax": False,
+            "squared_pred": True,
+            "weight_hd": 0.5,
+            "weight_dice": 0.5,
+        }
+    elif args.criterion == "boundary":
+        criterion_function = losses.BoundaryLoss
+        kwargs = {
+            "idc": list(range(args.num_classes)),
+            "sigmoid": True,
+            "softmax": False,
+        }
+    elif args.criterion == "dice_boundary":
+        criterion_function = losses.DiceBoundaryLoss
+        kwargs = {
+            "idc_boundary": list(range(args.num_classes)),
+            "include_background": True,
+            "sigmoid": True,
+            "softmax": False,
+            "squared_pred": True,
+        }
+    elif args.criterion in _MONAI_ONLY_CRITERIA:
+        raise NotImplementedError(f"--criterion {args.criterion} is MONAI's own loss and is not built here")
+    else:
+        raise NameError("Not Supported Criterion")
+    kwargs["reduction"] = "mean"
+    return criterion_function(**kwargs)

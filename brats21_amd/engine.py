@@ -6,7 +6,7 @@ import torch
 
 from . import ops
 from .evaluate import Evaluator  # noqa: F401  (re-export: the evaluate-step driver)
-from .losses import DiceLoss, deep_supervision_loss, fused_deep_supervision_dice
+from .losses import DiceLoss, deep_supervision_loss, deep_supervision_prepared_loss, fused_deep_supervision_dice
 
 
 class TrainStep:
@@ -19,7 +19,8 @@ class TrainStep:
         src/main_train.py:110): fp16 MFMA kernels (same rate, three more mantissa bits), the loss is scaled before
         backward, gradients are unscaled / checked for inf and the step is skipped on overflow by ``scaler``
         (a torch.amp.GradScaler, created here when none is passed) exactly as in the reference's loop.
-    ``buckets`` is a brats21_amd.ddp.GradientBuckets when world_size > 1."""
+    ``buckets`` is a brats21_amd.ddp.GradientBuckets when world_size > 1.  ``target`` is a tensor, or -- for the boundary
+    criteria of definer.make_criterion -- the pair [target, distance_map] (learning/engine.py:93-94)."""
 
     def __init__(self, model, optimizer, criterion=None, amp=True, buckets=None, fused_dice=True, jaccard=False,
                  max_grad_norm=None, amp_dtype=torch.bfloat16, scaler=None):
@@ -36,6 +37,8 @@ class TrainStep:
         """Engine._compute_loss (learning/engine.py:312-333): mean of the criterion over main + deep heads."""
         if self.fused:
             return fused_deep_supervision_dice(outputs, target, jaccard=self.jaccard)
+        if hasattr(self.criterion, "prepare"):  # the distance-map criteria: the target's field once per step, not per head
+            return deep_supervision_prepared_loss(self.criterion, outputs, target)[0]
         return deep_supervision_loss(self.criterion, outputs, target)[0]
 
     def _zero_grad(self):
@@ -124,7 +127,8 @@ class GraphedTrainStep:
         self.graph = self.static_image = self.static_target = self.static_loss = None
 
     def _capture(self, image, target):
-        self.static_image, self.static_target = image.clone(), target.clone()
+        pair = isinstance(target, (tuple, list))  # [target, distance_map] of the boundary criteria
+        self.static_image, self.static_target = image.clone(), [t.clone() for t in target] if pair else target.clone()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -146,8 +150,10 @@ class GraphedTrainStep:
         else:
             if image.data_ptr() != self.static_image.data_ptr():
                 self.static_image.copy_(image, non_blocking=True)
-            if target.data_ptr() != self.static_target.data_ptr():
-                self.static_target.copy_(target, non_blocking=True)
+            pair = isinstance(target, (tuple, list))
+            for new, static in zip(target, self.static_target) if pair else [(target, self.static_target)]:
+                if new.data_ptr() != static.data_ptr():
+                    static.copy_(new, non_blocking=True)
             sync_lr = getattr(self.step.optimizer, "sync_lr", None)
             if sync_lr is not None:
                 sync_lr()  # (a scheduler may have changed group["lr"] since the last replay)

@@ -1,7 +1,11 @@
 """Loss that "stays in PyTorch-ROCm" (BASELINE.json north_star): the Dice / Jaccard criterion the
 reference configures at src/definer.py:184-203 (monai.losses.DiceLoss(include_background=True,
 sigmoid=True, squared_pred=True, batch=True, reduction='mean', smooth 1e-5)) and the
-deep-supervision averaging of learning/engine.py:312-333."""
+deep-supervision averaging of learning/engine.py:312-333; and the distance-map criteria of learning/losses.py:59-467
+(HausdorffLoss, DiceHDLoss, SurfaceLoss = BoundaryLoss, DiceBoundaryLoss) as src/definer.py:246-282 configures them, on
+csrc/edt.hip + csrc/dist_loss.hip: no host round trip, so a step with them captures into a hipGraph like the Dice step."""
+from collections.abc import Sequence
+
 import torch
 import torch.nn as nn
 
@@ -82,3 +86,312 @@ def fused_deep_supervision_dice(outputs, target, jaccard=False, eps=1e-5):
     """Same value and gradients as deep_supervision_loss(DiceLoss(jaccard), outputs, target), fused."""
     heads = [outputs[0]] + list(outputs[1]) if isinstance(outputs, (tuple, list)) else [outputs]
     return _FusedDiceFn.apply(target, jaccard, eps, *heads)
+
+
+# ------------------------------------------------------------------------------------------ distance-map criteria
+def _check_reference_options(name, sigmoid, softmax, to_onehot_y, other_act, reduction):
+    """The option set src/definer.py:246-282 uses; everything else the reference's classes accept is not built."""
+    if not sigmoid:
+        raise NotImplementedError(f"{name}: only sigmoid=True is built (the kernels fuse the sigmoid, src/definer.py:246-282)")
+    if softmax or to_onehot_y or other_act is not None:
+        raise NotImplementedError(f"{name}: softmax / to_onehot_y / other_act are not built (the reference factory never sets them)")
+    if getattr(reduction, "value", reduction) != "mean":
+        raise NotImplementedError(f"{name}: only reduction='mean' is built")
+
+
+def _select(t, idc):
+    """t[:, idc] as contiguous f32; the full channel range (the factory's case) costs no copy."""
+    t = t.float()
+    if list(idc) != list(range(t.shape[1])):
+        t = t[:, list(idc)]
+    return t.contiguous()
+
+
+def _need_cuda(t, what):
+    if not t.is_cuda:
+        from . import _lib
+        raise _lib.BratsHipError(f"brats21_amd.losses.{what} runs on the GPU only (no CPU fallback)")
+
+
+class PreparedTarget:
+    """What a distance-map criterion derives from the target alone (criterion.prepare(target)): computed once per step and
+    shared by every deep-supervision head instead of once per head (learning/engine.py:326-329 recomputes it)."""
+
+    def __init__(self, owner, target, **fields):
+        self.owner, self.target = owner, target
+        self.__dict__.update(fields)
+
+
+def sigmoid_one_hot(logits):
+    """probs2one_hot(sigmoid(logits)) (learning/losses.py:43-56) as uint8 [N, K, ...]: 1 on the arg-max channel of every voxel,
+    ties to the lowest channel (csrc/dist_loss.hip)."""
+    from . import _lib
+    _need_cuda(logits, "sigmoid_one_hot")
+    x = logits.detach().contiguous().float()
+    n, k = x.shape[:2]
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().brats_sigmoid_argmax_onehot(x.data_ptr(), out.data_ptr(), n, k, x[0, 0].numel(),
+                                                          torch.cuda.current_stream().cuda_stream), "sigmoid_argmax_onehot")
+    return out
+
+
+def _loss_ws(lib, device):
+    return torch.empty(lib.brats_dist_loss_ws_floats(), dtype=torch.float32, device=device)
+
+
+class _HausdorffFn(torch.autograd.Function):
+    """mean of (p - t)^2 (tdm^alpha + pdm^alpha); the fields carry no gradient.  One statistics pass and one gradient pass
+    (brats_hd_loss_stats / brats_hd_loss_grad), the weight recomputed from the two fields in the backward."""
+
+    @staticmethod
+    def forward(ctx, logits, t, tdm, pdm, alpha):
+        from . import _lib
+        lib = _lib.lib()
+        x = logits.contiguous().float()
+        total = x.numel()
+        s = torch.empty(1, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.brats_hd_loss_stats(x.data_ptr(), t.data_ptr(), tdm.data_ptr(), pdm.data_ptr(), alpha, s.data_ptr(),
+                                               _loss_ws(lib, x.device).data_ptr(), total,
+                                               torch.cuda.current_stream().cuda_stream), "hd_loss_stats")
+        ctx.save_for_backward(x, t, tdm, pdm)
+        ctx.alpha = alpha
+        return s[0] / total
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _lib
+        x, t, tdm, pdm = ctx.saved_tensors
+        total = x.numel()
+        scale = (g.float() / total).reshape(1).contiguous()
+        dx = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().brats_hd_loss_grad(x.data_ptr(), t.data_ptr(), tdm.data_ptr(), pdm.data_ptr(), ctx.alpha,
+                                                     scale.data_ptr(), dx.data_ptr(), total,
+                                                     torch.cuda.current_stream().cuda_stream), "hd_loss_grad")
+        return dx, None, None, None, None
+
+
+class _BoundaryFn(torch.autograd.Function):
+    """mean of p * dist (brats_boundary_loss_stats / brats_boundary_loss_grad)."""
+
+    @staticmethod
+    def forward(ctx, logits, dist):
+        from . import _lib
+        lib = _lib.lib()
+        x = logits.contiguous().float()
+        total = x.numel()
+        s = torch.empty(1, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.brats_boundary_loss_stats(x.data_ptr(), dist.data_ptr(), s.data_ptr(), _loss_ws(lib, x.device).data_ptr(),
+                                                     total, torch.cuda.current_stream().cuda_stream), "boundary_loss_stats")
+        ctx.save_for_backward(x, dist)
+        return s[0] / total
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _lib
+        x, dist = ctx.saved_tensors
+        total = x.numel()
+        scale = (g.float() / total).reshape(1).contiguous()
+        dx = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().brats_boundary_loss_grad(x.data_ptr(), dist.data_ptr(), scale.data_ptr(), dx.data_ptr(), total,
+                                                           torch.cuda.current_stream().cuda_stream), "boundary_loss_grad")
+        return dx, None
+
+
+class _DiceFn(torch.autograd.Function):
+    """monai DiceLoss(sigmoid, squared_pred, reduction mean) on the kernels of the fused Dice (brats_dice_stats /
+    brats_dice_grad): batch=False -- one value per (n, k), one call per sample on its contiguous slice -- or batch=True."""
+
+    @staticmethod
+    def forward(ctx, logits, t, jaccard, smooth_nr, smooth_dr, batch):
+        from . import _lib
+        lib = _lib.lib()
+        st = torch.cuda.current_stream().cuda_stream
+        x = logits.contiguous().float()
+        n, k = x.shape[:2]
+        vox = x[0, 0].numel()
+        groups = [(x, t, n)] if batch else [(x[i], t[i], 1) for i in range(n)]
+        sums = torch.empty((len(groups), k, 3), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            ws = torch.empty(lib.brats_dice_ws_floats(n, k), dtype=torch.float32, device=x.device)
+            for i, (xs, ts, ns) in enumerate(groups):
+                _lib.check(lib.brats_dice_stats(xs.data_ptr(), ts.data_ptr(), sums[i].data_ptr(), ws.data_ptr(), ns, k, vox, st), "dice_stats")
+        inter, p2, t2 = sums[..., 0], sums[..., 1], sums[..., 2]
+        cnt = float(len(groups) * k)
+        num = 2.0 * inter + smooth_nr
+        if jaccard:
+            den = 2.0 * (t2 + p2 - inter) + smooth_dr
+            coef = torch.stack([(-2.0 / den - 2.0 * num / den ** 2) / cnt, 2.0 * num / den ** 2 / cnt], -1)
+        else:
+            den = t2 + p2 + smooth_dr
+            coef = torch.stack([-2.0 / den / cnt, num / den ** 2 / cnt], -1)
+        ctx.save_for_backward(x, t, coef.contiguous())
+        ctx.batch = batch
+        return (1.0 - num / den).mean()
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _lib
+        lib = _lib.lib()
+        st = torch.cuda.current_stream().cuda_stream
+        x, t, coef = ctx.saved_tensors
+        n, k = x.shape[:2]
+        vox = x[0, 0].numel()
+        coef = (coef * g).contiguous()
+        dx = torch.empty_like(x)
+        groups = [(x, t, dx, n)] if ctx.batch else [(x[i], t[i], dx[i], 1) for i in range(n)]
+        with torch.cuda.device(x.device):
+            for i, (xs, ts, ds, ns) in enumerate(groups):
+                _lib.check(lib.brats_dice_grad(xs.data_ptr(), ts.data_ptr(), coef[i].data_ptr(), ds.data_ptr(), ns, k, vox, st), "dice_grad")
+        return dx, None, None, None, None, None
+
+
+class _PreparedCriterion(nn.Module):
+    """criterion(logits, target): target is what the reference passes (a tensor, or the pair [target, distance_map] of the
+    boundary criteria, learning/engine.py:93-94) or the PreparedTarget of this criterion's prepare(target)."""
+
+    def _prepared(self, target):
+        if isinstance(target, PreparedTarget):
+            if target.owner is not self:
+                raise ValueError("the PreparedTarget was made by another criterion")
+            return target
+        return self.prepare(target)
+
+    def forward(self, logits, target):
+        _need_cuda(logits, type(self).__name__)
+        return self._loss(logits, self._prepared(target))
+
+
+class HausdorffLoss(_PreparedCriterion):
+    """learning/losses.py:98-179 with sigmoid=True, reduction mean: mean over N x len(idc) x voxels of
+    (p - t)^2 (tdm^alpha + pdm^alpha), tdm the distance transform of the target, pdm that of the arg-max one-hot of p
+    truncated to integers (the reference computes it into an int32 array, learning/losses.py:37,88,158-162)."""
+
+    def __init__(self, idc, alpha=2.0, to_onehot_y=False, sigmoid=False, softmax=False, other_act=None, reduction="mean"):
+        super().__init__()
+        _check_reference_options("HausdorffLoss", sigmoid, softmax, to_onehot_y, other_act, reduction)
+        self.idc, self.alpha = list(idc), float(alpha)
+
+    def prepare(self, target):
+        from .ops import distance_transform_edt
+        _need_cuda(target, "HausdorffLoss")
+        t = _select(target, self.idc)
+        return PreparedTarget(self, target, t=t, tdm=distance_transform_edt(t))
+
+    def _loss(self, logits, prep):
+        from .ops import distance_transform_edt
+        if logits.shape[0] != prep.t.shape[0] or logits.shape[2:] != prep.t.shape[2:] or logits.shape[1] != prep.target.shape[1]:
+            raise AssertionError(f"ground truth has different shape ({tuple(prep.target.shape)}) from input ({tuple(logits.shape)})")
+        onehot = sigmoid_one_hot(logits)  # the arg-max runs over ALL channels, idc selects afterwards (learning/losses.py:158-159)
+        x = logits
+        if self.idc != list(range(logits.shape[1])):
+            x, onehot = logits[:, self.idc], onehot[:, self.idc].contiguous()
+        # mode 2: the reference's predicted field is truncated (its one-hot is int32 and one_hot2hd_dist fills zeros_like of it)
+        return _HausdorffFn.apply(x, prep.t, prep.tdm, distance_transform_edt(onehot, mode=2), self.alpha)
+
+
+class SurfaceLoss(_PreparedCriterion):
+    """learning/losses.py:296-355 with sigmoid=True, reduction mean: mean of p * dist over N x len(idc) x voxels; `dist` is
+    the precomputed map (transforms.one_hot_to_dist) -- element 1 when the target is the pair [target, distance_map]."""
+
+    def __init__(self, idc, to_onehot_y=False, sigmoid=False, softmax=False, other_act=None, reduction="mean"):
+        super().__init__()
+        _check_reference_options(type(self).__name__, sigmoid, softmax, to_onehot_y, other_act, reduction)
+        self.idc = list(idc)
+
+    def prepare(self, target):
+        dist = target[1] if isinstance(target, Sequence) else target
+        _need_cuda(dist, "SurfaceLoss")
+        return PreparedTarget(self, target, full_shape=tuple(dist.shape), dist=_select(dist, self.idc))
+
+    def _loss(self, logits, prep):
+        if tuple(logits.shape) != prep.full_shape:
+            raise AssertionError(f"distance map has different shape ({prep.full_shape}) from input ({tuple(logits.shape)})")
+        x = logits if self.idc == list(range(logits.shape[1])) else logits[:, self.idc]
+        return _BoundaryFn.apply(x, prep.dist)
+
+
+BoundaryLoss = SurfaceLoss
+
+
+class _SigmoidDice(nn.Module):
+    """The monai DiceLoss inside the two hybrid criteria: sigmoid, squared_pred, include_background, reduction mean."""
+
+    def __init__(self, name, include_background, squared_pred, jaccard, smooth_nr, smooth_dr, batch):
+        super().__init__()
+        if not include_background or not squared_pred:
+            raise NotImplementedError(f"{name}: the Dice part is built for include_background=True, squared_pred=True "
+                                      "(src/definer.py:254-282)")
+        self.jaccard, self.smooth_nr, self.smooth_dr, self.batch = bool(jaccard), float(smooth_nr), float(smooth_dr), bool(batch)
+
+    def forward(self, logits, t):
+        if logits.shape != t.shape:
+            raise AssertionError(f"ground truth has different shape ({tuple(t.shape)}) from input ({tuple(logits.shape)})")
+        return _DiceFn.apply(logits, t, self.jaccard, self.smooth_nr, self.smooth_dr, self.batch)
+
+
+class DiceHDLoss(_PreparedCriterion):
+    """learning/losses.py:182-293: Dice + Hausdorff loss (hybrid=True: weight_dice * Dice + weight_hd * hd).  batch=False,
+    the reference factory's setting, is one Dice value per (sample, class)."""
+
+    def __init__(self, idc_hd, alpha_hd=2, hybrid=False, weight_hd=0.5, weight_dice=0.5, include_background=True, to_onehot_y=False,
+                 sigmoid=False, softmax=False, other_act=None, squared_pred=False, jaccard=False, reduction="mean", smooth_nr=1e-5,
+                 smooth_dr=1e-5, batch=False):
+        super().__init__()
+        self.hd = HausdorffLoss(idc=idc_hd, alpha=alpha_hd, to_onehot_y=to_onehot_y, sigmoid=sigmoid, softmax=softmax,
+                                other_act=other_act, reduction=reduction)
+        self.dice = _SigmoidDice("DiceHDLoss", include_background, squared_pred, jaccard, smooth_nr, smooth_dr, batch)
+        self.hybrid, self.weight_hd, self.weight_dice = bool(hybrid), float(weight_hd), float(weight_dice)
+
+    def prepare(self, target):
+        hd = self.hd.prepare(target)
+        full = hd.t if hd.t.shape == target.shape else target.contiguous().float()
+        return PreparedTarget(self, target, hd=hd, t=full)
+
+    def _loss(self, logits, prep):
+        if logits.dim() != prep.t.dim():
+            raise ValueError("the number of dimensions for input and target should be the same.")
+        dice, hd = self.dice(logits, prep.t), self.hd(logits, prep.hd)
+        return self.weight_dice * dice + self.weight_hd * hd if self.hybrid else dice + hd
+
+
+class DiceBoundaryLoss(_PreparedCriterion):
+    """learning/losses.py:361-467: lambda_dice * Dice(input, target[0]) + lambda_boundary * SurfaceLoss(input, target[1]);
+    the target is the pair [target, distance_map]."""
+
+    def __init__(self, idc_boundary, include_background=True, to_onehot_y=False, sigmoid=False, softmax=False, other_act=None,
+                 squared_pred=False, jaccard=False, reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5, batch=False, lambda_dice=1.0,
+                 lambda_boundary=1.0):
+        super().__init__()
+        self.boundary = BoundaryLoss(idc=idc_boundary, to_onehot_y=to_onehot_y, sigmoid=sigmoid, softmax=softmax, other_act=other_act,
+                                     reduction=reduction)
+        self.dice = _SigmoidDice("DiceBoundaryLoss", include_background, squared_pred, jaccard, smooth_nr, smooth_dr, batch)
+        if lambda_dice < 0.0:
+            raise ValueError("lambda_dice should be no less than 0.0.")
+        if lambda_boundary < 0.0:
+            raise ValueError("lambda_boundary should be no less than 0.0.")
+        self.lambda_dice, self.lambda_boundary = float(lambda_dice), float(lambda_boundary)
+
+    def prepare(self, target):
+        if not isinstance(target, Sequence) or len(target) != 2:
+            raise ValueError("DiceBoundaryLoss: the target is the pair [target, distance_map]")
+        _need_cuda(target[0], "DiceBoundaryLoss")
+        return PreparedTarget(self, target, boundary=self.boundary.prepare(target[1]), t=target[0].contiguous().float())
+
+    def _loss(self, logits, prep):
+        return self.lambda_dice * self.dice(logits, prep.t) + self.lambda_boundary * self.boundary(logits, prep.boundary)
+
+
+def deep_supervision_prepared_loss(criterion, outputs, target):
+    """deep_supervision_loss for a criterion with a prepare(target) step: what depends on the target alone (its distance
+    field, the selected and upcast tensors) is computed once and shared by the main and the deep heads.  Same value and
+    gradients as deep_supervision_loss(criterion, outputs, target), bit for bit."""
+    prepared = criterion.prepare(target)
+    if isinstance(outputs, (tuple, list)):
+        heads = [outputs[0]] + list(outputs[1])
+        return torch.stack([criterion(h, prepared) for h in heads]).mean(), outputs[0]
+    return criterion(outputs, prepared), outputs

@@ -1288,6 +1288,43 @@ def conv3d_wgrad_shift(x, dy, ksize=1, dil=1, want_dbias=False, out=None, amax_d
     return dw, db
 
 
+# ------------------------------------------------------------------------------------------ distance transform
+MASK_F32, MASK_U8 = 0, 1
+
+
+def distance_transform_edt(mask, mode=0):
+    """scipy.ndimage.distance_transform_edt(mask) with unit sampling over the last three axes of a cuda tensor [..., D, H, W]
+    (every leading index is a volume of its own): f32 distance of each foreground voxel (value != 0; f32, uint8 or bool
+    masks are read as they are, other dtypes through f32) to the nearest background voxel, 0 on background, bit-equal to
+    scipy's f64 result cast to f32 (csrc/edt.hip; a volume without background: the distance to index (-1, 0, 0), as scipy).
+    mode=1: the signed boundary map of the reference's one_hot2dist / OneHotToDist instead (transforms.one_hot_to_dist);
+    mode=2: the distance truncated to an integer (the predicted field of the reference's HausdorffLoss).
+    No host synchronisation: graph-capturable."""
+    if not mask.is_cuda:
+        raise _lib.BratsHipError("brats21_amd.ops.distance_transform_edt runs on the GPU only (no CPU fallback)")
+    if mask.dim() < 3:
+        raise ValueError("distance_transform_edt: expected [..., D, H, W]")
+    if mask.dtype == torch.bool:
+        m, kind = mask.contiguous().view(torch.uint8), MASK_U8
+    elif mask.dtype == torch.uint8:
+        m, kind = mask.contiguous(), MASK_U8
+    else:
+        m, kind = mask.contiguous().float(), MASK_F32
+    d, h, w = (int(v) for v in m.shape[-3:])
+    out = torch.empty(m.shape, dtype=torch.float32, device=m.device)
+    planes = m.numel() // max(1, d * h * w)
+    if m.numel() == 0:
+        return out
+    l = _lib.lib()
+    with torch.cuda.device(m.device):
+        nbytes = l.brats_edt_ws_bytes(planes, d, h, w)
+        if nbytes == 0:
+            raise ValueError(f"distance_transform_edt: unsupported shape {tuple(m.shape)} (D, H, W <= 2048, at most 65535 volumes)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=m.device)
+        _lib.check(l.brats_edt(m.data_ptr(), kind, planes, d, h, w, int(mode), out.data_ptr(), ws.data_ptr(), _stream()), "edt")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ box calibration
 def probe_box(device=None, mfma_ms=50.0, stream_bytes=403 << 20, modes=(0, 1)):
     """What THIS box delivers right now on the two resources the rooflines are quoted against (csrc/probe.hip): 16-bit

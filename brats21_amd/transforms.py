@@ -168,6 +168,18 @@ def divisible_pad(x, k=8):
     return spatial_pad(x, [-(-s // k) * k for s in x.shape[2:]])
 
 
+def one_hot_to_dist(seg):
+    """OneHotToDistd(sampling=[1, 1, 1]) (utils/transforms.py:95-142; the `distance_map` key of the boundary criteria,
+    src/definer.py:530-548) on a one-hot label [N, K, D, H, W] or [K, D, H, W]: per (sample, channel) with any foreground
+    edt(~m) * [~m] - (edt(m) - 1) * [m], zeros for an empty channel; f32, exact (csrc/edt.hip), no host round trip."""
+    if not seg.is_cuda:
+        raise _lib.BratsHipError("brats21_amd.transforms.one_hot_to_dist runs on the GPU only (no CPU fallback)")
+    if seg.dim() not in (4, 5):
+        raise ValueError("one_hot_to_dist: expected [N, K, D, H, W] or [K, D, H, W]")
+    from .ops import distance_transform_edt
+    return distance_transform_edt(seg, mode=1)
+
+
 class TrainAugment:
     """The random part of the reference's training chain (src/definer.py:458-466) on GPU-resident, already padded
     volumes: RandSpatialCrop(roi) -> RandRotate90(p=0.7, axes (0, 2)) -> RandFlip(p=0.7, all axes) ->
@@ -192,8 +204,10 @@ class TrainAugment:
             "smooth": tuple(float(self.R.uniform(0.25, 1.5)) for _ in range(3)) if self.R.rand() < 0.2 else None,
         }
 
-    def __call__(self, img, seg, params=None):
-        """img [N, 4, D, H, W], seg [N, 3, D, H, W] (cuda) -> (patch, label) of roi_size."""
+    def __call__(self, img, seg, params=None, distance_map=None):
+        """img [N, 4, D, H, W], seg [N, 3, D, H, W] (cuda) -> (patch, label) of roi_size; with distance_map [N, 3, D, H, W]
+        (one_hot_to_dist(seg): the boundary criteria's second target, add_key_when_distance_map of src/definer.py:530-548)
+        -> (patch, label, map), the map cropped, rotated and flipped like the label."""
         p = params or self.draw(img.shape[2:])
         perm = rot90_perm(p["k_rot"])
         if p["flip"]:
@@ -205,4 +219,7 @@ class TrainAugment:
             x = gamma_noise(x, p["gamma"], noise)
         if p.get("smooth") is not None:
             x = gaussian_smooth(x, p["smooth"])
-        return normalize_intensity(x, nonzero=True, channel_wise=True, remove_outliers=self.remove_outliers), y
+        x = normalize_intensity(x, nonzero=True, channel_wise=True, remove_outliers=self.remove_outliers)
+        if distance_map is None:
+            return x, y
+        return x, y, crop_perm(distance_map, p["start"], self.roi, perm)

@@ -52,7 +52,9 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * table of brats_conv3d_pack_weights_multi changed meaning); 5 in round 5 (additions only: brats_conv3d_set_x3_wgrad_fused,
  * brats_dropout, brats_evonorm_bwd_tiles + its workspace query); 6 in round 6 (additions only: brats_conv3d_set_kp); 7: additions
  * only (brats_cc_filter, brats_rare_fill + their workspace queries).  Still 7 after further additions only (brats_hausdorff +
- * its workspace query): an older library lacks them and says so when they are called (brats21_amd/_lib.py). */
+ * its workspace query; brats_edt + its workspace query, brats_sigmoid_argmax_onehot, brats_hd_loss_stats / _grad,
+ * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats): an older library lacks them and says so when they are called
+ * (brats21_amd/_lib.py), and tests/test_postproc_cpu.py pins the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
 const char* brats_last_error(void);
@@ -563,6 +565,49 @@ int brats_rare_fill(uint8_t* labels, int N, int D, int H, int W, int axis, int m
 size_t brats_hausdorff_ws_bytes(int NK, int D, int H, int W);
 int brats_hausdorff(const float* pred, const float* target, int NK, int D, int H, int W, double percentile, int directed,
                     float* out, void* ws, brats_stream_t s);
+
+/* ---- exact Euclidean distance transform (scipy.ndimage.distance_transform_edt with unit sampling) of `planes` independent
+ * volumes mask [planes][D][H][W]; mask_kind BRATS_MASK_F32 (foreground = value != 0) or BRATS_MASK_U8 (byte != 0).
+ * mode 0: out = distance of every foreground voxel to the nearest background voxel, 0 on background (the fields of
+ *   one_hot2hd_dist, learning/losses.py:77-95).
+ * mode 2: mode 0 truncated to an integer, floor(sqrt(d2)): what one_hot2hd_dist returns for an INTEGER one-hot -- it fills
+ *   np.zeros_like(seg), and HausdorffLoss hands it the int32 one-hot of probs2one_hot (learning/losses.py:37,88,158-162), so
+ *   the predicted field of the hd criteria is the truncated one.
+ * mode 1: the signed boundary map of one_hot2dist / OneHotToDist (learning/losses.py:59-74, utils/transforms.py:95-122): per
+ *   plane with any foreground edt(~m) * [~m] - (edt(m) - 1) * [m], all zeros for a plane without foreground.
+ * Squared distances are exact int32 (three separable passes: a row scan along W, then the integer lower-envelope scan along
+ * D and along H); the f32 result is sqrt in double rounded once, i.e. scipy's f64 field cast to f32, bit for bit.
+ * A plane without foreground gives zeros.  A plane without BACKGROUND gives the distance to a virtual background voxel at
+ * index (-1, 0, 0), sqrt((z + 1)^2 + y^2 + x^2), which is what scipy 1.15 returns there (pinned by tests/golden/losses.npz).
+ * Every decision is taken on the device: no host synchronisation, no allocation, deterministic, graph-capturable.
+ * ws: brats_edt_ws_bytes() device bytes (two int32 fields).  D, H, W <= 2048, planes <= 65535; BRATS_E_ARG beyond. */
+enum { BRATS_MASK_F32 = 0, BRATS_MASK_U8 = 1 };
+size_t brats_edt_ws_bytes(int planes, int D, int H, int W);
+int brats_edt(const void* mask, int mask_kind, int planes, int D, int H, int W, int mode, float* out, void* ws,
+              brats_stream_t s);
+
+/* ---- distance-map losses (learning/losses.py:98-467 as configured by src/definer.py:246-282: sigmoid, reduction mean).
+ * NCDHW f32 logits [N][K][voxels], p = sigmoid(x).
+ * sigmoid_argmax_onehot: probs2one_hot (learning/losses.py:43-56) of p: onehot[n][k][v] (uint8) = 1 iff k is the arg-max over
+ *   the channels of p[n][:][v], ties to the lowest channel -- compared on the kernels' own p, so equal or saturated
+ *   probabilities tie the way torch.argmax does on torch.sigmoid's.
+ * hd_loss (HausdorffLoss): sum[0] = sum over all elements of (p - t)^2 (tdm^alpha + pdm^alpha), the caller divides by the
+ *   count; grad: dx = 2 (p - t) (tdm^alpha + pdm^alpha) p (1 - p) * scale[0] (device scalar: upstream gradient / count).
+ *   tdm: the mode-0 field of the target, pdm: the mode-2 field of the predicted one-hot; they carry no gradient.  The weight
+ *   tdm^alpha + pdm^alpha is recomputed by the gradient pass from the two fields: writing it once and rereading it moves the
+ *   same 36 bytes per element over both passes and would cost one more full-size tensor per head.
+ * boundary_loss (SurfaceLoss): sum[0] = sum of p * dist; grad: dx = dist p (1 - p) * scale[0].
+ * ws: f32 workspace of brats_dist_loss_ws_floats() elements (per-block partials, added in block order). */
+size_t brats_dist_loss_ws_floats(void);
+int brats_sigmoid_argmax_onehot(const float* logits, uint8_t* onehot, int N, int K, size_t voxels, brats_stream_t s);
+int brats_hd_loss_stats(const float* logits, const float* target, const float* tdm, const float* pdm, float alpha,
+                        float* sum, float* ws, size_t total, brats_stream_t s);
+int brats_hd_loss_grad(const float* logits, const float* target, const float* tdm, const float* pdm, float alpha,
+                       const float* scale, float* dlogits, size_t total, brats_stream_t s);
+int brats_boundary_loss_stats(const float* logits, const float* dist, float* sum, float* ws, size_t total,
+                              brats_stream_t s);
+int brats_boundary_loss_grad(const float* logits, const float* dist, const float* scale, float* dlogits, size_t total,
+                             brats_stream_t s);
 
 /* ---- multi-tensor Ranger2020 step (learning/optimizer.py:136-255: RAdam with the
  * N_sma threshold, gradient centralisation :11-20, lookahead :233-240).  All tensors f32, contiguous.

@@ -1,0 +1,144 @@
+"""Device-event timing of the distance transform and the distance-map criteria (csrc/edt.hip, csrc/dist_loss.hip) on a
+training-sized batch [2, 3, 128, 128, 128]: median of `--calls` warm calls of
+  * the transform alone: the target's field (f32 mask), the predicted field (arg-max one-hot + uint8 mask, truncated),
+    the signed boundary map (both directions);
+  * forward + backward of each criterion of definer.make_criterion for one head and for five heads (the deep-supervision
+    count of EquiUnet), the target's field shared between the heads;
+  * the EquiUnet-48 training step (bf16, Ranger2020, eager and as one hipGraph) with --criterion hd beside the fused-Dice
+    step of the same run -- the comparison that matters.
+
+    python scripts/time_losses.py [--calls 20] [--patch 128] [--json out.json] [--host] [--no-step]
+
+--host, where scipy is importable, also times what the reference does instead on every head (learning/losses.py:153-162):
+device -> host copy, scipy.ndimage.distance_transform_edt per (sample, class), host -> device copy."""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from brats21_amd import definer, get_model, losses, ops, transforms  # noqa: E402
+
+
+def time_calls(fn, calls, warm=3):
+    for _ in range(warm):
+        fn()
+    times = []
+    for _ in range(calls):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b))
+    return {"median": round(float(np.median(times)), 4), "min": round(float(np.min(times)), 4), "max": round(float(np.max(times)), 4)}
+
+
+def tumour(n, size, dev):
+    """[n, 3, *size] nested balls (TC / WT / ET), a different centre per sample."""
+    z, y, x = torch.meshgrid(*[torch.arange(s, dtype=torch.float32, device=dev) for s in size], indexing="ij")
+    out = []
+    for i in range(n):
+        c = [s * (0.45 + 0.1 * i) for s in size]
+        r2 = (z - c[0]) ** 2 + (y - c[1]) ** 2 + (x - c[2]) ** 2
+        out.append(torch.stack([r2 <= (0.12 * size[0]) ** 2, r2 <= (0.25 * size[0]) ** 2, r2 <= (0.05 * size[0]) ** 2]))
+    return torch.stack(out).float()
+
+
+def criterion(name):
+    with contextlib.redirect_stdout(io.StringIO()):
+        return definer.make_criterion(argparse.Namespace(criterion=name, num_classes=3))
+
+
+def host_round_trip(target):
+    """seconds for one head's target field the reference's way: to the host, scipy per (sample, class), back"""
+    from scipy.ndimage import distance_transform_edt
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    m = target.cpu().numpy()
+    out = np.zeros_like(m)
+    for n in range(m.shape[0]):
+        for k in range(m.shape[1]):
+            pos = m[n, k].astype(bool)
+            if pos.any():
+                out[n, k] = distance_transform_edt(pos)
+    torch.tensor(out, device=target.device, dtype=torch.float32)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def step_times(dev, patch, calls, res):
+    from brats21_amd.engine import GraphedTrainStep, TrainStep
+    from brats21_amd.optim import Ranger2020
+    size = (patch,) * 3
+    x = torch.randn((2, 4) + size, device=dev)
+    t = tumour(2, size, dev)
+    for graph in (False, True):
+        for name in ("dice", "hd"):
+            torch.manual_seed(0)
+            with contextlib.redirect_stdout(io.StringIO()):
+                m = get_model(argparse.Namespace(model="equiunet", width=48, norm="group", act="relu", num_classes=3, dropout=0)).to(dev).train()
+                opt = Ranger2020(m.parameters(), lr=1e-4, alpha=0.5, k=6, N_sma_threshhold=5, betas=(.95, 0.999), eps=1e-5, weight_decay=1e-5,
+                                 capturable=graph)
+            step = TrainStep(m, opt, criterion=None if name == "dice" else criterion(name), amp=True)
+            if graph:
+                step = GraphedTrainStep(step, warmup=2)
+            res[f"step_equiunet48_{name}_{'graph' if graph else 'eager'}_ms"] = time_calls(lambda: step(x, t), calls)
+            del m, opt, step
+            torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--patch", type=int, default=128)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--no-step", action="store_true")
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    size = (a.patch,) * 3
+    res = {"shape": [2, 3] + list(size), "calls": a.calls}
+    t = tumour(2, size, dev)
+    heads = [torch.randn((2, 3) + size, device=dev).requires_grad_(True) for _ in range(5)]
+    oh = losses.sigmoid_one_hot(heads[0])
+    res["edt_target_f32_ms"] = time_calls(lambda: ops.distance_transform_edt(t), a.calls)
+    res["onehot_ms"] = time_calls(lambda: losses.sigmoid_one_hot(heads[0]), a.calls)
+    res["edt_predicted_u8_ms"] = time_calls(lambda: ops.distance_transform_edt(oh, mode=2), a.calls)
+    res["boundary_map_ms"] = time_calls(lambda: transforms.one_hot_to_dist(t), a.calls)
+    dist = transforms.one_hot_to_dist(t)
+    for name in ("hd", "dice_hd", "boundary", "dice_boundary"):
+        c = criterion(name)
+        label = [t, dist] if "boundary" in name else t
+        for nh in (1, 5):
+            def fwd_bwd():
+                for h in heads:
+                    h.grad = None
+                losses.deep_supervision_prepared_loss(c, (heads[0], heads[1:nh]), label)[0].backward()
+            res[f"{name}_fwd_bwd_{nh}head_ms"] = time_calls(fwd_bwd, a.calls)
+    if a.host:
+        try:
+            import scipy  # noqa: F401
+            res["host_scipy_round_trip_1head_target_s"] = round(host_round_trip(t), 3)
+            res["host_scipy_round_trip_1head_prediction_s"] = round(host_round_trip(oh.float()), 3)
+            res["host_cores"] = os.cpu_count()
+        except ImportError:
+            res["host_scipy_round_trip_1head_target_s"] = None
+    del heads
+    torch.cuda.empty_cache()
+    if not a.no_step:
+        step_times(dev, a.patch, a.calls, res)
+    print(json.dumps(res))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
