@@ -13,8 +13,8 @@ under autocast the bf16-storage / f32-accumulate kernels run, otherwise the exac
 (the 1e-3 logit parity mode).  ``model.precision = "bf16" | "fp32"`` overrides it.
 """
 import contextlib
+import functools
 import math
-
 import os
 
 import torch
@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import PACK_DGRAD, PACK_FWD, BratsHipError
+from ._program import _PackedWeightsModule, _fn_backward, _fn_forward, _heads_bwd, _inherit_amax
 
 
 # ------------------------------------------------------------------------------------------ parameter holders
@@ -153,88 +154,7 @@ def _head(cin, k):
     return nn.ModuleList([_ConvParams(cin, k, 1, bias=True)])  # key "<name>.0.weight" like nn.Sequential
 
 
-class _PackedWeightsModule(nn.Module):
-    """Keeps ops' no_grad packed-weight cache honest: the cache is dropped on every train() / eval() transition and on
-    every grad-enabled forward, so weights changed without a version bump (``p.data.copy_`` of the reference's
-    Ranger2020, learning/optimizer.py:243,253) are never served stale to a later evaluation."""
-
-    PRECISIONS = ("auto", "bf16", "fp16", "fp32", "x3", "fp16x3", "bf16x3", "x3fwd", "x3bwd")
-
-    @property
-    def precision(self):
-        return self._precision
-
-    @precision.setter
-    def precision(self, value):
-        # a typo ("X3", "x3 ") must not fall through to autocast / exact f32 under a parity-mode label (ADVICE r4)
-        if value not in self.PRECISIONS:
-            raise ValueError(f"model.precision / BRATS_PRECISION must be one of {self.PRECISIONS}, got {value!r}")
-        self._precision = value
-
-    def train(self, mode=True):
-        if mode != self.training:
-            ops.invalidate_packed_weights()
-        return super().train(mode)
-
-    def _init_dropout(self, p):
-        """--dropout p (src/arguments_train.py:52).  The masks come from this library's Philox stream (csrc/dropout.hip), seeded
-        from torch's CPU generator at construction (torch.manual_seed makes a run repeatable); the (seed, step counter) pair is a
-        non-persistent buffer: not part of the state dict, like torch's own RNG state."""
-        if not 0.0 <= float(p) < 1.0:
-            raise ValueError(f"dropout probability has to be in [0, 1), got {p}")
-        self.dropout_p = float(p)
-        # The seed comes from a PRIVATE generator seeded with torch.initial_seed(): constructing a model never advances the global
-        # CPU generator (the initial weights under a given torch.manual_seed do not depend on --dropout; ADVICE r5), and p = 0 draws
-        # nothing.  Data-parallel ranks build identical replicas under one torch seed: the rank is mixed in at the first forward
-        # (RANK of the launcher, else torch.distributed's rank) so that they draw different masks.
-        seed = 0
-        if self.dropout_p > 0.0:
-            seed = int(torch.randint(0, 2 ** 62, (1,), generator=torch.Generator().manual_seed(torch.initial_seed())))
-        self._dropout_seed_base, self._dropout_rank_mixed = seed, self.dropout_p == 0.0
-        self.register_buffer("_dropout_state", torch.tensor([seed, 0], dtype=torch.int64), persistent=False)
-
-    def _advance_dropout(self, device):
-        """Next step's dropout state: the counter moves ON THE DEVICE (a captured step draws fresh masks at every replay); the
-        returned copy belongs to this forward / backward pair."""
-        if self._dropout_state.device != device:
-            raise BratsHipError("brats21_amd: module and input are on different devices")
-        if not self._dropout_rank_mixed:
-            rank = os.environ.get("RANK")
-            if rank is None:
-                import torch.distributed as dist
-                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-            self._dropout_state[0] = (self._dropout_seed_base + 0x9E3779B97F4A7C15 * int(rank)) % (2 ** 63)
-            self._dropout_rank_mixed = True
-        self._dropout_state[1] += 1
-        return self._dropout_state.clone()
-
-    def _weights_may_have_changed(self):
-        if torch.is_grad_enabled():
-            ops.invalidate_packed_weights()
-
-
 # ------------------------------------------------------------------------------------------ programs
-class _AmaxSlots:
-    """Zero-initialised device scalars for the |max| side outputs of the producer kernels (one fill per pass)."""
-
-    def __init__(self, n, device):
-        self.buf = torch.zeros(n, dtype=torch.float32, device=device)
-        self.i = 0
-
-    def take(self):
-        s = self.buf[self.i:self.i + 1]
-        self.i += 1
-        return s
-
-
-def _inherit_amax(dst, src):
-    """max-pooling / trilinear interpolation never exceed the |max| of their input."""
-    a = getattr(src, "_amax", None)
-    if a is not None:
-        dst._amax = a
-    return dst
-
-
 def _f8_ok(fp8, dtype, x, x2=None):
     return (bool(fp8) and ops.is16(dtype) and x.shape[1] >= ops.F8_MIN_SIZE and
             ops.conv_f8_chunk(x.shape[-1], x2.shape[-1] if x2 is not None else 0) > 0)
@@ -255,11 +175,16 @@ def _one_sample(t):
     return t.view(1, n * d, h, w, c)
 
 
-def _bn_fwd_tail(unit, x, x2, y, stats, act, pool, training, drop=None):
+def _blk(b):
+    """(first, second) unit of a UBlock."""
+    return b.ConvBnRelu1, b.ConvBnRelu2
+
+
+def _bn_fwd_tail(cx, unit, x, x2, y, stats, pool):
     """BatchNorm3d + activation behind the convolution (see ConvBnRelu)."""
     n, d, h, wd, c = y.shape
     bn = unit.bn
-    if training:
+    if cx.training:
         mean_rstd, scale_shift = ops.gn_finalize(stats.view(1, -1, c, 2), 1, c, c, n * d * h * wd, bn.weight.detach(), bn.bias.detach())
         with torch.no_grad():  # running buffers: momentum 0.1, UNBIASED variance (torch.nn.functional.batch_norm)
             cnt = float(n * d * h * wd)
@@ -272,25 +197,30 @@ def _bn_fwd_tail(unit, x, x2, y, stats, act, pool, training, drop=None):
         mean_rstd = None
         scale = bn.weight.detach() * torch.rsqrt(bn.running_var + 1e-5)
         scale_shift = torch.stack([scale, bn.bias.detach() - bn.running_mean * scale], -1).reshape(1, c, 2).contiguous().float()
-    kact, slope_t = _unit_act(unit, act)
+    kact, slope_t = _unit_act(unit, cx.act)
     z = ops.affine_act(_one_sample(y), scale_shift, kact, slope_t=slope_t).view(n, d, h, wd, c)
-    if drop is not None:
-        ops.dropout(z, drop[0], drop[1], drop[2], out=z)
-    rec = (unit, x, x2, y, mean_rstd, scale_shift)
+    cx.dropped(z, cx.drop_of(unit), out=z)
+    cx.recs[unit] = (unit, x, x2, y, mean_rstd, scale_shift)
     if pool:
-        return (z, ops.maxpool2(z, want_argmax=pool == "argmax")), rec
-    return z, rec
+        return z, ops.maxpool2(z, want_argmax=pool == "argmax")
+    return z
 
 
-def _cgr_fwd(unit, x, dtype, act, out=None, x2=None, fp8=None, slots=None, no_act=False, pool=False, lazy=False, training=True,
-             drop=None):
+def _cgr_fwd(cx, unit, x, x2=None, *, no_act=False, pool=False, lazy=False):
     """One ConvBnRelu: pack -> implicit-GEMM conv over the virtual concat [x | x2] (+ tile statistics)
-    -> finalize -> normalise+act.  fp8: the convolution runs on the e4m3 kernel (scales from the |max| the producer of
-    x recorded); the normalise+act pass records the |max| of its own output for the next layer."""
-    # drop = (p, state, unit id): nn.Dropout(p) behind the activation (networks/equiunet2020.py:62; training mode only).  The
-    # activation is then always materialised (no fused pooling / head / on-load forms) and dropped in place (ops.dropout).
-    if drop is not None:
-        lazy = False
+    -> finalize -> normalise+act; what the backward needs goes to cx.recs[unit].  cx.fp8: the convolution runs on the e4m3
+    kernel (scales from the |max| the producer of x recorded); the normalise+act pass records the |max| of its own output for
+    the next layer.
+    no_act: return the raw convolution output (the last layer under the fused output head, ops.gn_head: the activation is
+    applied on load there).  pool: the layer ends an encoder level -> (z, max-pooled z).  lazy: z has one reader, the next
+    convolution -> an ops.Pending where cx.lazy_ok."""
+    dtype, fp8 = cx.dtype, cx.fp8
+    # nn.Dropout(p) behind the activation (networks/equiunet2020.py:62; training mode only).  The activation is then always
+    # materialised (no fused pooling / head / on-load forms) and dropped in place (ops.dropout).
+    uid = cx.drop_of(unit)
+    lazy = lazy and cx.lazy_ok and uid is None
+    if pool:  # (training: the pooling pass also records the arg-max bytes its backward reads)
+        pool = "argmax" if cx.will_bwd else True
     w = unit.conv.weight
     cbias, gamma_c, beta_c = None, unit.bn.weight.detach(), unit.bn.bias.detach()
     if unit.bcn:
@@ -328,47 +258,54 @@ def _cgr_fwd(unit, x, dtype, act, out=None, x2=None, fp8=None, slots=None, no_ac
     else:
         with ops.use_plan(None) if unit.bcn else contextlib.nullcontext():  # (a_c * W is a new tensor every step: not a plan entry)
             wpk = ops.pack_weights(w, dtype, PACK_FWD, cin_pad=cin_pad, dil=unit.dilation, c1=c1)
-        # (_x3amax: the network input in split-precision mode -- the only conv input no normalisation has bounded; see _EquiUnetFn)
+        # (_x3amax: the network input in split-precision mode -- the only conv input no normalisation has bounded; see _fn_forward)
         y, stats = ops.conv3d(x, wpk, cout, 3, unit.dilation, want_stats=True, x2=x2, amax=getattr(x, "_x3amax", None), bias=cbias)
     n, d, h, wd, _ = y.shape
     if unit.batch_norm:
-        return _bn_fwd_tail(unit, x, x2, y, stats, act, pool, training, drop)
+        return _bn_fwd_tail(cx, unit, x, x2, y, stats, pool)
     mean_rstd, scale_shift = ops.gn_finalize(stats, n, cout, unit.groups, d * h * wd, gamma_c, beta_c)
-    if no_act:  # the last layer under the fused output head (ops.gn_head): the activation is applied on load there
-        return y, (unit, x, x2, y, mean_rstd, scale_shift)
-    amax = slots.take() if slots is not None else None
-    kact, slope_t = _unit_act(unit, act)
+    rec = (unit, x, x2, y, mean_rstd, scale_shift)
+    if no_act:
+        cx.recs[unit] = rec
+        return y
+    amax = cx.slot(y.device)
+    kact, slope_t = _unit_act(unit, cx.act)
     if lazy and slope_t is None and kact in ("relu", "leakyrelu") and amax is None and not pool:
-        return ops.Pending(y, scale_shift, kact), None  # (no_grad only: nothing is taped)
-    if pool and drop is None and kact in ("relu", "leakyrelu") and y.numel() * y.element_size() >= (256 << 20):
-        # the layer ends an encoder level: normalise + act and the 2x2x2 max pool of the result in one pass -- for tensors
+        return ops.Pending(y, scale_shift, kact)  # (no_grad only: nothing is taped)
+    cx.recs[unit] = rec
+    if pool and uid is None and kact in ("relu", "leakyrelu") and y.numel() * y.element_size() >= (256 << 20):
+        # normalise + act and the 2x2x2 max pool of the result in one pass -- for tensors
         # beyond the Infinity Cache (the 128^3 level: 188 us against 148 + 85); smaller ones are re-read from the cache by
         # the pooling kernel at no HBM cost and the two plain kernels are as fast (measured: 70 against 63 us)
         z, pooled = ops.affine_act_pool(y, scale_shift, kact, amax=amax, slope_t=slope_t, want_argmax=pool == "argmax")
         if amax is not None:
             z._amax = pooled._amax = amax  # (max|pool(z)| <= max|z|: the pooled tensor inherits the scale source)
-        return (z, pooled), (unit, x, x2, y, mean_rstd, scale_shift)
-    z = ops.affine_act(y, scale_shift, kact, out=out, amax=amax, slope_t=slope_t)
+        return z, pooled
+    z = ops.affine_act(y, scale_shift, kact, amax=amax, slope_t=slope_t)
     if amax is not None:
         z._amax = amax
-    if drop is not None:
-        ops.dropout(z, drop[0], drop[1], drop[2], out=z)
+    cx.dropped(z, uid, out=z)
     if pool:
-        return (z, _inherit_amax(ops.maxpool2(z, want_argmax=pool == "argmax"), z)), (unit, x, x2, y, mean_rstd, scale_shift)
-    return z, (unit, x, x2, y, mean_rstd, scale_shift)
+        return z, _inherit_amax(ops.maxpool2(z, want_argmax=pool == "argmax"), z)
+    return z
 
 
-def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=None, slots=None, dest=None, head=None,
-             pool=None, bst=None, drop=None):
-    """Returns dx, or (dx1, dx2) -- two dense tensors from one dgrad launch -- for a two-source unit.
-    bst: the record of the unit that PRODUCED this unit's input (the first unit of the block).  Where the kernel form is built,
-    the input-gradient launch also takes the first pass of that unit's GroupNorm backward (ops.conv3d_bstats) and dx is
-    returned as (dx, tile_stats); handed on as `dz`, such a pair makes this function finish from the tile sums
-    (ops.gn_act_bwd_tiles) instead of reading dz and y twice.
-    fp8 == "all": the input gradient (dgrad) and -- for the dilation-1 layers the all-taps kernel covers -- the weight
+def _cgr_bwd(cx, unit, dz, *, need_dx=True, head=None, pool=None, bst=None):
+    """Backward of one ConvBnRelu; the parameter gradients go to cx.put.  Returns dx, or (dx1, dx2) -- two dense tensors from
+    one dgrad launch -- for a two-source unit.
+    head = (head module, dlogits) instead of dz: the last layer, whose output feeds only the 1x1x1 head.
+    pool = (d_skip, d_pooled, arg-max bytes) instead of dz: the layer ends an encoder level.
+    bst: the unit that PRODUCED this unit's input (the first unit of the block).  Where the kernel form is built
+    (model.fold_bwd_stats), the input-gradient launch also takes the first pass of that unit's GroupNorm backward
+    (ops.conv3d_bstats) and dx is returned as (dx, tile_stats); handed on as `dz`, such a pair makes this function finish from
+    the tile sums (ops.gn_act_bwd_tiles) instead of reading dz and y twice.
+    cx.fp8 == "all": the input gradient (dgrad) and -- for the dilation-1 layers the all-taps kernel covers -- the weight
     gradient run on the e4m3 kernels too, scaled by the |max| of dy that the GroupNorm backward records (and the |max| of
     the layer input recorded in the forward pass)."""
-    unit, x, x2, y, mean_rstd, scale_shift = rec
+    _, x, x2, y, mean_rstd, scale_shift = cx.recs[unit]
+    dtype, fp8 = cx.dtype, cx.fp8
+    if bst is not None:  # dropout: the folds that never materialise a unit's output gradient are off
+        bst = cx.recs[bst] if (cx.m.fold_bwd_stats and cx.drop is None) else None
     cin = unit.conv.weight.shape[1]
     gamma_c = unit.bn.weight.detach()
     w_bwd = unit.conv.weight
@@ -379,8 +316,7 @@ def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=Non
     tiles = None
     if isinstance(dz, tuple):
         dz, tiles = dz
-    if drop is not None:  # the forward's mask, regenerated: d(dropout(z)) / dz = the same multiplier (ops.dropout)
-        dz = ops.dropout(dz, drop[0], drop[1], drop[2])
+    dz = cx.dropped(dz, cx.drop_of(unit))  # the forward's mask, regenerated: d(dropout(z)) / dz = the same multiplier
     all8 = fp8 == "all" and ops.is16(dtype)
     f8 = all8 and need_dx and ops.conv_f8_chunk(y.shape[-1]) > 0
     # e4m3 weight gradient: where the all-taps kernel is built for the layer and the producers of x (x2) recorded |max|
@@ -388,13 +324,11 @@ def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=Non
     w8 = (all8 and unit.dilation == 1 and ax is not None and (x2 is None or ax2 is not None) and ops.is16(y.dtype)
           and ops.conv3d_wgrad_f8_ok(x, y, x2))
     # split precision on fp16 pairs: dy (values of 1e-6 and below) is scaled by a power of two taken from its recorded |max|
-    x3s = ops.x3_mode() == ops.X3F and dtype == torch.float32
-    amax = slots.take() if ((f8 or w8 or x3s) and slots is not None) else None
-    kact, slope_t = _unit_act(unit, act)
+    x3s = cx.x3s
+    amax = cx.slot(y.device, True) if (f8 or w8 or x3s) else None
+    kact, slope_t = _unit_act(unit, cx.act)
     if slope_t is not None:
-        grads[names[unit.prelu.weight]] = ops.prelu_slope_grad(dz, y, scale_shift)
-        if sink is not None:
-            sink(names[unit.prelu.weight], grads[names[unit.prelu.weight]])
+        cx.put(unit.prelu.weight, ops.prelu_slope_grad(dz, y, scale_shift))
     if unit.batch_norm:
         if mean_rstd is None:
             raise NotImplementedError("--norm batch: backward through an eval-mode forward (running statistics) is not implemented")
@@ -405,18 +339,16 @@ def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=Non
         if amax is not None:
             dy._amax = amax
     elif head is not None:
-        # the last layer: its output feeds only the 1x1x1 head, whose backward is folded into the GroupNorm backward --
-        # d(up1) is never written, the head's weight / bias gradients come out of the same passes (ops.gn_act_bwd_head)
+        # the head's backward is folded into the GroupNorm backward -- d(up1) is never written, the head's weight / bias
+        # gradients come out of the same passes (ops.gn_act_bwd_head)
         hd, dout = head
         dy, dgamma, dbeta, dhw, dhb = ops.gn_act_bwd_head(dout, hd.weight, y, scale_shift, mean_rstd, gamma_c,
                                                           unit.groups, kact, amax=amax)
-        for prm, g in ((hd.weight, dhw), (hd.bias, dhb)):
-            grads[names[prm]] = g
-            if sink is not None:
-                sink(names[prm], g)
+        cx.put(hd.weight, dhw)
+        cx.put(hd.bias, dhb)
     elif pool is not None:
-        # the layer ends an encoder level: dz = skip gradient + max-pool backward, composed inside the GroupNorm backward from
-        # (d_skip, d_pooled, arg-max bytes) -- the pooling backward's output tensor is never written (ops.gn_act_bwd_pool)
+        # dz = skip gradient + max-pool backward, composed inside the GroupNorm backward -- the pooling backward's output
+        # tensor is never written (ops.gn_act_bwd_pool)
         dy, dgamma, dbeta = ops.gn_act_bwd_pool(pool[0], pool[1], pool[2], y, scale_shift, mean_rstd, gamma_c,
                                                 unit.groups, kact, amax=amax)
     elif tiles is not None:
@@ -425,8 +357,7 @@ def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=Non
     else:
         dy, dgamma, dbeta = ops.gn_act_bwd(dz, y, scale_shift, mean_rstd, gamma_c, unit.groups, kact, amax=amax,
                                            slope_t=slope_t)
-    # data-parallel: the weight gradient is written straight into its slice of the all-reduce bucket
-    wdst = dest(names[unit.conv.weight]) if dest is not None else None
+    wdst = cx.dest(unit.conv.weight)  # data-parallel: the weight gradient is written straight into its slice of the bucket
     if w8 and amax is not None:
         dw = ops.conv3d_wgrad_f8(x, dy, ax, amax, x2=x2, amax2=ax2, out=wdst)
     elif x2 is not None and x.shape[-1] % 16:  # narrow test widths only: the wgrad ci tile (16) would straddle x | x2
@@ -440,9 +371,7 @@ def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=Non
     else:
         pg = {unit.conv.weight: dw, unit.bn.weight: dgamma, unit.bn.bias: dbeta}
     for prm, g in pg.items():
-        grads[names[prm]] = g
-        if sink is not None:  # data-parallel: hand finished gradients to the bucketed all-reduce right away
-            sink(names[prm], g)
+        cx.put(prm, g)
     if not need_dx:
         return None
     if f8:
@@ -459,7 +388,7 @@ def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=Non
     if x2 is None:
         if bst is not None and not f8:
             u1, _, _, y1, mr1, ss1 = bst
-            kact1, slope1 = _unit_act(u1, act)
+            kact1, slope1 = _unit_act(u1, cx.act)
             if (not u1.batch_norm and not u1.bcn and not unit.bcn and mr1 is not None and y1.shape[-1] == cin and y1.dtype == dy.dtype
                     and ops.conv_bstats_ok(dtype, unit.dilation, dy.shape[-1], cin, kact1, slope1)):
                 # (dx, tile sums of u1's GroupNorm backward)
@@ -474,74 +403,27 @@ def _cgr_bwd(rec, dz, dtype, act, grads, names, need_dx=True, sink=None, fp8=Non
     return dx[..., :c1], dx[..., c1:]
 
 
-def douts_device(douts):
-    return next(d.device for d in douts if d is not None)
-
-
 class _EquiUnetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, dtype, *params):
-        # training: the module packed all layers' weights up front (ops.plan_for); pack_weights() then returns views
-        ctx.plan = ops._PLANS.get(model) if (model.training and model.pack_plan) else None
-        ctx.x3 = model._x3_modes() if dtype == torch.float32 else (None, None)
-        with ops.use_plan(ctx.plan), ops.split_precision(ctx.x3[0]):
-            return _EquiUnetFn._forward(ctx, model, x, dtype, *params)
+        return _fn_forward(_EquiUnetFn._forward, ctx, model, x, dtype, params)
 
     @staticmethod
     def backward(ctx, *douts):
-        with ops.use_plan(ctx.plan), ops.split_precision(ctx.x3[1]):
-            return _EquiUnetFn._backward(ctx, *douts)
+        return _fn_backward(_EquiUnetFn._backward, ctx, douts)
 
     @staticmethod
-    def _forward(ctx, model, x, dtype, *params):
-        m = model
-        act = m.act
-        f = m.features
-        n, _, d, h, w = x.shape
-        dev = x.device
-        tape = []
-
-        fp8 = m.conv_fp8 if ops.is16(dtype) else None
-        slots = _AmaxSlots(32, dev) if fp8 else None
-
-        will_bwd = any(ctx.needs_input_grad) and model._fwd_grad  # (needs_input_grad ignores no_grad)
-
-        # inference (no_grad): the activation between the two units of a block has ONE reader, the block's second
-        # convolution -- it is never stored (ops.Pending: normalise + act applied on load, model.norm_on_load)
-        lazy_ok = (not will_bwd) and (not torch.is_grad_enabled()) and m.norm_on_load and ops.is16(dtype)
-
-        # nn.Dropout(p) behind every unit's activation, training mode only (networks/equiunet2020.py:62): the state (seed, step
-        # counter) is advanced on the device and a copy travels to the backward, which regenerates the masks from it
-        drop_state = m._advance_dropout(dev) if (m.training and m.dropout_p > 0.0) else None
-        ctx.drop_state = drop_state
-        if drop_state is not None and fp8:
-            raise NotImplementedError("--dropout > 0 with the e4m3 convolution path is not implemented")
-
-        def drop_of(unit):
-            return (m.dropout_p, drop_state, m._unit_ids[unit]) if drop_state is not None else None
-
-        def cgr(unit, xin, x2=None, pool=False, lazy=False):
-            # (training: the fused pooling pass also records the arg-max bytes its backward reads)
-            z, rec = _cgr_fwd(unit, xin, dtype, act, None, x2, fp8, slots, pool=("argmax" if will_bwd else True) if pool else False,
-                              lazy=lazy and lazy_ok, training=m.training, drop=drop_of(unit))
-            tape.append(rec)
-            return z
+    def _forward(ctx, cx, x0):
+        m = cx.m
+        cgr = functools.partial(_cgr_fwd, cx)
 
         def up(t):
             return _inherit_amax(ops.upsample(t, 2), t)
 
-        x0 = ops.ncdhw_to_ndhwc(x, dtype, cpad=8 if (ops.is16(dtype) or ops.x3_active()) else 4)
-        if ops.x3_mode() == ops.X3F:
-            # fp16 pairs overflow at |x| >= 65504 (hi = inf, lo = NaN: silently NaN logits).  Every other convolution
-            # input is a normalised activation; the network INPUT is whatever the caller passes (un-normalised volumes reach
-            # 3e4 and more), so its |max| is recorded (one 134 MB pass at 2 x 128^3) and the first layer's forward scales by the
-            # matching power of two (brats_conv3d_x3_fwd's xamax: exact).  The first layer's WEIGHT gradient still splits the
-            # unscaled input: split-precision training expects z-scored inputs like the reference's pipeline produces
-            # (utils/transforms.py:364-385), inference does not.
-            x0._x3amax = ops.absmax(x0)
         # encoder (networks/equiunet2020.py:469-475); every tensor is dense NDHWC, the decoder convolutions
         # read the virtual concat [skip | up-sampled] from two pointers (no torch.cat, no strided slices)
-        # (the last layer of a level writes its activation -- the skip connection -- and the max-pooled tensor in one pass)
+        # (the last layer of a level writes its activation -- the skip connection -- and the max-pooled tensor in one pass;
+        #  lazy: the activation between the two units of a block has ONE reader, the block's second convolution)
         down1, p1 = cgr(m.encoder1.ConvBnRelu2, cgr(m.encoder1.ConvBnRelu1, x0, lazy=True), pool=True)
         down2, p2 = cgr(m.encoder2.ConvBnRelu2, cgr(m.encoder2.ConvBnRelu1, p1, lazy=True), pool=True)
         down3, p3 = cgr(m.encoder3.ConvBnRelu2, cgr(m.encoder3.ConvBnRelu1, p2, lazy=True), pool=True)
@@ -557,83 +439,48 @@ class _EquiUnetFn(torch.autograd.Function):
         # the last layer's activation up1 feeds only the output head: where the kernels for it are built, the head reads
         # the raw convolution output and applies GroupNorm + act on load (ops.gn_head), the backward recomputes what it
         # needs (ops.gn_act_bwd_head) -- up1 (2 x 403 MB written + read at 2 x 48 x 128^3) is never stored
-        kact, slope_t = _unit_act(m.decoder1.ConvBnRelu2, act)
+        last = m.decoder1.ConvBnRelu2
+        kact, slope_t = _unit_act(last, cx.act)
         nk = m.outconv.weight.shape[0]
-        fuse_top = (m.fold_head_fwd and drop_state is None and not m.decoder1.ConvBnRelu2.batch_norm and slope_t is None and kact in ("relu", "leakyrelu") and nk <= 4
-                    and (not will_bwd or (m.fold_head_bwd and ops.head_fold_ok(m.outconv.weight, kact, slope_t))))
+        fuse_top = (m.fold_head_fwd and cx.drop is None and not last.batch_norm and slope_t is None and kact in ("relu", "leakyrelu")
+                    and nk <= 4 and (not cx.will_bwd or (m.fold_head_bwd and ops.head_fold_ok(m.outconv.weight, kact, slope_t))))
         if fuse_top:
-            y1, rec1 = _cgr_fwd(m.decoder1.ConvBnRelu2, u1, dtype, act, None, None, fp8, slots, no_act=True)
-            tape.append(rec1)
+            y1 = cgr(last, u1, no_act=True)
             up1 = None
-            outs = [ops.gn_head(y1, rec1[5], m.outconv.weight, m.outconv.bias, kact)]
+            outs = [ops.gn_head(y1, cx.recs[last][5], m.outconv.weight, m.outconv.bias, kact)]
         else:
-            up1 = cgr(m.decoder1.ConvBnRelu2, u1)
+            up1 = cgr(last, u1)
             outs = [ops.head(up1, m.outconv.weight, m.outconv.bias, 1)]
         ctx.top_fused = fuse_top
         ctx.out_shape = tuple(outs[0].shape)
-        heads = [(m.outconv, up1, 1)]
+        ctx.heads = [(m.outconv, up1, 1)]
         if deep_heads:
             for hd, src, sc in ((m.deep_bottom[0], bottom, 8), (m.deep_bottom2[0], bottom_2, 8), (m.deep3[0], up3, 4),
                                 (m.deep2[0], up2, 2)):
                 outs.append(ops.head(src, hd.weight, hd.bias, sc))
-                heads.append((hd, src, sc))
-        ctx.model, ctx.dtype, ctx.tape, ctx.heads = m, dtype, tape, heads
+                ctx.heads.append((hd, src, sc))
         ctx.bufs = (down1, down2, down3, down4, bottom, bottom_2, up3, up2, up1)
-        ctx.nparams = len(params)
         return tuple(outs)
 
     @staticmethod
-    def _backward(ctx, *douts):
-        m, dtype, tape = ctx.model, ctx.dtype, ctx.tape
-        act, f = m.act, m.features
-        names = {p: i for i, p in enumerate(m.parameters())}
-        grads = {}
+    def _backward(ctx, cx, *douts):
+        m = cx.m
         down1, down2, down3, down4, bottom, bottom_2, up3, up2, up1 = ctx.bufs
-        rec = {r[0]: r for r in tape}
+        cbw = functools.partial(_cgr_bwd, cx)
 
-        fp8 = m.conv_fp8 if ops.is16(dtype) else None
-        slots = _AmaxSlots(32, douts[0].device) if (fp8 == "all" or ops.x3_mode() == ops.X3F) else None
-
-        drop_state = ctx.drop_state  # dropout: the folds that never materialise a unit's output gradient are off
-
-        def cbw(unit, dz, need_dx=True, head=None, pool=None, first=None):
-            # first: the block's first unit, whose output is this unit's only input -- its GroupNorm backward's first pass rides
-            # in this unit's input-gradient launch (model.fold_bwd_stats)
-            bst = rec[first] if (first is not None and m.fold_bwd_stats and drop_state is None) else None
-            drop = (m.dropout_p, drop_state, m._unit_ids[unit]) if drop_state is not None else None
-            return _cgr_bwd(rec[unit], dz, dtype, act, grads, names, need_dx, m._grad_sink, fp8, slots, m._grad_dest, head, pool, bst,
-                            drop)
-
-        def level_bwd(unit, down, d_pooled, d_skip, need_dx=True, first=None):
+        def level_bwd(unit, down, d_pooled, d_skip, need_dx=True, bst=None):
             """Backward of the last layer of an encoder level: its output gradient = d_skip + max-pool backward(d_pooled)."""
             idx = getattr(down, "_pool_argmax", None)
-            kact, slope_t = _unit_act(unit, act)
-            if (idx is not None and m.fold_pool_bwd and drop_state is None and not unit.batch_norm and slope_t is None
+            kact, slope_t = _unit_act(unit, cx.act)
+            if (idx is not None and m.fold_pool_bwd and cx.drop is None and not unit.batch_norm and slope_t is None
                     and kact in ("relu", "leakyrelu")):
-                return cbw(unit, None, need_dx, pool=(d_skip, d_pooled, idx), first=first)
-            return cbw(unit, ops.maxpool2_bwd(down, d_pooled, dx_skip=d_skip), need_dx, first=first)
+                return cbw(unit, None, need_dx=need_dx, pool=(d_skip, d_pooled, idx), bst=bst)
+            return cbw(unit, ops.maxpool2_bwd(down, d_pooled, dx_skip=d_skip), need_dx=need_dx, bst=bst)
 
-        # heads: d(logits) -> gradient w.r.t. their NDHWC source tensors
-        dsrc = {}
-        top = None  # the output head on up1: folded into the GroupNorm backward of the last layer where that is built
-        for (hd, src, sc), dout in zip(ctx.heads, douts):
-            if dout is None and hd is m.outconv and ctx.top_fused:
-                # a loss built from the deep heads only: the fused top has no stored up1 to fall back on -- zero logit gradients
-                dout = torch.zeros((ctx.out_shape), dtype=torch.float32, device=douts_device(douts))
-            if dout is None:
-                continue
-            if hd is m.outconv and (ctx.top_fused or (m.fold_head_bwd and drop_state is None and not m.decoder1.ConvBnRelu2.batch_norm
-                                                       and ops.head_fold_ok(hd.weight, *_unit_act(m.decoder1.ConvBnRelu2, act)))):
-                top = (hd, dout)
-                continue
-            dx, dw, db = ops.head_bwd(src, hd.weight, dout, sc)
-            grads[names[hd.weight]] = dw
-            grads[names[hd.bias]] = db
-            if m._grad_sink is not None:
-                m._grad_sink(names[hd.weight], dw)
-                m._grad_sink(names[hd.bias], db)
-            key = src.data_ptr()
-            dsrc[key] = dx if key not in dsrc else dsrc[key] + dx
+        c1, c2 = _blk(m.decoder1)
+        # the output head on up1: folded into the GroupNorm backward of the last layer where that is built
+        top, dsrc = _heads_bwd(ctx, cx, douts, m.fold_head_bwd and cx.drop is None and not c2.batch_norm
+                               and ops.head_fold_ok(m.outconv.weight, *_unit_act(c2, cx.act)))
 
         def extra(t):
             return dsrc.get(t.data_ptr())
@@ -641,39 +488,34 @@ class _EquiUnetFn(torch.autograd.Function):
         def plus(a, b):
             return a if b is None else a + b
 
-        def blk(b):  # (first, second) unit of a block
-            return b.ConvBnRelu1, b.ConvBnRelu2
-
-        c1, c2 = blk(m.decoder1)
-        d_c1 = cbw(c2, None, head=top, first=c1) if top is not None else cbw(c2, extra(up1) if extra(up1) is not None else torch.zeros_like(up1), first=c1)
+        d_c1 = cbw(c2, None, head=top, bst=c1) if top is not None else cbw(c2, extra(up1) if extra(up1) is not None else torch.zeros_like(up1), bst=c1)
         d_skip1, d_u1 = cbw(c1, d_c1)
         d_up2 = plus(ops.upsample_bwd(d_u1, 2), extra(up2))
-        c1, c2 = blk(m.decoder2)
-        d_skip2, d_u2 = cbw(c1, cbw(c2, d_up2, first=c1))
+        c1, c2 = _blk(m.decoder2)
+        d_skip2, d_u2 = cbw(c1, cbw(c2, d_up2, bst=c1))
         d_up3 = plus(ops.upsample_bwd(d_u2, 2), extra(up3))
-        c1, c2 = blk(m.decoder3)
-        d_skip3, d_u3 = cbw(c1, cbw(c2, d_up3, first=c1))
+        c1, c2 = _blk(m.decoder3)
+        d_skip3, d_u3 = cbw(c1, cbw(c2, d_up3, bst=c1))
         d_b2 = plus(ops.upsample_bwd(d_u3, 2), extra(bottom_2))
         d_skip4, d_bot = cbw(m.bottom_2, d_b2)
         d_bottom = plus(d_bot, extra(bottom))
-        c1, c2 = blk(m.bottom)
-        d_down4 = d_skip4 + cbw(c1, cbw(c2, d_bottom, first=c1))
-        c1, c2 = blk(m.encoder4)
-        d_p3 = cbw(c1, cbw(c2, d_down4, first=c1))
-        c1, c2 = blk(m.encoder3)
-        d_p2 = cbw(c1, level_bwd(c2, down3, d_p3, d_skip3, first=c1))
-        c1, c2 = blk(m.encoder2)
-        d_p1 = cbw(c1, level_bwd(c2, down2, d_p2, d_skip2, first=c1))
-        c1, c2 = blk(m.encoder1)
-        cbw(c1, level_bwd(c2, down1, d_p1, d_skip1, first=c1), need_dx=False)
-        ctx.tape = ctx.bufs = None
-        return (None, None, None) + tuple(grads.get(i) for i in range(ctx.nparams))
-
+        c1, c2 = _blk(m.bottom)
+        d_down4 = d_skip4 + cbw(c1, cbw(c2, d_bottom, bst=c1))
+        c1, c2 = _blk(m.encoder4)
+        d_p3 = cbw(c1, cbw(c2, d_down4, bst=c1))
+        c1, c2 = _blk(m.encoder3)
+        d_p2 = cbw(c1, level_bwd(c2, down3, d_p3, d_skip3, bst=c1))
+        c1, c2 = _blk(m.encoder2)
+        d_p1 = cbw(c1, level_bwd(c2, down2, d_p2, d_skip2, bst=c1))
+        c1, c2 = _blk(m.encoder1)
+        cbw(c1, level_bwd(c2, down1, d_p1, d_skip1, bst=c1), need_dx=False)
+        ctx.bufs = None
 
 # ------------------------------------------------------------------------------------------ module
 class EquiUnet(_PackedWeightsModule):
     """Constructor signature of networks/equiunet2020.py:413-414."""
     name = "EquiUnet"
+    _cpu_hint = "; move input/model to cuda"
 
     def __init__(self, inplanes, num_classes, features, norm_layer=None, act="relu", deep_supervision=False, dropout=0,
                  refinement=False):
@@ -694,33 +536,13 @@ class EquiUnet(_PackedWeightsModule):
         self.features = list(features)
         # nn.Dropout(p) behind every ConvBnRelu's activation (networks/equiunet2020.py:62; --dropout, src/arguments_train.py:52)
         self._init_dropout(dropout)
-        # "auto" = follow torch.autocast; BRATS_PRECISION=x3 makes the split-precision parity mode the default of an unmodified
-        # training script run with --no_amp
-        self.precision = os.environ.get("BRATS_PRECISION", "auto")
-        # None | "fwd" | "all": run the 3x3x3 convolutions (forward / forward + input gradients) on the e4m3 MFMA kernel
-        # when the activations are bf16 (BASELINE.json configs[4]); the weight gradients stay bf16
-        self.conv_fp8 = None
-        self.skip_deep_heads_in_eval = False
+        self._init_switches(pack_plan="0")
+        # pack_plan is off by default here: this network's step is GPU-bound; the single launch (0.11 ms) saves 0.1 ms over the
+        # 33 per-layer ones (6.6 us each), and the convolutions lose 0.10-0.18 ms per step on weights that were packed long before
+        # their layer runs and have left L2 (same-box A/B); EquiUnetASSPEvo (host-bound eager) gains 10 %.
         # inference (no_grad, 16-bit): the activation between the two convolutions of a block is applied on load by the second
         # one and never stored (ops.Pending / brats_conv3d_fwd_pre); BRATS_NORM_ON_LOAD=0: the two-pass path, for A/B runs
         self.norm_on_load = os.environ.get("BRATS_NORM_ON_LOAD", "1") != "0"
-        self._grad_sink = None  # set by brats21_amd.ddp.GradientBuckets
-        self._grad_dest = None  # (ditto: parameter index -> its slice of an all-reduce bucket, or None)
-        # training: one multi-tensor weight-packing launch per step (ops.PackPlan).  Off by default here: this network's
-        # step is GPU-bound; the single launch (0.11 ms) saves 0.1 ms over the 33 per-layer ones (6.6 us each), and the
-        # convolutions lose 0.10-0.18 ms per step on weights that were packed long before their layer runs and have left
-        # L2 (same-box A/B); EquiUnetASSPEvo (host-bound eager) gains 10 %.
-        self.pack_plan = os.environ.get("BRATS_PACK_PLAN", "0") != "0"
-        # the output head's backward inside the GroupNorm backward of the last layer (brats_gn_act_bwd_head); 0: the two-call
-        # path (brats_head_bwd + brats_gn_act_bwd) for same-box A/B runs
-        self.fold_head_bwd = os.environ.get("BRATS_FOLD_HEAD", "1") != "0"
-        # the pooling backward + skip add inside the GroupNorm backward of the level's last layer (brats_gn_act_bwd_pool)
-        self.fold_pool_bwd = os.environ.get("BRATS_FOLD_POOL", "1") != "0"
-        # GroupNorm backward's first pass (sum u, sum u * xhat) of a block's first unit inside the input-gradient launch of its
-        # second unit (brats_conv3d_fwd_bstats + brats_gn_act_bwd_tiles): dz and y are read once instead of twice
-        self.fold_bwd_stats = os.environ.get("BRATS_FOLD_BWD_STATS", "1") != "0"
-        # ... and its forward on the last layer's raw convolution output (brats_gn_head_fwd): up1 is never stored
-        self.fold_head_fwd = os.environ.get("BRATS_FOLD_HEAD_FWD", os.environ.get("BRATS_FOLD_HEAD", "1")) != "0"
         f = self.features
         nl = norm_layer
         self.encoder1 = UBlock(inplanes, f[0], f[0], norm=nl, act=act)
@@ -748,42 +570,5 @@ class EquiUnet(_PackedWeightsModule):
                 nn.init.normal_(mod.weight.data, 1.0, 0.02)
                 nn.init.constant_(mod.bias.data, 0.0)
 
-    def _dtype(self):
-        if self.precision == "bf16":
-            return torch.bfloat16
-        if self.precision == "fp16":
-            return torch.float16
-        if self.precision in ("fp32", "x3", "fp16x3", "bf16x3", "x3fwd", "x3bwd"):
-            return torch.float32
-        if torch.is_autocast_enabled():  # the reference's switch (learning/engine.py:304): its autocast dtype is fp16
-            return torch.float16 if torch.get_autocast_dtype("cuda") == torch.float16 else torch.bfloat16
-        return torch.float32
-
-    def _x3_modes(self):
-        """(forward, backward) split of the 3x3x3 convolutions when the activations are f32 (ops.split_precision):
-        precision "x3" (= "fp16x3") = fp16 pairs (f32-class: 2^-22 per product) forward AND backward -- dY, whose values lie far
-        below fp16's range, is scaled by a power of two from the |max| its producer kernel records (brats_conv3d_x3_fwd /
-        _x3_wgrad; the reference needs a GradScaler for the same reason); "bf16x3" = bf16 pairs everywhere (2^-16 per product:
-        logits ~5e-4, gradients ~5e-3 from f64 -- measured, tests/test_x3_gpu.py); anything else = the exact-f32 MFMA kernels."""
-        if self.precision in ("x3", "fp16x3"):
-            return ops.X3F, ops.X3F
-        if self.precision == "bf16x3":
-            return ops.X3B, ops.X3B
-        if self.precision in ("x3fwd", "x3bwd"):  # (diagnostic: one pass split, the other exact f32)
-            return (ops.X3F, None) if self.precision == "x3fwd" else (None, ops.X3F)
-        return None, None
-
     def forward(self, x):
-        if not x.is_cuda:
-            raise BratsHipError("brats21_amd.EquiUnet runs on the GPU only (no CPU fallback); move input/model to cuda")
-        if x.dim() != 5 or x.shape[1] != 4 or any(s % 8 for s in x.shape[2:]):
-            raise ValueError("expected input [N, 4, D, H, W] with D, H, W divisible by 8")
-        params = tuple(self.parameters())
-        self._fwd_grad = torch.is_grad_enabled()  # (inside autograd.Function.forward grad mode is always off)
-        self._weights_may_have_changed()
-        if self.training and self.pack_plan and torch.is_grad_enabled():
-            ops.plan_for(self, x.device)  # all layers' weights (forward + dgrad layouts) packed by one launch
-        outs = _EquiUnetFn.apply(self, x.float(), self._dtype(), *params)
-        if self.deep_supervision:
-            return outs[0], list(outs[1:])
-        return outs[0]
+        return self._run(_EquiUnetFn, x)

@@ -8,15 +8,13 @@ One autograd node; explicit forward / backward programs over NDHWC activations (
 """
 import warnings
 
-import os
-
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import ops
-from .._lib import PACK_DGRAD, PACK_FWD, BratsHipError
-from .equiunet import douts_device, _AmaxSlots, _ConvParams, _PackedWeightsModule, _inherit_amax
+from .._lib import PACK_DGRAD, PACK_FWD
+from .equiunet import _ConvParams
+from ._program import _Ctx, _PackedWeightsModule, _fn_backward, _fn_forward, _heads_bwd, _inherit_amax  # noqa: F401  (_Ctx: tests)
 
 
 # ------------------------------------------------------------------------------------------ parameter holders
@@ -72,59 +70,6 @@ class SimpleASPPEVO(nn.Module):
 # ------------------------------------------------------------------------------------------ unit programs
 def _flat(p):
     return p.detach().reshape(-1).contiguous()
-
-
-class _Ctx:
-    """Per-forward state shared by the unit programs."""
-
-    def __init__(self, model, dtype):
-        self.m, self.dtype = model, dtype
-        # e4m3 convolutions (EquiUnet.conv_fp8 semantics): the EvoNorm / SE kernels record the |max| of what they write
-        # into slots taken here; a tensor without a recorded |max| falls back to ops.absmax inside ops.conv3d_f8
-        self.fp8 = getattr(model, "conv_fp8", None) if ops.is16(dtype) else None
-        # split precision on fp16 pairs (backward): dy is scaled by a power of two from its recorded |max| (EquiUnet._x3_modes)
-        self.x3s = ops.x3_mode() == ops.X3F and dtype == torch.float32
-        self.slots = None
-        self.names = {p: i for i, p in enumerate(model.parameters())}
-        self.grads = {}
-        # nn.Dropout(p) behind every EvoNorm but the ASPP's (networks/equiunet2021.py:200,203,219; :178 pins the ASPP's to 0),
-        # training mode only: (p, state) with state = (seed, step counter) on the device; None = off
-        self.drop = None
-
-    def dropped(self, t, uid, out=None):
-        """t * keep / (1 - p) with unit uid's mask of this step (forward: in place on the activation; backward: on the gradient)."""
-        if self.drop is None or uid is None:
-            return t
-        return ops.dropout(t, self.drop[0], self.drop[1], uid, out=out)
-
-    def slot(self, device, force=False):
-        if not self.fp8 and not force:
-            return None
-        if self.slots is None or self.slots.i >= self.slots.buf.numel():
-            self.slots = _AmaxSlots(64, device)
-        return self.slots.take()
-
-    def identity_ss(self, n, c, device):
-        """{scale, shift} = {1, 0} per (sample, channel): ops.conv3d_bstats' activation argument when there is no activation."""
-        key = (n, c)
-        if getattr(self, "_ss", None) is None:
-            self._ss = {}
-        if key not in self._ss:
-            ss = torch.zeros((n, c, 2), dtype=torch.float32, device=device)
-            ss[..., 0] = 1.0
-            self._ss[key] = ss
-        return self._ss[key]
-
-    def dest(self, param):
-        """The parameter's slice of a DDP all-reduce bucket (ddp.GradientBuckets.dest) for kernels that can write there."""
-        d = getattr(self.m, "_grad_dest", None)
-        return d(self.names[param]) if d is not None else None
-
-    def put(self, param, grad):
-        i = self.names[param]
-        self.grads[i] = grad.reshape(param.shape)
-        if self.m._grad_sink is not None:
-            self.m._grad_sink(i, self.grads[i])
 
 
 def _conv_any_fwd(cx, conv, x, dil, want_stats, out=None):
@@ -262,7 +207,7 @@ def _block_fwd(cx, blk, x, out=None, head=None):
     """head: the 1x1x1 output head module when the block's output feeds nothing else -- the block then returns the head's
     logits instead of its output tensor, which is recomputed on load inside the head kernel and never stored."""
     s = blk.conv_conv_se
-    uid = cx.m._unit_ids[blk] if cx.drop is not None else None
+    uid = cx.drop_of(blk)
     z1, _, r1 = _conv_evo_fwd(cx, s[0], s[1], x, uid=uid)
     if cx.drop is not None:
         # dropout between the second EvoNorm and the SE layer (networks/equiunet2021.py:201-205): the fused EvoNorm + SE forms derive
@@ -343,40 +288,23 @@ def _block_bwd(cx, rec, do, need_dx=True, head=None, pool=None):
 class _AsspFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, dtype, *params):
-        # training: the module packed all layers' weights up front (ops.plan_for); pack_weights() then returns views
-        ctx.plan = ops._PLANS.get(model) if (model.training and model.pack_plan) else None
-        ctx.x3 = model._x3_modes() if dtype == torch.float32 else (None, None)
-        with ops.use_plan(ctx.plan), ops.split_precision(ctx.x3[0]):
-            return _AsspFn._forward(ctx, model, x, dtype, *params)
+        return _fn_forward(_AsspFn._forward, ctx, model, x, dtype, params)
 
     @staticmethod
     def backward(ctx, *douts):
-        with ops.use_plan(ctx.plan), ops.split_precision(ctx.x3[1]):
-            return _AsspFn._backward(ctx, *douts)
+        return _fn_backward(_AsspFn._backward, ctx, douts)
 
     @staticmethod
-    def _forward(ctx, model, x, dtype, *params):
-        m = model
+    def _forward(ctx, cx, x0):
+        m, dtype, uid = cx.m, cx.dtype, cx.drop_of  # (uid: dropout stream of a ConvEvo unit; the ASPP's has p = 0, networks/equiunet2021.py:178)
         f = m.features
-        cx = _Ctx(m, dtype)
-        if m.training and m.dropout_p > 0.0:
-            if cx.fp8:
-                raise NotImplementedError("--dropout > 0 with the e4m3 convolution path is not implemented")
-            cx.drop = (m.dropout_p, m._advance_dropout(x.device))
-
-        def uid(mod):  # dropout stream of a ConvEvo unit (the ASPP's has p = 0: networks/equiunet2021.py:178)
-            return m._unit_ids[mod] if cx.drop is not None else None
-        n, _, d, h, w = x.shape
-        dev = x.device
+        n, d, h, w, _ = x0.shape
+        dev = x0.device
         h0, h1, h2 = f[0] // 2, f[1] // 2, f[2] // 2
-        x0 = ops.ncdhw_to_ndhwc(x, dtype, cpad=8 if (ops.is16(dtype) or ops.x3_active()) else 4)
-        if ops.x3_mode() == ops.X3F:
-            x0._x3amax = ops.absmax(x0)  # fp16 pairs: the first layer's forward scales the un-normalised input (networks/equiunet.py)
-        will_bwd = any(ctx.needs_input_grad) and model._fwd_grad  # (needs_input_grad ignores no_grad)
 
         def pool(t):  # max and average of a 2x2x2 cell never exceed the |max| of the input
             # (training: the arg-max bytes go along, the pooling backward reads them instead of the window)
-            return _inherit_amax(ops.maxpool2(t, with_avg=True, want_argmax=will_bwd), t)
+            return _inherit_amax(ops.maxpool2(t, with_avg=True, want_argmax=cx.will_bwd), t)
 
         def cat_amax(cat, a, b):  # a concat buffer written by two producers: |max| = the larger of theirs
             if cx.fp8 and hasattr(a, "_amax") and hasattr(b, "_amax"):
@@ -412,7 +340,7 @@ class _AsspFn(torch.autograd.Function):
         # decoder1's output feeds only the output head: where the kernels for it are built the head recomputes it on load
         # (ops.evonorm_head) and the backward folds the head in (ops.evonorm_se_bwd(head=...)) -- up1 is never stored
         nk = m.out_conv.weight.shape[0]
-        fuse_top = m.fold_head_fwd and cx.drop is None and nk <= 4 and (not will_bwd or (m.fold_head_bwd and nk == 3))
+        fuse_top = m.fold_head_fwd and cx.drop is None and nk <= 4 and (not cx.will_bwd or (m.fold_head_bwd and nk == 3))
         if fuse_top:
             logits, rd1 = _block_fwd(cx, m.decoder1, cat1, head=m.out_conv)
             up1 = None
@@ -422,40 +350,24 @@ class _AsspFn(torch.autograd.Function):
             outs = [ops.head(up1, m.out_conv.weight, m.out_conv.bias, 1)]
         ctx.top_fused = fuse_top
         ctx.out_shape = tuple(outs[0].shape)
-        heads = [(m.out_conv, up1, 1)]
+        ctx.heads = [(m.out_conv, up1, 1)]
         if m.deep_supervision and not (m.skip_deep_heads_in_eval and not m.training):
             for hd, src, sc in ((m.deep3[0], up3, 4), (m.deep2[0], up2, 2)):
                 outs.append(ops.head(src, hd.weight, hd.bias, sc))
-                heads.append((hd, src, sc))
-        ctx.cx, ctx.heads, ctx.nparams = cx, heads, len(params)
+                ctx.heads.append((hd, src, sc))
         ctx.recs = dict(rb1=rb1, rb2=rb2, rb3=rb3, rb4=rb4, ra=ra, rk1=rk1, rbr1=rbr1, rbr2=rbr2, rbr3=rbr3, ru3=ru3,
                         ru2=ru2, ru1=ru1, rd3=rd3, rd2=rd2, rd1=rd1)
         ctx.bufs = (down1, down2, down3, up3, up2, up1)
         return tuple(outs)
 
     @staticmethod
-    def _backward(ctx, *douts):
-        cx, R = ctx.cx, ctx.recs
-        m = cx.m
-        cx.x3s = ops.x3_mode() == ops.X3F and cx.dtype == torch.float32  # (the BACKWARD split decides about the dy scales)
+    def _backward(ctx, cx, *douts):
+        R, m = ctx.recs, cx.m
         f = m.features
         h0, h1, h2 = f[0] // 2, f[1] // 2, f[2] // 2
         down1, down2, down3, up3, up2, up1 = ctx.bufs
-        dsrc = {}
-        top = None  # the output head on up1: folded into the backward of the decoder1 block (three logit planes)
-        for (hd, src, sc), dout in zip(ctx.heads, douts):
-            if dout is None and hd is m.out_conv and ctx.top_fused:
-                # a loss built from the deep heads only: the fused top has no stored up1 to fall back on -- zero logit gradients
-                dout = torch.zeros((ctx.out_shape), dtype=torch.float32, device=douts_device(douts))
-            if dout is None:
-                continue
-            if hd is m.out_conv and (ctx.top_fused or (m.fold_head_bwd and cx.drop is None and hd.weight.shape[0] == 3)):
-                top = (hd, dout)
-                continue
-            dx, dw, db = ops.head_bwd(src, hd.weight, dout, sc)
-            cx.put(hd.weight, dw)
-            cx.put(hd.bias, db)
-            dsrc[src.data_ptr()] = dx
+        # the output head on up1: folded into the backward of the decoder1 block (three logit planes)
+        top, dsrc = _heads_bwd(ctx, cx, douts, m.fold_head_bwd and cx.drop is None and m.out_conv.weight.shape[0] == 3)
 
         def plus(a, t):
             b = dsrc.get(t.data_ptr())
@@ -481,9 +393,7 @@ class _AsspFn(torch.autograd.Function):
         d_p2 = level_bwd(R["rb3"], down3, d_p3, _conv_evo_bwd(cx, R["rbr3"], dcat3[..., :h2]))
         d_p1 = level_bwd(R["rb2"], down2, d_p2, _conv_evo_bwd(cx, R["rbr2"], dcat2[..., :h1]))
         level_bwd(R["rb1"], down1, d_p1, _conv_evo_bwd(cx, R["rbr1"], dcat1[..., :h0]), need_dx=False)
-        grads = cx.grads
-        ctx.recs = ctx.bufs = ctx.cx = None
-        return (None, None, None) + tuple(grads.get(i) for i in range(ctx.nparams))
+        ctx.recs = ctx.bufs = None
 
 
 # ------------------------------------------------------------------------------------------ module
@@ -503,24 +413,7 @@ class EquiUnetASSPEvo(_PackedWeightsModule):
         self.deep_supervision = deep_supervision
         self.act = act.upper()
         self.features = list(features)
-        # "auto" = follow torch.autocast; BRATS_PRECISION=x3 makes the split-precision parity mode the default of an unmodified
-        # training script run with --no_amp
-        self.precision = os.environ.get("BRATS_PRECISION", "auto")
-        self.conv_fp8 = None  # None | "fwd" | "all": e4m3 kernel for the 3x3x3 convolutions (see EquiUnet.conv_fp8)
-        self.pack_plan = os.environ.get("BRATS_PACK_PLAN", "1") != "0"  # training: one multi-tensor weight-packing launch per step (ops.PackPlan)
-        # the output head's backward inside the backward of the decoder1 block (brats_evonorm_se_bwd with dlogits); 0: the
-        # separate brats_head_bwd pass, for same-box A/B runs
-        self.fold_head_bwd = os.environ.get("BRATS_FOLD_HEAD", "1") != "0"
-        # the pooling backward + bridge-gradient add inside the block's EvoNorm / SE backward (brats_evonorm_se_bwd_pool)
-        self.fold_pool_bwd = os.environ.get("BRATS_FOLD_POOL", "1") != "0"
-        # EvoNorm backward's first pass of a block's first unit inside the input-gradient launch of its second convolution
-        # (ops.conv3d_bstats on the stored EvoNorm output + ops.evonorm_bwd_tiles): dz1 and y1 are read once instead of twice
-        self.fold_bwd_stats = os.environ.get("BRATS_FOLD_BWD_STATS", "1") != "0"
-        # ... and its forward on the last block's raw convolution output (brats_evonorm_head_fwd): up1 is never stored
-        self.fold_head_fwd = os.environ.get("BRATS_FOLD_HEAD_FWD", os.environ.get("BRATS_FOLD_HEAD", "1")) != "0"
-        self.skip_deep_heads_in_eval = False
-        self._grad_sink = None
-        self._grad_dest = None
+        self._init_switches(pack_plan="1")
         f = self.features
         self.encoder1 = ConvEvoBlockCorrected(inplanes, f[0])
         self.encoder2 = ConvEvoBlockCorrected(2 * f[0], f[1])
@@ -552,38 +445,5 @@ class EquiUnetASSPEvo(_PackedWeightsModule):
                 ids[mod], nxt = nxt, nxt + 1
         self._unit_ids = ids
 
-    def _dtype(self):
-        if self.precision == "bf16":
-            return torch.bfloat16
-        if self.precision == "fp16":
-            return torch.float16
-        if self.precision in ("fp32", "x3", "fp16x3", "bf16x3", "x3fwd", "x3bwd"):
-            return torch.float32
-        if torch.is_autocast_enabled():  # the reference's switch (learning/engine.py:304): its autocast dtype is fp16
-            return torch.float16 if torch.get_autocast_dtype("cuda") == torch.float16 else torch.bfloat16
-        return torch.float32
-
-    def _x3_modes(self):
-        """(forward, backward) split of the 3x3x3 convolutions when the activations are f32 (ops.split_precision):
-        see EquiUnet._x3_modes."""
-        if self.precision in ("x3", "fp16x3"):
-            return ops.X3F, ops.X3F
-        if self.precision == "bf16x3":
-            return ops.X3B, ops.X3B
-        if self.precision in ("x3fwd", "x3bwd"):  # (diagnostic: one pass split, the other exact f32)
-            return (ops.X3F, None) if self.precision == "x3fwd" else (None, ops.X3F)
-        return None, None
-
     def forward(self, x):
-        if not x.is_cuda:
-            raise BratsHipError("brats21_amd.EquiUnetASSPEvo runs on the GPU only (no CPU fallback)")
-        if x.dim() != 5 or x.shape[1] != 4 or any(s % 8 for s in x.shape[2:]):
-            raise ValueError("expected input [N, 4, D, H, W] with D, H, W divisible by 8")
-        self._fwd_grad = torch.is_grad_enabled()  # (inside autograd.Function.forward grad mode is always off)
-        self._weights_may_have_changed()
-        if self.training and self.pack_plan and torch.is_grad_enabled():
-            ops.plan_for(self, x.device)  # all layers' weights (forward + dgrad layouts) packed by one launch
-        outs = _AsspFn.apply(self, x.float(), self._dtype(), *tuple(self.parameters()))
-        if self.deep_supervision:
-            return outs[0], list(outs[1:])
-        return outs[0]
+        return self._run(_AsspFn, x)

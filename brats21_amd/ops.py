@@ -151,6 +151,11 @@ def _desc(t):
     return t.data_ptr(), c, p
 
 
+def _desc2(t):
+    """_desc of an optional second source (the virtual concat [x | x2]); (None, 0, 0) without one."""
+    return _desc(t) if t is not None else (None, 0, 0)
+
+
 def _f32(t):
     if t is None:
         return None
@@ -242,6 +247,26 @@ def _cache_put(key, w, packed):
         _PACK_KEEP.append(packed)
 
 
+def _pack_geometry(w, mode, cin_pad=None, cin_off=0, cin_cnt=None, c1=None):
+    """Of packing w [Cout, Cin, k, k, k]: (cin_w, cnt, kdim, rows, src) -- the input channels after zero-padding to cin_pad, the
+    size of the slice [cin_off, cin_off + cnt) that is packed, the GEMM's K and rows by mode, and src = (c1, c2): the channels of
+    the (possibly two-source) input the kernel will read, which decide about its K chunk."""
+    cin_w = cin_pad if cin_pad is not None else w.shape[1]
+    cnt = cin_w - cin_off if cin_cnt is None else cin_cnt
+    kdim, rows = (cnt, w.shape[0]) if mode == PACK_FWD else (w.shape[0], cnt)
+    return cin_w, cnt, kdim, rows, ((kdim, 0) if (c1 is None or mode != PACK_FWD) else (c1, kdim - c1))
+
+
+def _padded(w, cin_w):
+    """w detached, contiguous f32, its input channels zero-padded to cin_w."""
+    w = w.detach()
+    if cin_w != w.shape[1]:
+        wp = torch.zeros((w.shape[0], cin_w) + tuple(w.shape[2:]), dtype=torch.float32, device=w.device)
+        wp[:, :w.shape[1]] = w
+        w = wp
+    return w.contiguous().float()
+
+
 _PACK_JOB = np.dtype([("w", "<u8"), ("out", "<u8"), ("dtype", "<i4"), ("mode", "<i4"), ("taps", "<i4"), ("cin_w", "<i4"),
                       ("cin_real", "<i4"), ("cin_off", "<i4"), ("rows", "<i4"), ("rows16", "<i4"), ("kdim", "<i4"), ("ck", "<i4"),
                       ("ms_n", "<i4"), ("reserved", "<i4"), ("total", "<u8")])  # == brats_pack_job (include/brats_hip.h)
@@ -274,11 +299,9 @@ class PackPlan:
             w = wref()
             if w is None or w.dtype != torch.float32 or not w.is_contiguous():
                 continue
-            cout_w, cin_real, k = w.shape[0], w.shape[1], w.shape[2]
-            cin_w = cin_pad if cin_pad is not None else cin_real
-            cnt = cin_w - cin_off if cin_cnt is None else cin_cnt
-            kdim, rows = (cnt, cout_w) if mode == PACK_FWD else (cout_w, cnt)
-            ck = conv_chunk(dtype, k, dil, kdim, 0, rows) if (c1 is None or mode != PACK_FWD) else conv_chunk(dtype, k, dil, c1, kdim - c1, rows)
+            cin_real, k = w.shape[1], w.shape[2]
+            cin_w, _, kdim, rows, src = _pack_geometry(w, mode, cin_pad, cin_off, cin_cnt, c1)
+            ck = conv_chunk(dtype, k, dil, *src, rows)
             code = _code(dtype)
             nbytes = _lib.lib().brats_conv3d_packed_bytes(code, k, kdim, rows, ck)
             rows16 = (rows + 15) // 16
@@ -383,21 +406,11 @@ def pack_weights(w, dtype, mode, cin_pad=None, cin_off=0, cin_cnt=None, dil=1, c
 
 
 def _pack_weights(w, dtype, mode, cin_pad, cin_off, cin_cnt, dil, c1):
-    cout_w, cin_w, k = w.shape[0], w.shape[1], w.shape[2]
-    w = w.detach()
-    if cin_pad is not None and cin_pad != cin_w:
-        wp = torch.zeros((cout_w, cin_pad, k, k, k), dtype=torch.float32, device=w.device)
-        wp[:, :cin_w] = w
-        w, cin_w = wp, cin_pad
-    w = w.contiguous().float()
-    cin_cnt = cin_w - cin_off if cin_cnt is None else cin_cnt
+    cout_w, k = w.shape[0], w.shape[2]
+    cin_w, cin_cnt, kdim, rows, src = _pack_geometry(w, mode, cin_pad, cin_off, cin_cnt, c1)
+    w = _padded(w, cin_w)
     code = _code(dtype)
-    if mode == PACK_FWD:
-        kdim, rows = cin_cnt, cout_w
-    else:
-        kdim, rows = cout_w, cin_cnt
-    # the K chunk must be the one the kernel will pick for the (possibly two-source) input it reads
-    ck = conv_chunk(dtype, k, dil, kdim, 0, rows) if (c1 is None or mode != PACK_FWD) else conv_chunk(dtype, k, dil, c1, kdim - c1, rows)
+    ck = conv_chunk(dtype, k, dil, *src, rows)
     nbytes = _lib.lib().brats_conv3d_packed_bytes(code, k, kdim, rows, ck)
     packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
     _lib.check(_lib.lib().brats_conv3d_pack_weights(w.data_ptr(), packed.data_ptr(), code, mode, k, cout_w, cin_w,
@@ -454,6 +467,26 @@ def conv_pre_ok(dtype, ksize, dil, c1, c2, cout):
     return is16(dtype) and bool(_lib.lib().brats_conv3d_pre_ok(_code(dtype), ksize, dil, c1, c2, cout))
 
 
+def _conv_outputs(x, cout, out, split, want_stats, what):
+    """What a convolution of x writes: -> (y, stats | None, args).  y = `out` (checked), a fresh [N, D, H, W, cout] tensor, or --
+    split -- the pair of dense tensors with the output channels [0, split) and [split, cout); stats = [N, tiles, cout, 2];
+    args = (y, pitch, y2, c2, split, stats) as the entry points take them."""
+    n, d, h, w, _ = x.shape
+    y2 = None
+    if split is not None:
+        out = new_act(n, d, h, w, split, x.dtype, x.device)
+        y2 = new_act(n, d, h, w, cout - split, x.dtype, x.device)
+    elif out is None:
+        out = new_act(n, d, h, w, cout, x.dtype, x.device)
+    optr, oc, op = _desc(out)
+    if (y2 is None and oc != cout) or out.dtype != x.dtype:
+        raise _lib.BratsHipError(f"{what}: bad output tensor")
+    stats = torch.empty((n, tiles_per_sample(d, h, w), cout, 2), dtype=torch.float32, device=x.device) if want_stats else None
+    args = (optr, op, y2.data_ptr() if y2 is not None else None, (cout - split) if y2 is not None else 0, split or 0,
+            stats.data_ptr() if stats is not None else None)
+    return ((out, y2) if y2 is not None else out), stats, args
+
+
 def conv3d(x, packed_w, cout, ksize=3, dil=1, bias=None, out=None, want_stats=False, x2=None, split=None, amax=None):
     if isinstance(x, Pending) or isinstance(x2, Pending):
         return _conv3d_pre(x, packed_w, cout, ksize, dil, bias, out, want_stats, x2)
@@ -471,20 +504,12 @@ def _conv3d_pre(x, packed_w, cout, ksize, dil, bias, out, want_stats, x2):
     act, slope = (p1 or p2).act, (p1 or p2).slope
     ptr, c, p = _desc(xa)
     n, d, h, w, _ = xa.shape
-    ptr2, c2, pp2 = (None, 0, 0)
-    if xb is not None:
-        ptr2, c2, pp2 = _desc(xb)
-    if out is None:
-        out = new_act(n, d, h, w, cout, xa.dtype, xa.device)
-    optr, oc, op = _desc(out)
-    if oc != cout or out.dtype != xa.dtype:
-        raise _lib.BratsHipError("conv3d: bad output tensor")
-    stats = torch.empty((n, tiles_per_sample(d, h, w), cout, 2), dtype=torch.float32, device=xa.device) if want_stats else None
+    ptr2, c2, pp2 = _desc2(xb)
+    out, stats, (optr, op, _, _, _, sptr) = _conv_outputs(xa, cout, out, None, want_stats, "conv3d")
     with _span("conv_igemm", c + c2, cout, ksize, dil, n, d, h, w, str(xa.dtype)):
         _lib.check(_lib.lib().brats_conv3d_fwd_pre(ptr, c, p, p1.scale_shift.data_ptr() if p1 is not None else None, ptr2, c2, pp2,
                                                    p2.scale_shift.data_ptr() if p2 is not None else None, ACTS[act], float(slope),
-                                                   packed_w.data_ptr(), _f32(bias), optr, op,
-                                                   stats.data_ptr() if stats is not None else None, _code(xa.dtype), dil, n, d, h, w,
+                                                   packed_w.data_ptr(), _f32(bias), optr, op, sptr, _code(xa.dtype), dil, n, d, h, w,
                                                    cout, _stream()), "conv3d_fwd_pre")
     return out, stats
 
@@ -498,37 +523,17 @@ def _conv3d(x, packed_w, cout, ksize=3, dil=1, bias=None, out=None, want_stats=F
     matching power of two and the result scaled back (brats_conv3d_x3_fwd: the input gradient, whose x = dY is tiny)."""
     ptr, c, p = _desc(x)
     n, d, h, w, _ = x.shape
-    ptr2, c2, p2 = (None, 0, 0)
-    if x2 is not None:
-        ptr2, c2, p2 = _desc(x2)
-    y2 = None
-    if split is not None:
-        out = new_act(n, d, h, w, split, x.dtype, x.device)
-        y2 = new_act(n, d, h, w, cout - split, x.dtype, x.device)
-    elif out is None:
-        out = new_act(n, d, h, w, cout, x.dtype, x.device)
-    optr, oc, op = _desc(out)
-    if (y2 is None and oc != cout) or out.dtype != x.dtype:
-        raise _lib.BratsHipError("conv3d: bad output tensor")
-    stats = None
-    if want_stats:
-        stats = torch.empty((n, tiles_per_sample(d, h, w), cout, 2), dtype=torch.float32, device=x.device)
+    ptr2, c2, p2 = _desc2(x2)
+    y, stats, oargs = _conv_outputs(x, cout, out, split, want_stats, "conv3d")
     kd = _conv_dtype(x.dtype, ksize)  # (split precision: f32 tensors, weights packed under the same mode)
-    if amax is not None and kd in (X3F, X3B):
-        with _span("conv_igemm", c + c2, cout, ksize, dil, n, d, h, w, str(kd)):
-            _lib.check(_lib.lib().brats_conv3d_x3_fwd(ptr, c, p, ptr2, c2, p2, _f32(amax), packed_w.data_ptr(), _f32(bias), optr, op,
-                                                      y2.data_ptr() if y2 is not None else None,
-                                                      (cout - split) if y2 is not None else 0, split or 0,
-                                                      stats.data_ptr() if stats is not None else None, _code(kd), dil, n, d, h, w,
-                                                      cout, _stream()), "conv3d_x3_fwd")
-        return ((out, y2) if y2 is not None else out), stats
     with _span("conv_igemm", c + c2, cout, ksize, dil, n, d, h, w, str(kd)):
-        _lib.check(_lib.lib().brats_conv3d_fwd(ptr, c, p, ptr2, c2, p2, packed_w.data_ptr(), _f32(bias), optr, op,
-                                               y2.data_ptr() if y2 is not None else None,
-                                               (cout - split) if y2 is not None else 0, split or 0,
-                                               stats.data_ptr() if stats is not None else None, _code(kd), ksize,
-                                               dil, n, d, h, w, cout, _stream()), "conv3d_fwd")
-    return ((out, y2) if y2 is not None else out), stats
+        if amax is not None and kd in (X3F, X3B):
+            _lib.check(_lib.lib().brats_conv3d_x3_fwd(ptr, c, p, ptr2, c2, p2, _f32(amax), packed_w.data_ptr(), _f32(bias), *oargs,
+                                                      _code(kd), dil, n, d, h, w, cout, _stream()), "conv3d_x3_fwd")
+        else:
+            _lib.check(_lib.lib().brats_conv3d_fwd(ptr, c, p, ptr2, c2, p2, packed_w.data_ptr(), _f32(bias), *oargs, _code(kd),
+                                                   ksize, dil, n, d, h, w, cout, _stream()), "conv3d_fwd")
+    return y, stats
 
 
 # ------------------------------------------------------------------------------------------ fp8 conv
@@ -566,19 +571,12 @@ def pack_weights_f8(w, mode, cin_pad=None, cin_off=0, cin_cnt=None, c1=None):
         hit = _cache_get(key, w)
         if hit is not None:
             return hit
-    w0 = w
-    cout_w, cin_w, k = w.shape[0], w.shape[1], w.shape[2]
-    if k != 3:
+    w0, cout_w = w, w.shape[0]
+    if w.shape[2] != 3:
         raise _lib.BratsHipError("pack_weights_f8: 3x3x3 kernels only")
-    w = w.detach()
-    if cin_pad is not None and cin_pad != cin_w:
-        wp = torch.zeros((cout_w, cin_pad, k, k, k), dtype=torch.float32, device=w.device)
-        wp[:, :cin_w] = w
-        w, cin_w = wp, cin_pad
-    w = w.contiguous().float()
-    cin_cnt = cin_w - cin_off if cin_cnt is None else cin_cnt
-    kdim, rows = (cin_cnt, cout_w) if mode == PACK_FWD else (cout_w, cin_cnt)
-    ck = conv_f8_chunk(kdim) if (c1 is None or mode != PACK_FWD) else conv_f8_chunk(c1, kdim - c1)
+    cin_w, cin_cnt, kdim, rows, src = _pack_geometry(w, mode, cin_pad, cin_off, cin_cnt, c1)
+    w = _padded(w, cin_w)
+    ck = conv_f8_chunk(*src)
     if ck <= 0:
         raise _lib.BratsHipError(f"pack_weights_f8: K channels {kdim} (c1={c1}) are not multiples of 16")
     nbytes = _lib.lib().brats_conv3d_f8_packed_bytes(kdim, rows, ck)
@@ -599,9 +597,7 @@ def conv3d_f8(x, packed_w, cout, dil=1, bias=None, out=None, want_stats=False, x
         raise _lib.BratsHipError("conv3d_f8: bf16 activations only")
     ptr, c, p = _desc(x)
     n, d, h, w, _ = x.shape
-    ptr2, c2, p2 = (None, 0, 0)
-    if x2 is not None:
-        ptr2, c2, p2 = _desc(x2)
+    ptr2, c2, p2 = _desc2(x2)
     if xscale is None:
         if amax is None:
             amax = absmax(x)
@@ -609,26 +605,12 @@ def conv3d_f8(x, packed_w, cout, dil=1, bias=None, out=None, want_stats=False, x
             amax2 = absmax(x2)
     else:
         amax = amax2 = None
-    y2 = None
-    if split is not None:
-        out = new_act(n, d, h, w, split, x.dtype, x.device)
-        y2 = new_act(n, d, h, w, cout - split, x.dtype, x.device)
-    elif out is None:
-        out = new_act(n, d, h, w, cout, x.dtype, x.device)
-    optr, oc, op = _desc(out)
-    if (y2 is None and oc != cout) or out.dtype != x.dtype:
-        raise _lib.BratsHipError("conv3d_f8: bad output tensor")
-    stats = None
-    if want_stats:
-        stats = torch.empty((n, tiles_per_sample(d, h, w), cout, 2), dtype=torch.float32, device=x.device)
+    y, stats, oargs = _conv_outputs(x, cout, out, split, want_stats, "conv3d_f8")
     with _span("conv_igemm_f8", c + c2, cout, 3, dil, n, d, h, w, "e4m3"):
         _lib.check(_fn16("brats_conv3d_f8_fwd", x.dtype)(ptr, c, p, _f32(amax), ptr2, c2, p2, _f32(amax2),
                                                   float(xscale) if xscale is not None else 0.0, packed_w.data_ptr(),
-                                                  _f32(bias), optr, op, y2.data_ptr() if y2 is not None else None,
-                                                  (cout - split) if y2 is not None else 0, split or 0,
-                                                  stats.data_ptr() if stats is not None else None, dil, n, d, h, w, cout,
-                                                  _stream()), "conv3d_f8_fwd")
-    return ((out, y2) if y2 is not None else out), stats
+                                                  _f32(bias), *oargs, dil, n, d, h, w, cout, _stream()), "conv3d_f8_fwd")
+    return y, stats
 
 
 def _grad_out(out, shape, device):
@@ -643,9 +625,7 @@ def conv3d_wgrad(x, dy, ksize=3, dil=1, want_dbias=False, x2=None, out=None, ama
     """dW [cout, cin (+cin2), k,k,k] f32 (and dbias) from the layer input [x | x2] and the output gradient dy.
     amax_dy (split precision only): 1-element f32 device tensor holding max|dy| (see conv3d's amax)."""
     ptr, c, p = _desc(x)
-    ptr2, c2, p2 = (None, 0, 0)
-    if x2 is not None:
-        ptr2, c2, p2 = _desc(x2)
+    ptr2, c2, p2 = _desc2(x2)
     dptr, cout, dp = _desc(dy)
     n, d, h, w, _ = x.shape
     kd = _conv_dtype(x.dtype, ksize)
@@ -681,9 +661,7 @@ def conv3d_wgrad_f8(x, dy, amax, amax_dy, x2=None, amax2=None, out=None):
     (v_mfma_scale_f32_16x16x128_f8f6f4).  amax* : 1-element f32 device tensors holding max|x|, max|x2|, max|dy| (recorded
     by the kernels that produced the tensors; absmax() otherwise).  Only where conv3d_wgrad_f8_ok()."""
     ptr, c, p = _desc(x)
-    ptr2, c2, p2 = (None, 0, 0)
-    if x2 is not None:
-        ptr2, c2, p2 = _desc(x2)
+    ptr2, c2, p2 = _desc2(x2)
     dptr, cout, dp = _desc(dy)
     n, d, h, w, _ = x.shape
     if not is16(x.dtype) or dy.dtype != x.dtype:
@@ -761,15 +739,21 @@ def affine_act_pool(y, scale_shift, act="relu", slope=0.01, amax=None, slope_t=N
     return z, pooled
 
 
+def _gn_bwd_bufs(y):
+    """(dy like y, reduction workspace, dgamma [C], dbeta [C]) of the GroupNorm + activation backward entry points."""
+    n, c = y.shape[0], y.shape[-1]
+    red = torch.empty(_lib.lib().brats_gn_bwd_ws_floats(n, c), dtype=torch.float32, device=y.device)
+    dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
+    dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
+    return torch.empty(y.shape, dtype=y.dtype, device=y.device), red, dgamma, dbeta
+
+
 def gn_act_bwd(dz, y, scale_shift, mean_rstd, gamma, groups=8, act="relu", slope=0.01, amax=None, slope_t=None):
     """Returns (dy, dgamma, dbeta) for z = act(GroupNorm(y)); amax (optional, zero-initialised) receives max|dy|."""
     dzp, c, dzpitch = _desc(dz)
     yp, _, ypitch = _desc(y)
     n, d, h, w, _ = y.shape
-    dy = new_act(n, d, h, w, c, y.dtype, y.device)
-    red = torch.empty(_lib.lib().brats_gn_bwd_ws_floats(n, c), dtype=torch.float32, device=y.device)
-    dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
-    dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
+    dy, red, dgamma, dbeta = _gn_bwd_bufs(y)
     _lib.check(_lib.lib().brats_gn_act_bwd(dzp, dzpitch, yp, ypitch, scale_shift.data_ptr(), mean_rstd.data_ptr(),
                                            _f32(gamma), dy.data_ptr(), c, red.data_ptr(), dgamma.data_ptr(),
                                            dbeta.data_ptr(), _code(y.dtype), ACTS[act], slope, _f32(slope_t), n, d * h * w, c,
@@ -818,10 +802,7 @@ def gn_act_bwd_tiles(tile_stats, dz, y, scale_shift, mean_rstd, gamma, groups=8,
     dzp, c, dzpitch = _desc(dz)
     yp, _, ypitch = _desc(y)
     n, d, h, w, _ = y.shape
-    dy = new_act(n, d, h, w, c, y.dtype, y.device)
-    red = torch.empty(_lib.lib().brats_gn_bwd_ws_floats(n, c), dtype=torch.float32, device=y.device)
-    dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
-    dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
+    dy, red, dgamma, dbeta = _gn_bwd_bufs(y)
     _lib.check(_lib.lib().brats_gn_act_bwd_tiles(tile_stats.data_ptr(), tile_stats.shape[1], dzp, dzpitch, yp, ypitch,
                                                  scale_shift.data_ptr(), mean_rstd.data_ptr(), _f32(gamma), dy.data_ptr(), c,
                                                  red.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), _code(y.dtype), ACTS[act],
@@ -838,11 +819,8 @@ def gn_act_bwd_head(dlogits, head_weight, y, scale_shift, mean_rstd, gamma, grou
     dev = y.device
     hw = head_weight.detach().reshape(k, c).contiguous().float()
     dl = dlogits.contiguous().float()
-    dy = new_act(n, d, h, w, c, y.dtype, dev)
-    red = torch.empty(_lib.lib().brats_gn_bwd_ws_floats(n, c), dtype=torch.float32, device=dev)
+    dy, red, dgamma, dbeta = _gn_bwd_bufs(y)
     hws = torch.empty(_lib.lib().brats_gn_bwd_head_ws_floats(n, c, k), dtype=torch.float32, device=dev)
-    dgamma = torch.empty(c, dtype=torch.float32, device=dev)
-    dbeta = torch.empty(c, dtype=torch.float32, device=dev)
     dhw = torch.empty((k, c), dtype=torch.float32, device=dev)
     dhb = torch.empty(k, dtype=torch.float32, device=dev)
     _lib.check(_lib.lib().brats_gn_act_bwd_head(dl.data_ptr(), hw.data_ptr(), k, yp, ypitch, scale_shift.data_ptr(),
@@ -859,11 +837,7 @@ def gn_act_bwd_pool(dskip, dpool, argmax, y, scale_shift, mean_rstd, gamma, grou
     n, d, h, w, _ = y.shape
     sp, _, spitch = _desc(dskip)
     pp, _, ppitch = _desc(dpool)
-    dev = y.device
-    dy = new_act(n, d, h, w, c, y.dtype, dev)
-    red = torch.empty(_lib.lib().brats_gn_bwd_ws_floats(n, c), dtype=torch.float32, device=dev)
-    dgamma = torch.empty(c, dtype=torch.float32, device=dev)
-    dbeta = torch.empty(c, dtype=torch.float32, device=dev)
+    dy, red, dgamma, dbeta = _gn_bwd_bufs(y)
     _lib.check(_lib.lib().brats_gn_act_bwd_pool(sp, spitch, pp, ppitch, argmax.data_ptr(), yp, ypitch, scale_shift.data_ptr(),
                                                 mean_rstd.data_ptr(), _f32(gamma), dy.data_ptr(), c, red.data_ptr(),
                                                 dgamma.data_ptr(), dbeta.data_ptr(), _code(y.dtype), ACTS[act], slope, n, d, h, w, c,
@@ -1216,16 +1190,13 @@ def pack_weights_direct(w, dtype, mode, cin_off=0, cin_cnt=None):
         hit = _cache_get(key, w)
         if hit is not None:
             return hit
-    cout_w, cin_w, k = w.shape[0], w.shape[1], w.shape[2]
-    cnt = cin_w - cin_off if cin_cnt is None else cin_cnt
-    kdim, rows = (cnt, cout_w) if mode == PACK_FWD else (cout_w, cnt)
+    cout_w, k = w.shape[0], w.shape[2]
+    cin_w, cnt, kdim, rows, _ = _pack_geometry(w, mode, None, cin_off, cin_cnt)
     code = _code(dtype)
     nbytes = _lib.lib().brats_dconv_packed_bytes(code, k, kdim, rows)
     if nbytes == 0:
         raise _lib.BratsHipError(f"pack_weights_direct: K channels {kdim} must be a multiple of {16 if code in (BF16, F16) else 8}")
-    wd = w.detach()
-    if wd.dtype != torch.float32 or not wd.is_contiguous():
-        wd = wd.contiguous().float()
+    wd = _padded(w, cin_w)
     packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
     _lib.check(_lib.lib().brats_dconv_pack_weights(wd.data_ptr(), packed.data_ptr(), code, mode, k, cout_w, cin_w, cin_off, cnt,
                                                    _stream()), "dconv_pack_weights")
@@ -1267,24 +1238,18 @@ def conv3d_wgrad_shift(x, dy, ksize=1, dil=1, want_dbias=False, out=None, amax_d
     if _X3 is not None and x.dtype == torch.float32 and c % 8 == 0 and cout % 8 == 0:
         kd = _X3  # (1x1x1 too: the voxel GEMM is MFMA-bound in exact f32 -- 3.0 of EquiUnetASSPEvo-48's 44 ms x3 step)
     code = _code(kd)
-    if amax_dy is not None and kd in (X3F, X3B):
-        nbytes = _lib.lib().brats_conv3d_wgrad_shift_ws_bytes(code, ksize, n, d, h, w, c, cout)
-        ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
-        dw = _grad_out(out, (cout, c, ksize, ksize, ksize), x.device)
-        db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_dbias else None
-        with _span("conv_wgrad", c, cout, ksize, dil, n, d, h, w, str(kd)):
-            _lib.check(_lib.lib().brats_conv3d_x3_wgrad_shift(ptr, c, p, dptr, dp, _f32(amax_dy), ws.data_ptr(), dw.data_ptr(),
-                                                              db.data_ptr() if db is not None else None, code, ksize, dil, n, d, h, w,
-                                                              cout, _stream()), "conv3d_x3_wgrad_shift")
-        return dw, db
     nbytes = _lib.lib().brats_conv3d_wgrad_shift_ws_bytes(code, ksize, n, d, h, w, c, cout)
     ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
     dw = _grad_out(out, (cout, c, ksize, ksize, ksize), x.device)
     db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_dbias else None
+    dbp = db.data_ptr() if db is not None else None
     with _span("conv_wgrad", c, cout, ksize, dil, n, d, h, w, str(kd)):
-        _lib.check(_lib.lib().brats_conv3d_wgrad_shift(ptr, c, p, dptr, dp, ws.data_ptr(), dw.data_ptr(),
-                                                       db.data_ptr() if db is not None else None, code, ksize, dil, n, d, h, w,
-                                                       cout, _stream()), "conv3d_wgrad_shift")
+        if amax_dy is not None and kd in (X3F, X3B):
+            _lib.check(_lib.lib().brats_conv3d_x3_wgrad_shift(ptr, c, p, dptr, dp, _f32(amax_dy), ws.data_ptr(), dw.data_ptr(), dbp,
+                                                              code, ksize, dil, n, d, h, w, cout, _stream()), "conv3d_x3_wgrad_shift")
+        else:
+            _lib.check(_lib.lib().brats_conv3d_wgrad_shift(ptr, c, p, dptr, dp, ws.data_ptr(), dw.data_ptr(), dbp, code, ksize, dil,
+                                                           n, d, h, w, cout, _stream()), "conv3d_wgrad_shift")
     return dw, db
 
 

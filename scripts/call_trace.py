@@ -1,0 +1,105 @@
+"""Library call trace of the two network programs: for each configuration, every libbrats_hip entry-point call of two training
+steps (engine.TrainStep, deep supervision on; the second step is the one that runs on a pack plan / DDP bucket slices) and of
+two no_grad eval forwards (the second one hits the packed-weight and BCNorm fold caches), followed by a sha256 of the losses,
+every parameter gradient and the eval logits.  A call is written as its name, its arguments -- pointers as 0 (null) or 1,
+integers and floats verbatim; kinds from _lib._parse_header() -- and its return value.  Two trees compute the same thing the same
+way when their outputs are identical:
+
+    python scripts/call_trace.py OUT.txt [--tree OTHER_CHECKOUT] [--only REGEX] [--no-full]
+"""
+import argparse, contextlib, hashlib, io, re, sys, warnings
+
+ap = argparse.ArgumentParser()
+ap.add_argument("out")
+ap.add_argument("--tree", default=".", help="the checkout whose brats21_amd is traced")
+ap.add_argument("--only", default=None, help="run the configurations whose name matches")
+ap.add_argument("--no-full", action="store_true", help="skip the 128^3 case")
+args = ap.parse_args()
+sys.path.insert(0, args.tree)
+
+import torch
+from brats21_amd import _lib, get_model, synth
+from brats21_amd.ddp import GradientBuckets
+from brats21_amd.engine import TrainStep
+from brats21_amd.optim import Ranger2020
+
+LOG = []
+
+
+class _Recorder:
+    """Stands in for the loaded library (_lib._lib): every entry point is called through, and logged."""
+
+    def __init__(self, real):
+        self._real, self._sigs = real, _lib._parse_header()
+
+    def __getattr__(self, name):
+        fn, (_, spec) = getattr(self._real, name), self._sigs[name]
+
+        def call(*a):
+            ret = fn(*a)
+            shown = [("0" if v is None or v == 0 else "1") if k == "p" else repr(v) for k, v in zip(spec, a)]
+            LOG.append(f"{name}({', '.join(shown)}) -> {ret!r}")
+            return ret
+        setattr(self, name, call)
+        return call
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().float().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def run(name, model, width, size=32, precision="bf16", norm="group", act="relu", dropout=0, buckets=False, **attrs):
+    if args.only and not re.search(args.only, name):
+        return
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    ns = argparse.Namespace(model=model, width=width, norm=norm, act=act, num_classes=3, dropout=dropout)
+    with contextlib.redirect_stdout(io.StringIO()), warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        m = get_model(ns).to(dev).train()
+    m.precision = precision
+    for k, v in attrs.items():
+        assert hasattr(m, k), k
+        setattr(m, k, v)
+    opt = Ranger2020(m.parameters(), lr=1e-4, weight_decay=1e-5, use_gc=False)
+    step = TrainStep(m, opt, amp=False, buckets=GradientBuckets(m) if buckets else None)
+    x, t = synth.random_image(2, 4, (size,) * 3, seed=1, device=dev), synth.nested_spheres(2, (size,) * 3, device=dev)
+    out = [f"==== {name}"]
+    for i in (1, 2):
+        del LOG[:]
+        loss = step(x, t)
+        out += [f"-- train step {i}"] + LOG[:] + [f"loss {sha(loss)}"]
+    out += [f"grad {k} {sha(p.grad) if p.grad is not None else None}" for k, p in m.named_parameters()]
+    m.eval()
+    for i in (1, 2):
+        del LOG[:]
+        with torch.no_grad():
+            logits = m(x)
+        out += [f"-- eval forward {i}"] + LOG[:]
+        out += [f"logits {sha(o)}" for o in ([logits[0]] + list(logits[1]) if isinstance(logits, tuple) else [logits])]
+    torch.cuda.synchronize()
+    with open(args.out, "a") as f:
+        f.write("\n".join(out) + "\n")
+    print(f"{name}: {len(out)} lines", flush=True)
+
+
+_lib._lib = _Recorder(_lib.lib())
+open(args.out, "w").close()
+for net in ("equiunet", "equiunet_assp_evo"):
+    for prec in ("bf16", "fp16", "fp32", "x3", "bf16x3"):
+        run(f"{net}-16-{prec}", net, 16, precision=prec)
+    for plan in (True, False):
+        run(f"{net}-16-bf16-pack_plan={plan}", net, 16, pack_plan=plan)
+    run(f"{net}-16-bf16-dropout", net, 16, dropout=0.1)
+    for fold in ("fold_head_bwd", "fold_pool_bwd", "fold_bwd_stats", "fold_head_fwd"):
+        run(f"{net}-16-bf16-{fold}=False", net, 16, **{fold: False})
+    for fp8 in ("fwd", "all"):
+        run(f"{net}-48-bf16-fp8={fp8}", net, 48, conv_fp8=fp8)
+    run(f"{net}-48-bf16-buckets", net, 48, buckets=True)
+for norm in ("group", "instance", "batch", "bcn"):
+    for act in ("relu", "leakyrelu", "prelu"):
+        if (norm, act) != ("batch", "prelu"):  # (not implemented: EquiUnet.__init__)
+            run(f"equiunet-8-fp32-{norm}-{act}", "equiunet", 8, precision="fp32", norm=norm, act=act)
+run("equiunet-16-bf16-norm_on_load=False", "equiunet", 16, norm_on_load=False)
+if not args.no_full:  # the only shape that takes the 256 MiB affine_act_pool branch
+    run("equiunet-48-bf16-128", "equiunet", 48, size=128)
