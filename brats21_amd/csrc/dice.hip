@@ -13,7 +13,8 @@ __global__ void dice_stats_kernel(const float* __restrict__ x, const float* __re
   const float* xp = x + (size_t)nk * voxels;
   const float* tp = t + (size_t)nk * voxels;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-  const size_t v4 = voxels / 4;
+  // the 16-byte path only where every plane starts on a 16-byte boundary; else v4 = 0 and all blocks share the scalar loop
+  const size_t v4 = (voxels % 4 == 0 && (((size_t)x | (size_t)t) & 15) == 0) ? voxels / 4 : 0;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < v4; i += (size_t)gridDim.x * blockDim.x) {
     const f32x4 xv = ((const f32x4*)xp)[i], tv = ((const f32x4*)tp)[i];
 #pragma unroll
@@ -24,11 +25,9 @@ __global__ void dice_stats_kernel(const float* __restrict__ x, const float* __re
       s2 += tv[j] * tv[j];
     }
   }
-  if (blockIdx.x == 0) {
-    for (size_t i = v4 * 4 + threadIdx.x; i < voxels; i += blockDim.x) {
-      const float p = 1.f / (1.f + __expf(-xp[i]));
-      s0 += tp[i] * p; s1 += p * p; s2 += tp[i] * tp[i];
-    }
+  for (size_t i = v4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < voxels; i += (size_t)gridDim.x * blockDim.x) {
+    const float p = 1.f / (1.f + __expf(-xp[i]));
+    s0 += tp[i] * p; s1 += p * p; s2 += tp[i] * tp[i];
   }
   __shared__ float r[3][256];
   r[0][threadIdx.x] = s0; r[1][threadIdx.x] = s1; r[2][threadIdx.x] = s2;
@@ -92,7 +91,7 @@ __global__ void dice_grad_kernel(const float* __restrict__ x, const float* __res
   const float* xp = x + (size_t)nk * voxels;
   const float* tp = t + (size_t)nk * voxels;
   float* dp = dx + (size_t)nk * voxels;
-  const size_t v4 = voxels / 4;
+  const size_t v4 = (voxels % 4 == 0 && (((size_t)x | (size_t)t | (size_t)dx) & 15) == 0) ? voxels / 4 : 0;  // (as in dice_stats_kernel)
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < v4; i += (size_t)gridDim.x * blockDim.x) {
     const f32x4 xv = ((const f32x4*)xp)[i], tv = ((const f32x4*)tp)[i];
     f32x4 o;
@@ -103,11 +102,9 @@ __global__ void dice_grad_kernel(const float* __restrict__ x, const float* __res
     }
     ((f32x4*)dp)[i] = o;
   }
-  if (blockIdx.x == 0) {
-    for (size_t i = v4 * 4 + threadIdx.x; i < voxels; i += blockDim.x) {
-      const float p = 1.f / (1.f + __expf(-xp[i]));
-      dp[i] = (a * tp[i] + b2 * p) * p * (1.f - p);
-    }
+  for (size_t i = v4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < voxels; i += (size_t)gridDim.x * blockDim.x) {
+    const float p = 1.f / (1.f + __expf(-xp[i]));
+    dp[i] = (a * tp[i] + b2 * p) * p * (1.f - p);
   }
 }
 

@@ -115,8 +115,23 @@ __global__ void __launch_bounds__(256) head_conv_mfma_kernel(const bf16_t* __res
     }
     return __builtin_bit_cast(bf16x8, u);
   };
-  // the f32 weights enter as three bf16 terms (w = hi + mid + lo exactly: 3 x 8 mantissa bits), so the products are
-  // those of the f32 weights with the bf16 activations, as in the reference's arithmetic; six MFMAs per 16 voxels
+  // the f32 weights enter as three 16-bit terms, so the products are those of the f32 weights with the 16-bit activations,
+  // as in the reference's arithmetic; six MFMAs per 16 voxels.  bf16: w = hi + mid + lo exactly (3 x 8 mantissa bits, f32's
+  // exponent range).  fp16: 3 x 11 bits cover the mantissa too, but an unscaled mid / lo term falls below half's smallest
+  // normal number 2^-14 (and below its last subnormal bit 2^-24: residuals of 2^-25 per weight whatever its size), so the
+  // weights are multiplied by one power of two per launch that puts max|w| into [2^14, 2^15) -- every weight above
+  // 2^-6 max|w| then has three normal terms, one above 2^-15 max|w| is still split exactly -- and the accumulator by its inverse
+  // (both exact)
+#ifdef BRATS_FP16
+  float wmax = 0.f;  // the lanes v < K of one wave hold all K x C weights between them
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int c = 32 * (j >> 3) + 8 * q + (j & 7);
+    wmax = fmaxf(wmax, fabsf((v < K && c < C) ? w[v * C + c] : 0.f));
+  }
+  for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o, 64));
+  const float wscale = x3_scale_from_amax(wmax), winv = x3_inv_scale(wscale);
+#endif
   bf16x8 wa[3][2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -126,6 +141,9 @@ __global__ void __launch_bounds__(256) head_conv_mfma_kernel(const bf16_t* __res
     for (int j = 0; j < 8; ++j) {
       const int c = 32 * s + 8 * q + j;
       float rest = (v < K && c < C) ? w[v * C + c] : 0.f;
+#ifdef BRATS_FP16
+      rest *= wscale;
+#endif
 #pragma unroll
       for (int part = 0; part < 3; ++part) {
         const bf16_t hb = f2bf(rest);
@@ -173,7 +191,11 @@ __global__ void __launch_bounds__(256) head_conv_mfma_kernel(const bf16_t* __res
       if (q == 0 && vv < voxels) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
+#ifdef BRATS_FP16
+          if (r < K) lowp[(size_t)r * voxels + vv] = acc[r] * winv + bias[r];
+#else
           if (r < K) lowp[(size_t)r * voxels + vv] = acc[r] + bias[r];
+#endif
       }
     }
   }
