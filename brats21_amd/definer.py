@@ -1,7 +1,8 @@
 """The reference's ``--model`` factory for the accelerated models (src/definer.py:37-174):
 ``get_model(args) -> torch.nn.Module`` with the same Namespace fields (model, width, norm, act,
 num_classes, dropout) and the same error behaviour (NameError for an unknown model), and its ``--criterion`` factory
-(src/definer.py:177-288): ``make_criterion(args)`` with the Namespace fields criterion and num_classes."""
+(src/definer.py:177-288): ``make_criterion(args)`` with the Namespace fields criterion and num_classes, and its ``--optimizer``
+factory (src/definer.py:291-380): ``make_optimizer(args, model)``."""
 import argparse
 
 import torch
@@ -82,3 +83,44 @@ def make_criterion(args: argparse.Namespace) -> torch.nn.Module:
         raise NameError("Not Supported Criterion")
     kwargs["reduction"] = "mean"
     return criterion_function(**kwargs)
+
+
+def make_optimizer(args: argparse.Namespace, model: torch.nn.Module) -> torch.optim.Optimizer:
+    """src/definer.py:291-380 with the reference's own keyword sets: ranger -> optim.Ranger2020 (two launches per step), sgd /
+    adam / adamw -> torch's.  The reference wraps the result for --adaptive_gradient_clipping itself (src/main_train.py:89-90):
+    ``optim.AGC(model.parameters(), optimizer)``."""
+    trainable = filter(lambda x: x.requires_grad, model.parameters())
+    if args.optimizer == "sgd":
+        optimizer_function = torch.optim.SGD
+        kwargs = {"momentum": 0.9}
+    elif args.optimizer in ("adam", "adamw"):
+        optimizer_function = torch.optim.Adam if args.optimizer == "adam" else torch.optim.AdamW
+        kwargs = {
+            "betas": (0.9, 0.999),
+            "eps": 1e-08,
+        }
+    elif args.optimizer == "ranger":
+        from .optim import Ranger2020
+
+        optimizer_function = Ranger2020
+        kwargs = {
+            "alpha": 0.5,
+            "k": 6,
+            "N_sma_threshhold": 5,
+            "betas": (.95, 0.999),
+            "eps": 1e-5,
+            "weight_decay": 0,
+            "use_gc": args.use_gc,
+            "use_gcnorm": args.use_gcnorm,
+            "normloss": args.normloss,
+            "normloss_factor": args.normloss_factor,
+            "gc_conv_only": args.gc_conv_only,
+            "gc_loc": True,
+        }
+    elif args.optimizer in ("ranger21", "novograd"):
+        raise NotImplementedError(f"--optimizer {args.optimizer} is a third-party package's optimizer and is not built here")
+    else:
+        raise NameError("Not Supported Optimizer")
+    kwargs["lr"] = args.learning_rate
+    kwargs["weight_decay"] = args.weight_decay
+    return optimizer_function(trainable, **kwargs)

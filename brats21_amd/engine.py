@@ -6,12 +6,15 @@ import torch
 
 from . import ops
 from .evaluate import Evaluator  # noqa: F401  (re-export: the evaluate-step driver)
+from .optim import clip_grad_norm_
 from .losses import DiceLoss, deep_supervision_loss, deep_supervision_prepared_loss, fused_deep_supervision_dice
 
 
 class TrainStep:
     """One training iteration: zero_grad -> autocast forward -> deep-supervision Dice -> backward ->
-    [bucketed gradient all-reduce] -> [clip] -> optimizer step.
+    [bucketed gradient all-reduce] -> [global-norm clip] -> optimizer step.  ``max_grad_norm`` is the reference's
+    --gradient_clipping (optim.clip_grad_norm_: three launches, device only); its --adaptive_gradient_clipping is the optimizer
+    passed in: ``optim.AGC(model.parameters(), optimizer)`` clips per unit at the head of its step(), after the global clip.
 
     amp=True is the reference's default (``--no_amp`` off).  ``amp_dtype``:
       * torch.bfloat16 (default): bf16 MFMA kernels under autocast; bf16 needs no GradScaler;
@@ -60,7 +63,7 @@ class TrainStep:
                 self.buckets.finish()
             if self.max_grad_norm is not None:  # Engine._unscale_and_clip (learning/engine.py:442-452)
                 self.scaler.unscale_(self.optimizer)
-                torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm)
+                clip_grad_norm_(self._params, self.max_grad_norm)
             self.scaler.step(self.optimizer)
             self.scaler.update()
             return loss
@@ -68,7 +71,7 @@ class TrainStep:
         if self.buckets is not None:
             self.buckets.finish()
         if self.max_grad_norm is not None:  # Engine._unscale_and_clip (learning/engine.py:442-452)
-            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm)
+            clip_grad_norm_(self._params, self.max_grad_norm)
         self.optimizer.step()
         return loss
 
@@ -102,12 +105,12 @@ class GraphedTrainStep:
             # decision into the graph.  With an optimizer that takes the scale and the flag as device tensors
             # (_step_supports_amp_scaling: brats21_amd.optim.Ranger2020(capturable=True), torch's fused Adam) nothing of the loop
             # touches the host -- scale(), the inf check, the skipped-or-not step and update() are all kernels -- and it captures.
-            if not (getattr(step.optimizer, "_step_supports_amp_scaling", False) and getattr(step.optimizer, "capturable", False)) \
-                    or step.max_grad_norm is not None:
+            # Gradient clipping (max_grad_norm) captures as well: scaler.unscale_() and optim.clip_grad_norm_ are kernels only.
+            if not (getattr(step.optimizer, "_step_supports_amp_scaling", False) and getattr(step.optimizer, "capturable", False)):
                 raise NotImplementedError("GraphedTrainStep: a TrainStep with a GradScaler (amp_dtype=torch.float16) captures only with "
                                           "an optimizer that implements the GradScaler protocol on the device "
-                                          "(brats21_amd.optim.Ranger2020(capturable=True)) and without gradient clipping; otherwise use "
-                                          "the eager TrainStep for fp16, or bf16 / model.precision='x3' for graph replay")
+                                          "(brats21_amd.optim.Ranger2020(capturable=True), alone or inside brats21_amd.optim.AGC); "
+                                          "otherwise use the eager TrainStep for fp16, or bf16 / model.precision='x3' for graph replay")
         if step.buckets is not None:
             import os
             import torch.distributed as dist

@@ -4,9 +4,14 @@ two HIP launches over all parameters (csrc/ranger.hip) instead of the reference'
 
 ``state_dict()`` / ``load_state_dict()`` are the reference's: per parameter ``step``, ``exp_avg``,
 ``exp_avg_sq``, ``slow_buffer`` -- so Engine.resume (learning/engine.py:511-525) restores either way.
+
+``clip_grad_norm_`` (torch.nn.utils.clip_grad_norm_, the reference's --gradient_clipping) and ``AGC`` (the reference's
+learning/lr_scheduler.py:133-241, its --adaptive_gradient_clipping) run on the same kind of device table in at most three
+launches over all gradients (csrc/gradclip.hip), without a host round trip, so both capture into the step's hipGraph.
 """
 import math
 import os
+from collections.abc import Iterable
 
 import numpy as np
 import torch
@@ -17,6 +22,45 @@ from . import _lib
 _REC = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("slow", "<u8"),
                  ("numel", "<i8"), ("rowlen", "<i4"), ("row_base", "<i4"), ("neg_step", "<f4"), ("wd", "<f4"),
                  ("flags", "<i4"), ("chunk_base", "<i4")])  # == brats_ranger_tensor (include/brats_hip.h)
+
+
+_CLIP_REC = np.dtype([("param", "<u8"), ("grad", "<u8"), ("numel", "<i8"), ("unit_len", "<i4"), ("unit_stride", "<i4"),
+                      ("unit_base", "<i4"), ("nunits", "<i4")])  # == brats_gradclip_tensor (include/brats_hip.h)
+
+
+class _DeviceTable:
+    """Per-tensor records on the host (a numpy record array, rewritten per step: gradient pointers, step scalars) and their
+    copy on the device.  The copy is asynchronous from a ring of pinned staging buffers -- a slot is reused only after its
+    copy ran -- and, while a stream is capturing, from one fixed pinned buffer: the graph's memcpy node re-reads that buffer
+    at every replay, so nobody may rewrite it afterwards (it is allocated here because pinning memory is not allowed during
+    a capture)."""
+
+    def __init__(self, rec, dev):
+        self.rec = rec
+        self.pinned = [torch.empty(rec.nbytes, dtype=torch.uint8).pin_memory() for _ in range(4)]
+        self.pinned_capture = torch.empty(rec.nbytes, dtype=torch.uint8).pin_memory()
+        self.events = [None] * 4
+        self.dev = torch.empty(rec.nbytes, dtype=torch.uint8, device=dev)
+        self.slot = 0
+
+    def upload(self, capturing):
+        """Copy the host records to the device table on the current stream; returns the device table."""
+        if capturing:
+            pinned = self.pinned_capture
+            pinned.numpy()[:] = self.rec.view(np.uint8)
+            self.dev.copy_(pinned, non_blocking=True)
+        else:
+            slot = self.slot
+            self.slot = (slot + 1) % 4
+            if self.events[slot] is not None:
+                self.events[slot].synchronize()
+            pinned = self.pinned[slot]
+            pinned.numpy()[:] = self.rec.view(np.uint8)
+            self.dev.copy_(pinned, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self.events[slot] = ev
+        return self.dev
 
 
 def radam_step_size(step, beta1, beta2, n_sma_threshold):
@@ -171,12 +215,7 @@ class Ranger2020(Optimizer):
             plan["rec"] = rec
             plan["states"] = [self.state[p] for p in active]
             plan["ptrs"] = [(int(r["param"]), int(r["exp_avg"]), int(r["exp_avg_sq"]), int(r["slow"])) for r in rec]
-            # pinned staging ring: the H2D copy of the table is asynchronous, a slot is reused only after its copy ran
-            plan["pinned"] = [torch.empty(rec.nbytes, dtype=torch.uint8).pin_memory() for _ in range(4)]
-            plan["pinned_capture"] = torch.empty(rec.nbytes, dtype=torch.uint8).pin_memory()  # see step(): capture mode
-            plan["events"] = [None] * 4
-            plan["dev_table"] = torch.empty(rec.nbytes, dtype=torch.uint8, device=dev)
-            plan["slot"] = 0
+            plan["table"] = _DeviceTable(rec, dev)
         return rec
 
     @torch.no_grad()
@@ -248,24 +287,7 @@ class Ranger2020(Optimizer):
                                                         found_inf.data_ptr() if found_inf is not None else None, stream), "ranger_advance")
             elif capturing:
                 raise _lib.BratsHipError("Ranger2020.step() inside a hipGraph capture needs capturable=True")
-            table = plan["dev_table"]
-            if capturing:
-                # the memcpy node re-reads this buffer at every replay: a buffer nobody rewrites afterwards (allocated with
-                # the plan -- pinning memory is not allowed while a stream is capturing)
-                pinned = plan["pinned_capture"]
-                pinned.numpy()[:] = rec.view(np.uint8)
-                table.copy_(pinned, non_blocking=True)
-            else:
-                slot = plan["slot"]
-                plan["slot"] = (slot + 1) % 4
-                if plan["events"][slot] is not None:
-                    plan["events"][slot].synchronize()
-                pinned = plan["pinned"][slot]
-                pinned.numpy()[:] = rec.view(np.uint8)
-                table.copy_(pinned, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                plan["events"][slot] = ev
+            table = plan["table"].upload(capturing)
             _lib.check(lib.brats_ranger_step_amp(
                 table.data_ptr(), len(active), plan["chunks"].data_ptr(), plan["chunks"].shape[0],
                 plan["rows"].data_ptr() if plan["rows"] is not None else None, plan["nrows"], plan["means"].data_ptr(),
@@ -276,3 +298,244 @@ class Ranger2020(Optimizer):
             for p in active:  # the kernel wrote through raw pointers: tell autograd / the packed-weight cache
                 torch.autograd.graph.increment_version(p)
         return None
+
+
+# ---------------------------------------------------------------------------------------------- gradient clipping
+def unit_layout(shape, agc=True):
+    """(nunits, unit_len, unit_stride) of the reference's ``unitwise_norm`` (learning/lr_scheduler.py:114-130): the whole tensor
+    for ndim <= 1, one unit per trailing index (norm over dim 0: strided columns) for ndim 2 / 3, one unit per slice along dim 0
+    for ndim 4 / 5.  Other ranks: ValueError as in the reference; for global-norm clipping alone (agc=False), where the units
+    are only a decomposition of the sum, they are cut along dim 0 as well."""
+    numel = 1
+    for d in shape:
+        numel *= int(d)
+    if len(shape) <= 1:
+        return 1, numel, 1
+    rows = int(shape[0])
+    if len(shape) in (2, 3):
+        return numel // rows, rows, numel // rows
+    if len(shape) in (4, 5) or not agc:
+        return rows, numel // rows, 1
+    raise ValueError('Wrong input dimensions')
+
+
+class _ClipPlan:
+    """Static tables of one set of tensors (units, chunks, the stats workspace) + the per-step record table."""
+
+    def __init__(self, params, dev, agc):
+        lib = _lib.lib()
+        chunk = lib.brats_gradclip_chunk()
+        self.params = params  # (kept alive: the cache key is their ids)
+        self.shapes = [p.shape for p in params]
+        rec = np.zeros(len(params), _CLIP_REC)
+        units, chunks, nunits = [], [], 0
+        for t, p in enumerate(params):
+            n = p.numel()
+            if n >= 2 ** 31:
+                raise _lib.BratsHipError("gradient clipping: a tensor has 2^31 or more elements")
+            nu, ulen, ustride = unit_layout(p.shape, agc)
+            rec[t] = (0, 0, n, ulen, ustride, nunits, nu)
+            units.append(np.stack([np.full(nu, t, np.int32), np.arange(nu, dtype=np.int32)], 1))
+            nch = (n + chunk - 1) // chunk
+            chunks.append(np.stack([np.full(nch, t, np.int32), np.arange(nch, dtype=np.int32)], 1))
+            nunits += nu
+        self.units = torch.from_numpy(np.concatenate(units)).to(dev)
+        self.chunks = torch.from_numpy(np.concatenate(chunks)).to(dev)
+        self.stats = torch.zeros((nunits, 2), dtype=torch.float32, device=dev)
+        self.table = _DeviceTable(rec, dev)
+
+    def run(self, what, max_norm, clipping, eps, grad_scale, found_inf):
+        """One brats_gradclip call on the current gradients.  max_norm None: no global norm; clipping None: no AGC.  Returns
+        the {total_norm, clip_coef} device pair, or None."""
+        rec, dev = self.table.rec, self.stats.device
+        pptr, gptr = rec["param"], rec["grad"]
+        for t, p in enumerate(self.params):
+            g = p.grad
+            if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev or g.shape != p.shape:
+                raise _lib.BratsHipError(f"{what}: gradients must be contiguous f32 tensors on the parameters' GPU (the pass works "
+                                         "in place: it cannot run on a converted copy)")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.BratsHipError(f"{what}: parameters must be contiguous f32 tensors")
+            pptr[t], gptr[t] = p.data_ptr(), g.data_ptr()
+        for t_ in (grad_scale, found_inf):
+            if t_ is not None and (t_.dtype != torch.float32 or t_.numel() != 1 or t_.device != dev):
+                raise _lib.BratsHipError(f"{what}: grad_scale / found_inf must be one-element f32 device tensors (torch.amp.GradScaler's)")
+        table = self.table.upload(torch.cuda.is_current_stream_capturing())
+        # (a fresh pair per call: the returned total norm is not overwritten by the next call; no launch, under capture it
+        # comes from the graph's pool)
+        pair = torch.empty(2, dtype=torch.float32, device=dev) if max_norm is not None else None
+        _lib.check(_lib.lib().brats_gradclip(
+            table.data_ptr(), len(self.params), self.units.data_ptr(), self.units.shape[0], self.chunks.data_ptr(),
+            self.chunks.shape[0], self.stats.data_ptr(), pair.data_ptr() if pair is not None else None,
+            float(max_norm) if max_norm is not None else -1.0, float(clipping) if clipping is not None else -1.0, float(eps),
+            grad_scale.data_ptr() if grad_scale is not None else None, found_inf.data_ptr() if found_inf is not None else None,
+            torch.cuda.current_stream().cuda_stream), what)
+        return pair
+
+
+_CLIP_PLANS = {}  # clip_grad_norm_'s plans, newest last (AGC keeps its own)
+
+
+def _clip(plans, what, params, max_norm, clipping, eps, grad_scale, found_inf, limit=8):
+    active = [p for p in params if p.grad is not None and p.numel() > 0]
+    if not active:
+        return None
+    dev = active[0].device
+    if dev.type != "cuda" or any(p.device != dev for p in active):
+        raise _lib.BratsHipError(f"brats21_amd.optim.{what} runs on one GPU only (no CPU fallback)")
+    key = (clipping is not None,) + tuple(id(p) for p in active)
+    plan = plans.get(key)
+    if plan is None or any(a.shape != b for a, b in zip(active, plan.shapes)):
+        plan = plans[key] = _ClipPlan(active, dev, clipping is not None)
+        while len(plans) > limit:
+            del plans[next(iter(plans))]
+    return plan.run(what, max_norm, clipping, eps, grad_scale, found_inf)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None, *, grad_scale=None,
+                    found_inf=None):
+    """torch.nn.utils.clip_grad_norm_ in three launches over all gradients (csrc/gradclip.hip): the 2-norm over every gradient,
+    ``clip_coef = min(1, max_norm / (total_norm + 1e-6))``, gradients scaled in place.  Returns the total norm as a 0-dim f32
+    device tensor; nothing touches the host.  ``foreach`` is accepted and ignored.
+
+    grad_scale / found_inf (extension, the GradScaler pair of Ranger2020): one-element f32 device tensors.  With grad_scale the
+    gradients still carry that loss scale: the norm is the unscaled gradients', the gradients stay scaled.  With found_inf
+    non-zero nothing is written (the returned norm is then undefined)."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    if float(norm_type) != 2.0:
+        raise NotImplementedError("brats21_amd.optim.clip_grad_norm_ implements norm_type=2 (the reference's)")
+    if error_if_nonfinite:
+        raise NotImplementedError("brats21_amd.optim.clip_grad_norm_: error_if_nonfinite=True would read the norm on the host")
+    max_norm = float(max_norm)
+    if max_norm < 0:
+        raise ValueError(f"Invalid max_norm: {max_norm}")
+    parameters = list(parameters)
+    pair = _clip(_CLIP_PLANS, "clip_grad_norm_", parameters, max_norm, None, 0.0, grad_scale, found_inf)
+    if pair is None:  # no gradients at all: torch returns 0.
+        return torch.zeros((), dtype=torch.float32, device=parameters[0].device if parameters else None)
+    return pair[0]
+
+
+@torch.no_grad()
+def clip_grad_norm_agc_(parameters, max_norm, clipping=1e-2, eps=1e-3, *, grad_scale=None, found_inf=None):
+    """``clip_grad_norm_(parameters, max_norm)`` followed by the clipping pass of ``AGC(parameters, ..., clipping, eps)`` -- the
+    reference's order -- as ONE call of three launches: the per-unit sums are taken once and AGC's unit norms are those of the
+    globally clipped gradient, ``clip_coef * ||g_unit||``.  Returns the total norm (before clipping) like clip_grad_norm_."""
+    max_norm = float(max_norm)
+    if max_norm < 0 or clipping < 0 or eps < 0:
+        raise ValueError(f"Invalid max_norm / clipping / eps: {max_norm}, {clipping}, {eps}")
+    parameters = [parameters] if isinstance(parameters, torch.Tensor) else list(parameters)
+    pair = _clip(_CLIP_PLANS, "clip_grad_norm_agc_", parameters, max_norm, clipping, eps, grad_scale, found_inf)
+    if pair is None:
+        return torch.zeros((), dtype=torch.float32, device=parameters[0].device if parameters else None)
+    return pair[0]
+
+
+class AGC(Optimizer):
+    """Adaptive gradient clipping around any optimizer: the reference's ``AGC`` (learning/lr_scheduler.py:133-241) with its
+    constructor, its errors and its shared ``param_groups`` / ``state``; ``step()`` clips every unit of every gradient (a unit is
+    what ``unitwise_norm`` takes a norm over) to ``clipping * max(||p_unit||, eps)`` in two launches over all tensors instead of a
+    dozen torch ops and two host-to-device uploads per tensor, then steps the wrapped optimizer.
+
+    Two departures from the reference:
+      1. ``params`` is materialised with ``list()``.  The reference keeps what it is given, and its only call site passes
+         ``model.parameters()``, a generator: its first ``step()`` exhausts it and from the second step on nothing is clipped.
+         This class clips at every step.
+      2. With ``model=``, every parameter is taken once.  The reference collects ``module.parameters()`` of every module that is
+         not named in ``ignore_agc`` -- the root module included, so a parameter appears once per enclosing module and is clipped
+         that many times (the repeats change nothing but rounding), and the ignored modules' parameters come in through their
+         parents all the same.  The set of parameters is the reference's.
+
+    torch.amp.GradScaler: the wrapper declares ``_step_supports_amp_scaling`` (and ``capturable``) exactly when the wrapped
+    optimizer does; the loss scale and the overflow flag that GradScaler.step() then leaves on the wrapper are used by the AGC
+    kernels (norms of the unscaled gradient; no-op on overflow) and handed to the wrapped optimizer while it steps."""
+
+    def __init__(self, params, optim, clipping=1e-2, eps=1e-3, model=None, ignore_agc=("fc",)):
+        if clipping < 0.0:
+            raise ValueError("Invalid clipping value: {}".format(clipping))
+        if eps < 0.0:
+            raise ValueError("Invalid eps value: {}".format(eps))
+        self.optim = optim
+        if not isinstance(ignore_agc, Iterable):
+            ignore_agc = [ignore_agc]
+        if model is not None:
+            assert ignore_agc not in [None, []], "You must specify ignore_agc for AGC to ignore fc-like(or other) layers"
+            names = [name for name, module in model.named_modules()]
+            for module_name in ignore_agc:
+                if module_name not in names:
+                    raise ModuleNotFoundError("Module name {} not found in the model".format(module_name))
+            seen, plist = set(), []
+            for name, module in model.named_modules():
+                if name not in ignore_agc:
+                    for p in module.parameters():
+                        if id(p) not in seen:
+                            seen.add(id(p))
+                            plist.append(p)
+        else:
+            plist = []
+            for p in params:  # tensors, or the parameter-group dicts torch's optimizers accept
+                plist.extend(p["params"] if isinstance(p, dict) else [p])
+        for p in plist:
+            unit_layout(p.shape)  # (a rank unitwise_norm does not know raises here, not at the first step)
+        self.agc_params = [{"params": plist}]
+        self.eps = eps
+        self.clipping = clipping
+        self._clip_plans = {}
+
+    # the wrapped optimizer's, not copies: load_state_dict() replaces both objects
+    @property
+    def param_groups(self):
+        return self.optim.param_groups
+
+    @property
+    def state(self):
+        return self.optim.state
+
+    @property
+    def defaults(self):
+        return {"clipping": self.clipping, "eps": self.eps, **self.optim.defaults}
+
+    @property
+    def _step_supports_amp_scaling(self):
+        return getattr(self.optim, "_step_supports_amp_scaling", False)
+
+    @property
+    def capturable(self):
+        return getattr(self.optim, "capturable", False) or all(g.get("capturable", False) for g in self.optim.param_groups)
+
+    def __getattr__(self, name):
+        if name in ("sync_lr", "sync_steps"):  # engine.GraphedTrainStep refreshes the device-side learning rate through these
+            return getattr(self.__dict__["optim"], name)
+        raise AttributeError(f"'{type(self).__name__}' object has no attribute '{name}'")
+
+    @torch.no_grad()
+    def clip_(self, grad_scale=None, found_inf=None):
+        """The clipping pass alone (two launches), in place on the gradients; step() runs it before the wrapped step."""
+        _clip(self._clip_plans, "AGC", self.agc_params[0]["params"], None, self.clipping, self.eps, grad_scale, found_inf, limit=2)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            with torch.enable_grad():
+                closure()
+        # what GradScaler.step() put on this object (instance attributes, removed by it afterwards)
+        grad_scale, found_inf = self.__dict__.get("grad_scale"), self.__dict__.get("found_inf")
+        self.clip_(grad_scale, found_inf)
+        if grad_scale is None and found_inf is None:
+            return self.optim.step(closure)
+        self.optim.grad_scale, self.optim.found_inf = grad_scale, found_inf
+        try:
+            return self.optim.step(closure)
+        finally:
+            del self.optim.grad_scale, self.optim.found_inf
+
+    def zero_grad(self, set_to_none=False):
+        return self.optim.zero_grad(set_to_none=set_to_none)
+
+    def state_dict(self):
+        return self.optim.state_dict()
+
+    def load_state_dict(self, state_dict):
+        return self.optim.load_state_dict(state_dict)

@@ -53,8 +53,8 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * brats_dropout, brats_evonorm_bwd_tiles + its workspace query); 6 in round 6 (additions only: brats_conv3d_set_kp); 7: additions
  * only (brats_cc_filter, brats_rare_fill + their workspace queries).  Still 7 after further additions only (brats_hausdorff +
  * its workspace query; brats_edt + its workspace query, brats_sigmoid_argmax_onehot, brats_hd_loss_stats / _grad,
- * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats): an older library lacks them and says so when they are called
- * (brats21_amd/_lib.py), and tests/test_postproc_cpu.py pins the 7. */
+ * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk): an older library lacks
+ * them and says so when they are called (brats21_amd/_lib.py), and tests/test_postproc_cpu.py pins the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
 const char* brats_last_error(void);
@@ -668,6 +668,37 @@ int brats_ranger_step_amp(const brats_ranger_tensor* table, int ntensors, const 
                           const brats_ranger_dyn* dyn, float beta1, float beta2, float one_minus_beta1,
                           float one_minus_beta2, float eps, float alpha, const float* grad_scale,
                           const float* found_inf, brats_stream_t s);
+
+/* ---- multi-tensor gradient clipping: torch.nn.utils.clip_grad_norm_ (the reference's --gradient_clipping, learning/engine.py:
+ * 442-452) and adaptive gradient clipping (its --adaptive_gradient_clipping: AGC / unitwise_norm, learning/lr_scheduler.py:
+ * 114-215) in at most three launches over all tensors, no host synchronisation, capturable.  All tensors f32, contiguous,
+ * fewer than 2^31 elements each; the gradient is changed in place: g <- g * clip_coef * f_unit.
+ * One record per tensor (device array `table`).  A unit is what unitwise_norm takes one norm over: nunits units of unit_len
+ * elements; unit_stride == 1: unit u is the contiguous run starting at u * unit_len (a slice along dim 0 of a 4-D / 5-D tensor, or
+ * a whole 0-D / 1-D tensor); unit_stride > 1: element j of unit u lies at u + j * unit_stride (the columns of a 2-D / 3-D tensor:
+ * unit_len = shape[0], unit_stride = nunits = numel / shape[0]).  unit_base = index of the tensor's first unit in `stats`.
+ * units: device int32 [nunits][2] = (tensor index, unit within the tensor), tensor-major; chunks: device int32 [nchunks][2] =
+ * (tensor index, chunk index), chunk = brats_gradclip_chunk() elements; stats: f32 [nunits][2] workspace = (sum p^2, sum g^2) per
+ * unit (sum p^2 only with AGC).
+ * pair: device f32 {total_norm, clip_coef}, written when not NULL: total_norm = sqrt(sum g^2 over all units, f64) / grad_scale,
+ *   clip_coef = max_norm >= 0 ? min(1, max_norm / (total_norm + 1e-6)) : 1.  NULL: no global norm, clip_coef = 1.
+ * agc_clipping >= 0 turns AGC on: with gn = clip_coef * sqrt(sum g^2) / grad_scale and mx = max(sqrt(sum p^2), agc_eps) *
+ *   agc_clipping, f_unit = gn > mx ? mx / max(gn, 1e-6) : 1.  agc_clipping < 0: f_unit = 1.
+ * grad_scale / found_inf: as brats_ranger_step_amp (found_inf non-zero: every kernel returns at once, nothing is written).
+ * Reductions run in a fixed order without atomics: results are bit-reproducible. */
+typedef struct {
+  const void* param;
+  void* grad;
+  long long numel;
+  int unit_len;
+  int unit_stride;
+  int unit_base;
+  int nunits;
+} brats_gradclip_tensor;
+int brats_gradclip_chunk(void);
+int brats_gradclip(const brats_gradclip_tensor* table, int ntensors, const int* units, int nunits, const int* chunks,
+                   int nchunks, float* stats, float* pair, float max_norm, float agc_clipping, float agc_eps,
+                   const float* grad_scale, const float* found_inf, brats_stream_t s);
 
 /* ---- input pipeline on the GPU (the reference's CPU transform chain,
  * src/definer.py:449-467).  NCDHW f32.
