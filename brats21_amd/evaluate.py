@@ -18,13 +18,21 @@ like the reference does.  Where the GPU form differs from the reference:
   3. Both always return a float32 tensor on the input's device (the reference returns a uint8 numpy array when it replaced
      something).
   4. A volume without a single background voxel is outside the contract (the reference assumes label 0 exists).
+
+The reference's ensemble fusion by STAPLE (--perform_staple / --staple_threshold, learning/engine.py:244-247) is here as well:
+perform_staple_on_brats_multi_channel (utils/transforms.py:650-687) and Evaluator(perform_staple=True, staple_threshold=) run
+ops.staple (csrc/staple.hip) on bit-packed rater decisions.  The reference calls SimpleITK's STAPLEImageFilter; SimpleITK is not
+available to this project's tests, so the kernels implement ITK's STAPLEImageFilter::GenerateData as RESTATED in DESIGN.md
+section 6 and are tested against a numpy restatement of the same text (tests/_staple_ref.py): nothing executable pins the ITK
+boundary.  The fused maps are float32 0 / 1 on the input's device (the reference returns a bool tensor on the CPU), and any
+batch size works (the reference: batch 1).
 """
 import numbers
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .inferers import GraphedPredictor, _first, sliding_window_inference
 from .transforms import convert_to_multichannel
 
@@ -242,6 +250,34 @@ def get_post_transforms(args):
     return post
 
 
+def perform_staple_on_brats_multi_channel(datas, threshold_value=0.5, return_as_tensor=True):
+    """utils/transforms.py:650-687 on the GPU: datas = the raters' thresholded TC / WT / ET maps, a sequence of [N, 3, D, H, W]
+    0 / 1 tensors (or numpy arrays); every (sample, channel) is fused by STAPLE on its own (ops.staple; 10000 iterations at
+    most, foreground value 1, as the reference sets them) and the weights are binarised with > threshold_value.
+    -> float32 0 / 1 [N, 3, D, H, W] on the device of the inputs (CPU inputs are copied to the GPU and back), or a numpy array
+    when not return_as_tensor."""
+    ops._staple_check_threshold(threshold_value, "threshold_value")
+    datas = [torch.from_numpy(np.ascontiguousarray(d)) if isinstance(d, np.ndarray) else d for d in datas]
+    if not 1 <= len(datas) <= ops.STAPLE_MAX_RATERS:
+        raise ValueError(f"perform_staple_on_brats_multi_channel: {len(datas)} raters (1 .. {ops.STAPLE_MAX_RATERS} supported)")
+    for d in datas:
+        if not torch.is_tensor(d):
+            raise TypeError(f"perform_staple_on_brats_multi_channel: expected tensors or arrays, got {type(d).__name__}")
+        if d.dim() != 5 or tuple(d.shape) != tuple(datas[0].shape) or d.device != datas[0].device:
+            raise ValueError(f"perform_staple_on_brats_multi_channel: every rater must be [N, C, D, H, W] of one shape on one "
+                             f"device, got {tuple(datas[0].shape)} on {datas[0].device} and {tuple(d.shape)} on {d.device}")
+    src = datas[0].device
+    if src.type != "cuda" and not torch.cuda.is_available():
+        raise _lib.BratsHipError("brats21_amd.evaluate.perform_staple_on_brats_multi_channel runs on the GPU only (no CPU fallback)")
+    dev = src if src.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    packer = ops.StaplePacker(datas[0].shape, len(datas), dev)
+    for d in datas:  # one rater at a time: a CPU ensemble is never on the GPU as a whole
+        packer.add(d.to(dev))
+    seg = ops.staple(packer, float(threshold_value))[0]
+    seg = seg if src.type == "cuda" else seg.to(src)
+    return seg if return_as_tensor else seg.cpu().numpy()
+
+
 class Evaluator:
     """The per-case body of Engine.evaluate (learning/engine.py:205-285) for one or several models:
     pad to k -> [TTA x] (sliding window | whole volume) -> on-GPU mean of sigmoid -> threshold ->
@@ -262,11 +298,20 @@ class Evaluator:
     ``metrics`` (default None: only ``dice``, as before) is a tuple of names of brats21_amd.metrics.METRICS (the
     reference's ``--key_metric`` / ``--additional_metrics``): with a target, ``out`` also holds ``hausdorff_distance95`` /
     ``sensitivity`` / ``specificity`` as device float32 [N, K], computed like ``dice`` on the padded segmentation and
-    target after background removal and before cropping (learning/engine.py:259-268)."""
+    target after background removal and before cropping (learning/engine.py:259-268).
+
+    ``perform_staple`` / ``staple_threshold`` (default off) are the reference's ``--perform_staple --staple_threshold T``
+    (learning/engine.py:244-247): instead of the mean, every model x TTA pass is a rater -- its own sigmoid goes through the post
+    chain (threshold, and the per-rater cleaning / replacement when those are set: the reference's apply_f(outputs,
+    post_trans)), the 0 / 1 result is packed to one bit per voxel (ops.StaplePacker), and ops.staple fuses the raters per
+    channel; W > staple_threshold replaces the thresholded mean, everything after it (background removal, metrics, labels,
+    crop) is unchanged.  At most 256 raters.  The only host read is STAPLE's done flag; ``out["staple"]`` holds ops.staple's
+    info (p, q, prior, iterations)."""
 
     def __init__(self, models, tta_transforms=None, sliding_window_size=None, sw_batch_size=1, overlap=0.25,
                  k_divisible=8, thresh=0.5, amp=True, use_graph=None, max_graphs=4, amp_dtype=torch.bfloat16,
-                 cleaning_areas_threshold=None, replace_value_threshold=None, metrics=None):
+                 cleaning_areas_threshold=None, replace_value_threshold=None, metrics=None, perform_staple=False,
+                 staple_threshold=0.5):
         _check_int(cleaning_areas_threshold, "cleaning_areas_threshold", allow_none=True)
         _check_int(replace_value_threshold, "replace_value_threshold", allow_none=True)
         if metrics is not None:
@@ -281,6 +326,13 @@ class Evaluator:
             use_graph = sliding_window_size is not None
         self.predictors = [GraphedPredictor(self._amp(m), modules=m, max_graphs=max_graphs) if use_graph else self._amp(m)
                            for m in self.models]
+        self.perform_staple = bool(perform_staple)
+        self.staple_threshold = ops._staple_check_threshold(staple_threshold, "staple_threshold")
+        if self.perform_staple:
+            self.raters = len(self.models) * (1 if tta_transforms is None else sum(1 for _ in tta_transforms))
+            if not 1 <= self.raters <= ops.STAPLE_MAX_RATERS:
+                raise ValueError(f"perform_staple: {len(self.models)} models x TTA passes = {self.raters} raters "
+                                 f"(1 .. {ops.STAPLE_MAX_RATERS} supported)")
 
     def _amp(self, model):
         def run(x):
@@ -312,21 +364,47 @@ class Evaluator:
                 passes += 1
         return acc, passes
 
+    def _post(self, prob, passes):
+        return _post_chain(prob, passes, self.thresh, cleaning_threshold=self.clean_t, clean=self.clean_t is not None,
+                           replace_threshold=self.replace_t, replace=self.replace_t is not None)
+
+    @torch.no_grad()
+    def staple_segmentation(self, image):
+        """Every model x TTA pass on the (padded) image as a STAPLE rater (learning/engine.py:229-247) -> (fused 0 / 1 maps,
+        ops.staple's info).  Only one pass's probability exists at a time; the raters are kept as bits."""
+        packer = None
+        for model, predictor in zip(self.models, self.predictors):
+            model.eval()
+            for t in ([None] if self.tta is None else self.tta):
+                if t is None:
+                    prob = torch.sigmoid(self._logits(predictor, image))
+                else:
+                    logits = self._logits(predictor, t.augment_image(image))
+                    prob = torch.zeros(t.deaug_perm.out_shape(logits.shape), dtype=torch.float32, device=image.device)
+                    t.accumulate_probability(logits, prob)
+                mask = self._post(prob, 1)
+                if packer is None:
+                    packer = ops.StaplePacker(mask.shape, self.raters, mask.device)
+                packer.add(mask)
+        return ops.staple(packer, self.staple_threshold)
+
     @torch.no_grad()
     def __call__(self, image, target=None, return_original_shape=True, want_labels=False):
         """image [N, C, D, H, W] (cuda) -> dict(seg, [labels], [dice]); seg is cropped back to the input
         shape when return_original_shape (learning/engine.py:282-285)."""
         _need_cuda(image, "Evaluator")
         padded, p_b, p_a = shape_to_divisible(image, k=self.k)
-        acc, passes = self.probability_sum(padded)
-        if self.clean_t is None and self.replace_t is None:
-            res = finalize_segmentation(acc, passes, padded, self.thresh, want_labels)
-        else:
-            seg = _post_chain(acc, passes, self.thresh, cleaning_threshold=self.clean_t, clean=self.clean_t is not None,
-                              replace_threshold=self.replace_t, replace=self.replace_t is not None)
-            res = finalize_segmentation(seg, 1, padded, 0.5, want_labels)
-        seg, labels = res if want_labels else (res, None)
         out = {}
+        if self.perform_staple:
+            seg, out["staple"] = self.staple_segmentation(padded)
+            res = finalize_segmentation(seg, 1, padded, 0.5, want_labels)
+        else:
+            acc, passes = self.probability_sum(padded)
+            if self.clean_t is None and self.replace_t is None:
+                res = finalize_segmentation(acc, passes, padded, self.thresh, want_labels)
+            else:
+                res = finalize_segmentation(self._post(acc, passes), 1, padded, 0.5, want_labels)
+        seg, labels = res if want_labels else (res, None)
         if target is not None:
             tp = shape_to_divisible(target, k=self.k)[0]
             out["dice"] = hard_dice_metric(seg, tp)

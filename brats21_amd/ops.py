@@ -1290,6 +1290,149 @@ def distance_transform_edt(mask, mode=0):
     return out
 
 
+# ------------------------------------------------------------------------------------------ STAPLE fusion
+STAPLE_MAX_RATERS = 256
+STAPLE_CHUNK = 16  # iterations enqueued between two reads of the done flags (scripts/time_staple.py records the time with it)
+
+
+def _staple_check_shape(shape):
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 5 or min(shape) < 1:
+        raise ValueError(f"STAPLE works on [N, C, D, H, W] maps, got shape {shape}")
+    if shape[2] * shape[3] * shape[4] >= 2 ** 31:
+        raise ValueError(f"STAPLE: {shape[2] * shape[3] * shape[4]} voxels per sample (fewer than 2^31 supported)")
+    if shape[0] * shape[1] > 65535:
+        raise ValueError(f"STAPLE: {shape[0] * shape[1]} (sample, channel) problems (at most 65535 supported)")
+    return shape
+
+
+class StaplePacker:
+    """The streaming input of ``staple``: ``add(mask)`` takes one rater's 0 / 1 map [N, C, D, H, W] (cuda; f32, uint8 or bool;
+    foreground = value 1) and keeps ONE BIT of it per voxel -- uint32 planes [N * C, ceil(max_raters / 32), voxels] plus the
+    rater's foreground count per (sample, channel) -- so an ensemble of 160 passes costs 20 bytes per voxel and channel, not 640.
+    The planes are allocated by the first ``add`` (on ``device``, or on the first mask's device when None)."""
+
+    def __init__(self, shape, max_raters, device=None):
+        self.shape = _staple_check_shape(shape)
+        if isinstance(max_raters, bool) or not isinstance(max_raters, int) or not 1 <= max_raters <= STAPLE_MAX_RATERS:
+            raise ValueError(f"StaplePacker: max_raters must be an int in 1 .. {STAPLE_MAX_RATERS}, got {max_raters!r}")
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != "cuda":
+            raise _lib.BratsHipError("brats21_amd.ops.StaplePacker runs on the GPU only (no CPU fallback)")
+        self.max_raters, self.raters = max_raters, 0
+        self.words = (max_raters + 31) // 32
+        self.problems = self.shape[0] * self.shape[1]
+        self.voxels = self.shape[2] * self.shape[3] * self.shape[4]
+        self.bits = self.counts = None
+
+    def add(self, mask):
+        if not torch.is_tensor(mask):
+            raise TypeError(f"StaplePacker.add: expected a torch.Tensor, got {type(mask).__name__}")
+        if tuple(mask.shape) != self.shape:
+            raise ValueError(f"StaplePacker.add: map of shape {tuple(mask.shape)}, the packer was made for {self.shape}")
+        if not mask.is_cuda:
+            raise _lib.BratsHipError("brats21_amd.ops.StaplePacker.add runs on the GPU only (no CPU fallback)")
+        if self.raters >= self.max_raters:
+            raise ValueError(f"StaplePacker.add: the packer was made for {self.max_raters} raters")
+        if self.device is None:
+            self.device = mask.device
+        if mask.device != self.device:
+            raise ValueError(f"StaplePacker.add: map on {mask.device}, the packer is on {self.device}")
+        if mask.dtype == torch.bool:
+            m, kind = mask.contiguous().view(torch.uint8), MASK_U8
+        elif mask.dtype == torch.uint8:
+            m, kind = mask.contiguous(), MASK_U8
+        else:
+            m, kind = mask.contiguous().float(), MASK_F32
+        with torch.cuda.device(self.device):
+            if self.bits is None:
+                self.bits = torch.zeros((self.problems, self.words, self.voxels), dtype=torch.int32, device=self.device)
+                self.counts = torch.zeros((self.problems, self.max_raters), dtype=torch.int32, device=self.device)
+            _lib.check(_lib.lib().brats_staple_pack(m.data_ptr(), kind, self.bits.data_ptr(), self.counts.data_ptr(), self.max_raters,
+                                                    self.problems, self.words, self.voxels, self.raters, _stream()), "staple_pack")
+        self.raters += 1
+        return self
+
+
+def _staple_check_threshold(threshold, what="threshold"):
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 <= float(threshold) <= 1.0:
+        raise ValueError(f"STAPLE: {what} must be a number in [0, 1], got {threshold!r}")
+    return float(threshold)
+
+
+def staple(raters_or_packer, threshold=0.5, max_iterations=10000, return_probability=False, chunk=None):
+    """STAPLE fusion (Warfield et al.) of binary maps, ITK's STAPLEImageFilter as restated in DESIGN.md section 6 -- the
+    reference's perform_staple_on_brats_multi_channel (utils/transforms.py:650-687) without SimpleITK and without the host:
+    every (sample, channel) is a problem of its own (the reference takes batch 1 only).
+
+    raters_or_packer: a list of R 0 / 1 maps [N, C, D, H, W] (cuda), or a StaplePacker they were streamed into.
+    -> (seg, info): seg f32 0 / 1 [N, C, D, H, W] = W > threshold (a NaN weight is background: a channel that no rater marks, or
+    that every rater fills, comes out empty, as from ITK); info = device tensors p [N, C, R] (sensitivities), q [N, C, R]
+    (specificities), prior [N, C], iterations [N, C] (int32; ITK's GetElapsedIterations()), plus ``probability`` (f64 W) with
+    return_probability, and the ints ``chunk`` / ``host_reads``.
+
+    The EM loop is data dependent and driven from here: ``chunk`` iterations (default STAPLE_CHUNK) are enqueued at a time and
+    the done flags are read once per chunk -- the only host read.  The kernels skip a finished problem, so the result and
+    ``iterations`` do not depend on the chunk length; all sums have a fixed order (csrc/staple.hip), so neither do they on the
+    run."""
+    threshold = _staple_check_threshold(threshold)
+    if isinstance(max_iterations, bool) or not isinstance(max_iterations, int) or not 1 <= max_iterations < 2 ** 31:
+        raise ValueError(f"staple: max_iterations must be a positive int, got {max_iterations!r}")
+    chunk = STAPLE_CHUNK if chunk is None else chunk
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"staple: chunk must be a positive int, got {chunk!r}")
+    if isinstance(raters_or_packer, StaplePacker):
+        pk = raters_or_packer
+        if pk.raters < 1:
+            raise ValueError("staple: the packer holds no rater")
+    else:
+        raters = list(raters_or_packer)
+        if not 1 <= len(raters) <= STAPLE_MAX_RATERS:
+            raise ValueError(f"staple: {len(raters)} raters (1 .. {STAPLE_MAX_RATERS} supported)")
+        for m in raters:
+            if not torch.is_tensor(m):
+                raise TypeError(f"staple: expected torch.Tensor maps, got {type(m).__name__}")
+            if tuple(m.shape) != tuple(raters[0].shape):
+                raise ValueError(f"staple: maps of different shapes {tuple(raters[0].shape)} and {tuple(m.shape)}")
+        _staple_check_shape(raters[0].shape)
+        if not all(m.is_cuda for m in raters):
+            raise _lib.BratsHipError("brats21_amd.ops.staple runs on the GPU only (no CPU fallback)")
+        pk = StaplePacker(raters[0].shape, len(raters), raters[0].device)
+        for m in raters:
+            pk.add(m)
+    r, nc, vox, dev = pk.raters, pk.problems, pk.voxels, pk.device
+    l = _lib.lib()
+    with torch.cuda.device(dev):
+        words = (r + 31) // 32
+        bits = pk.bits if words == pk.words else pk.bits[:, :words].contiguous()  # (a packer made for more raters than it got)
+        state = torch.empty((nc, 2 + 4 * r), dtype=torch.float64, device=dev)
+        flags = torch.empty((nc, 4), dtype=torch.int32, device=dev)
+        partial = torch.empty((nc, l.brats_staple_blocks(vox), r + 1), dtype=torch.float64, device=dev)
+        _lib.check(l.brats_staple_init(bits.data_ptr(), pk.counts.data_ptr(), pk.max_raters, state.data_ptr(), flags.data_ptr(), nc,
+                                       r, vox, _stream()), "staple_init")
+        enqueued = reads = 0
+        while enqueued < max_iterations:
+            n = min(chunk, max_iterations - enqueued)
+            _lib.check(l.brats_staple_iterate(bits.data_ptr(), pk.counts.data_ptr(), pk.max_raters, state.data_ptr(),
+                                              flags.data_ptr(), partial.data_ptr(), nc, r, vox, max_iterations, n, _stream()),
+                       "staple_iterate")
+            enqueued += n
+            if enqueued < max_iterations:  # (after max_iterations every problem is done)
+                reads += 1
+                if bool(flags[:, 1].all()):
+                    break
+        seg = torch.empty(pk.shape, dtype=torch.float32, device=dev)
+        prob = torch.empty(pk.shape, dtype=torch.float64, device=dev) if return_probability else None
+        _lib.check(l.brats_staple_apply(bits.data_ptr(), state.data_ptr(), nc, r, vox, threshold, seg.data_ptr(), MASK_F32,
+                                        prob.data_ptr() if prob is not None else None, _stream()), "staple_apply")
+    n, c = pk.shape[:2]
+    info = {"p": state[:, 2:2 + r].reshape(n, c, r), "q": state[:, 2 + r:2 + 2 * r].reshape(n, c, r),
+            "prior": state[:, 0].reshape(n, c), "iterations": flags[:, 2].reshape(n, c), "chunk": chunk, "host_reads": reads}
+    if prob is not None:
+        info["probability"] = prob
+    return seg, info
+
+
 # ------------------------------------------------------------------------------------------ box calibration
 def probe_box(device=None, mfma_ms=50.0, stream_bytes=403 << 20, modes=(0, 1)):
     """What THIS box delivers right now on the two resources the rooflines are quoted against (csrc/probe.hip): 16-bit

@@ -53,8 +53,9 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * brats_dropout, brats_evonorm_bwd_tiles + its workspace query); 6 in round 6 (additions only: brats_conv3d_set_kp); 7: additions
  * only (brats_cc_filter, brats_rare_fill + their workspace queries).  Still 7 after further additions only (brats_hausdorff +
  * its workspace query; brats_edt + its workspace query, brats_sigmoid_argmax_onehot, brats_hd_loss_stats / _grad,
- * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk): an older library lacks
- * them and says so when they are called (brats21_amd/_lib.py), and tests/test_postproc_cpu.py pins the 7. */
+ * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk; brats_staple_blocks / _pack /
+ * _init / _iterate / _apply): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
 const char* brats_last_error(void);
@@ -699,6 +700,40 @@ int brats_gradclip_chunk(void);
 int brats_gradclip(const brats_gradclip_tensor* table, int ntensors, const int* units, int nunits, const int* chunks,
                    int nchunks, float* stats, float* pair, float max_norm, float agc_clipping, float agc_eps,
                    const float* grad_scale, const float* found_inf, brats_stream_t s);
+
+/* ---- STAPLE fusion of an ensemble's binary maps: the reference's --perform_staple / --staple_threshold (learning/engine.py:
+ * 244-247 -> perform_staple_on_brats_multi_channel, utils/transforms.py:650-687: SimpleITK's STAPLEImageFilter per channel on the
+ * host).  The contract is ITK's STAPLEImageFilter::GenerateData as RESTATED in DESIGN.md section 6 (SimpleITK is not available
+ * to the tests: nothing executable pins that boundary).  NC independent problems (sample x channel) of R raters over V voxels,
+ * 1 <= R <= 256, V < 2^31 (BRATS_E_UNSUPPORTED beyond), all arithmetic f64 in a fixed order without floating-point atomics:
+ * the same input gives the same bits at every run.
+ *   bits   : uint32 [NC][words][V], words = ceil(R / 32): bit (r % 32) of word r / 32 = rater r's decision; zeroed by the caller
+ *   counts : uint32 [NC][count_stride >= R]: foreground voxels of each rater; zeroed by the caller
+ *   state  : f64 [NC][2 + 4 R] = g (the prior), sum of W of the last M-step, p[R], q[R], last_p[R], last_q[R]
+ *   flags  : int32 [NC][4] = next iteration index, done, iterations (ITK's GetElapsedIterations(): the index of the iteration
+ *            that converged, or max_iterations), number of voxels that no rater marks
+ *   partial: f64 [NC][brats_staple_blocks(V)][R + 1] workspace (per-workgroup sums)
+ * pack   : ORs rater `rater`'s map mask[NC][V] (BRATS_MASK_F32 / BRATS_MASK_U8; foreground = value 1) into bits and adds its
+ *          foreground count to counts; call once per rater index.
+ * init   : after the last pack: g = (sum of all votes) / (R V), one division of exact integers; last_p = last_q = -10; flags.
+ * iterate: enqueues `iterations` iterations of two launches each: (a) W of every voxel from its pattern and the current p, q
+ *          (votes / R in iteration 0) and the per-workgroup sums of W and W D[j]; (b) one workgroup per problem: p[j] =
+ *          sum W D[j] / sum W, q[j] = ((V - sum W) - (count_j - sum W D[j])) / (V - sum W), then the convergence rule: done when
+ *          no j has (p[j] - last_p[j])^2 > 1e-14 or (q[j] - last_q[j])^2 > 1e-14 (a NaN counts as converged), or after
+ *          max_iterations.  Every launch returns at once for a problem that is done, so the caller may enqueue any number of
+ *          iterations and read flags whenever it likes: the result does not depend on it.  No kernel waits for another workgroup.
+ * apply  : W = g a / (g a + (1 - g) b), a = prod_j (D_j ? p_j : 1 - p_j), b = prod_j (D_j ? 1 - q_j : q_j) in rater order;
+ *          seg[NC][V] (seg_kind BRATS_MASK_F32: f32 0 / 1, BRATS_MASK_U8: bytes; may be NULL) = W > threshold, NaN -> 0;
+ *          prob[NC][V] (f64, may be NULL) = W. */
+int brats_staple_blocks(size_t V);
+int brats_staple_pack(const void* mask, int mask_kind, uint32_t* bits, uint32_t* counts, int count_stride, int NC, int words,
+                      size_t V, int rater, brats_stream_t s);
+int brats_staple_init(const uint32_t* bits, const uint32_t* counts, int count_stride, double* state, int* flags, int NC, int R,
+                      size_t V, brats_stream_t s);
+int brats_staple_iterate(const uint32_t* bits, const uint32_t* counts, int count_stride, double* state, int* flags,
+                         double* partial, int NC, int R, size_t V, int max_iterations, int iterations, brats_stream_t s);
+int brats_staple_apply(const uint32_t* bits, const double* state, int NC, int R, size_t V, double threshold, void* seg,
+                       int seg_kind, double* prob, brats_stream_t s);
 
 /* ---- input pipeline on the GPU (the reference's CPU transform chain,
  * src/definer.py:449-467).  NCDHW f32.
