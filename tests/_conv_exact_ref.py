@@ -1,0 +1,351 @@
+"""Exact integer-operand references for the convolution kernels (tests/test_conv_exact_cpu.py, tests/test_conv_exact_gpu.py).
+
+The technique: every element of x, dy, w (and the bias) is a small integer, exact in bf16, fp16, f32, e4m3 and in the hi
+half of a split-precision pair.  Every product is then an integer, and while the worst-case sum of absolute values stays
+below 2^24 every partial sum in every summation order is exactly representable in f32: a kernel's f32 result must equal the
+reference BIT FOR BIT whatever its split-K schedule, slab order or MFMA shape, and a 16-bit output is the round-to-nearest-
+even of an exact integer.  The bounds are preconditions asserted on the operands / the reference alone (require_*).
+
+The references are float64 shifted GEMMs, one per tap, independent of torch's convolution.  Activations are channels-last
+[N, D, H, W, C] CPU float32 tensors (the layout the kernels read), weights torch's [Cout, Cin, k, k, k].
+
+The second half mirrors the host selection rules of csrc/conv_wgrad.hip (wgrad_nlane, wgrad_g8, wgrad_tiles,
+wgrad_alltaps_ok, wgrad_reduce_launch, wgrad_shift_geometry) -- the arithmetic is copied, so that a change of a rule makes the
+GPU tests fail (their mirrored workspace size no longer equals the library's) instead of quietly exercising another branch."""
+import functools
+
+import torch
+
+EXACT = float(2 ** 24)  # integers up to here are exact in f32
+
+
+# ------------------------------------------------------------------------------------------ operands
+def int_tensor(shape, seed, density=1.0, amax=2):
+    """Seeded CPU float32 tensor with integer values in [-amax, amax]; an element is non-zero with probability `density`
+    (non-zero values uniform over -amax..-1, 1..amax).  density = 1: uniform over -amax..amax (zero included)."""
+    g = torch.Generator().manual_seed(seed)
+    if density >= 1.0:
+        return torch.randint(-amax, amax + 1, shape, generator=g).float()
+    mag = torch.randint(1, amax + 1, shape, generator=g).float()
+    sign = torch.randint(0, 2, shape, generator=g).float() * 2 - 1
+    keep = (torch.rand(shape, generator=g) < density).float()
+    return mag * sign * keep
+
+
+def stats_density(cin, voxels, amax_x=2, amax_w=1):
+    """A density of x at which the EXPECTED per-(n, channel) total of y^2 of a 3x3x3 layer is 2^22 (a quarter of the bound
+    require_stats_exact asserts), for dense weights uniform over -amax_w..amax_w.  Derived from the operand distributions
+    only: E[y^2] = 27 cin density E[x^2 | x != 0] E[w^2]."""
+    ex2 = sum(v * v for v in range(1, amax_x + 1)) / amax_x
+    ew2 = sum(v * v for v in range(-amax_w, amax_w + 1)) / (2 * amax_w + 1)
+    return min(1.0, 2.0 ** 22 / (voxels * 27.0 * cin * ex2 * ew2))
+
+
+# ------------------------------------------------------------------------------------------ preconditions
+def require_wgrad_exact(x, dy, x2=None):
+    """Weight / bias gradient: K max|x| max|dy| < 2^24 with K = n d h w (every partial sum over voxels is an exact integer)."""
+    k = dy.shape[0] * dy.shape[1] * dy.shape[2] * dy.shape[3]
+    ax = float(x.abs().max()) if x2 is None else max(float(x.abs().max()), float(x2.abs().max()))
+    bound = k * max(ax, 1.0) * max(float(dy.abs().max()), 1.0)
+    for t in (x, dy) + (() if x2 is None else (x2,)):
+        assert bool((t == t.round()).all()), "operands must be integers"
+    assert bound < EXACT, f"weight-gradient precondition violated: K max|x| max|dy| = {bound:.0f} >= 2^24"
+
+
+def require_fwd_exact(x, w, bias=None, x2=None):
+    """Forward / input gradient: taps (cin + cin2) max|x| max|w| + max|bias| < 2^24."""
+    cin = x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)
+    taps = w.shape[2] * w.shape[3] * w.shape[4]
+    ax = float(x.abs().max()) if x2 is None else max(float(x.abs().max()), float(x2.abs().max()))
+    bound = taps * cin * max(ax, 1.0) * max(float(w.abs().max()), 1.0) + (float(bias.abs().max()) if bias is not None else 0.0)
+    for t in (x, w) + (() if x2 is None else (x2,)) + (() if bias is None else (bias,)):
+        assert bool((t == t.round()).all()), "operands must be integers"
+    assert bound < EXACT, f"forward precondition violated: taps cin max|x| max|w| + |bias| = {bound:.0f} >= 2^24"
+
+
+def require_sum_exact(y_ref):
+    """Per-(n, channel) sum of y: exact when the total of |y| is below 2^24 (it bounds every partial sum)."""
+    tot = float(y_ref.abs().sum((1, 2, 3)).max())
+    assert tot < EXACT, f"statistics precondition violated: per-(n, channel) sum of |y| = {tot:.0f} >= 2^24"
+
+
+def require_stats_exact(y_ref):
+    """Per-(n, channel) sum of y^2: all terms are non-negative, so every partial sum is bounded by the total."""
+    tot = float((y_ref.double() ** 2).sum((1, 2, 3)).max())
+    assert tot < EXACT, f"statistics precondition violated: per-(n, channel) sum of y^2 = {tot:.0f} >= 2^24"
+
+
+def stats_exact_ok(y_ref):
+    return float((y_ref.double() ** 2).sum((1, 2, 3)).max()) < EXACT
+
+
+# ------------------------------------------------------------------------------------------ float64 shifted-GEMM references
+def _taps(k, dil):
+    """[(tap index in torch's k x k x k order, (dz, dy, dx) voxel offset)]"""
+    if k == 1:
+        return [(0, (0, 0, 0))]
+    return [((a * 3 + b) * 3 + c, ((a - 1) * dil, (b - 1) * dil, (c - 1) * dil)) for a in range(3) for b in range(3) for c in range(3)]
+
+
+def _cat(x, x2):
+    return x if x2 is None else torch.cat([x, x2], -1)
+
+
+def _padded(x, r):
+    """float64 copy of the channels-last x with r zero voxels on every face."""
+    n, d, h, w, c = x.shape
+    xp = torch.zeros((n, d + 2 * r, h + 2 * r, w + 2 * r, c), dtype=torch.float64)
+    xp[:, r:r + d, r:r + h, r:r + w] = x.double()
+    return xp
+
+
+def wgrad_ref(x, dy, dil=1, k=3, x2=None):
+    """dW[co][ci][tap] = sum_v dy[v][co] * [x | x2][v + off(tap)][ci]: one float64 GEMM dy^T @ x_shifted per tap."""
+    x = _cat(x, x2)
+    n, d, h, w, c = x.shape
+    co = dy.shape[-1]
+    r = dil if k == 3 else 0
+    xp = _padded(x, r)
+    dyt = dy.double().reshape(-1, co).t().contiguous()
+    out = torch.empty((co, c, k ** 3), dtype=torch.float64)
+    for t, (oz, oy, ox) in _taps(k, dil):
+        xs = xp[:, r + oz:r + oz + d, r + oy:r + oy + h, r + ox:r + ox + w].reshape(-1, c)
+        out[:, :, t] = dyt @ xs
+    return out.reshape(co, c, k, k, k)
+
+
+def dbias_ref(dy):
+    return dy.double().sum((0, 1, 2, 3))
+
+
+def fwd_ref(x, wt, bias=None, dil=1, x2=None):
+    """y[v][co] = bias[co] + sum_tap [x | x2][v + off(tap)] @ wt[:, :, tap]^T, channels-last float64."""
+    x = _cat(x, x2)
+    n, d, h, w, c = x.shape
+    co, k = wt.shape[0], wt.shape[2]
+    r = dil if k == 3 else 0
+    xp = _padded(x, r)
+    wm = wt.double().reshape(co, c, k ** 3)
+    y = torch.zeros((n * d * h * w, co), dtype=torch.float64)
+    for t, (oz, oy, ox) in _taps(k, dil):
+        xs = xp[:, r + oz:r + oz + d, r + oy:r + oy + h, r + ox:r + ox + w].reshape(-1, c)
+        y += xs @ wm[:, :, t].t()
+    if bias is not None:
+        y += bias.double()
+    return y.reshape(n, d, h, w, co)
+
+
+def dgrad_ref(dy, wt, dil=1):
+    """dx[v + off(tap)][ci] += dy[v] @ wt[:, :, tap]: the forward loop transposed (a scatter into a padded dx), float64."""
+    n, d, h, w, co = dy.shape
+    c, k = wt.shape[1], wt.shape[2]
+    r = dil if k == 3 else 0
+    wm = wt.double().reshape(co, c, k ** 3)
+    dxp = torch.zeros((n, d + 2 * r, h + 2 * r, w + 2 * r, c), dtype=torch.float64)
+    dym = dy.double().reshape(-1, co)
+    for t, (oz, oy, ox) in _taps(k, dil):
+        dxp[:, r + oz:r + oz + d, r + oy:r + oy + h, r + ox:r + ox + w] += (dym @ wm[:, :, t]).reshape(n, d, h, w, c)
+    return dxp[:, r:r + d, r:r + h, r:r + w].contiguous()
+
+
+def tile_sums_ref(y_ref):
+    """(sum y, sum y^2) per (n, channel) of the unrounded result: [n, cout] float64 each."""
+    yd = y_ref.double()
+    return yd.sum((1, 2, 3)), (yd * yd).sum((1, 2, 3))
+
+
+# ------------------------------------------------------------------------------------------ the comparison
+def assert_exact(got, ref, dtype=None, what=""):
+    """`got` (any device) equals the float64 reference bit for bit: `ref` is cast to f32 (exact under the preconditions) and,
+    for a 16-bit kernel output, rounded to `dtype` (round to nearest even, as the kernels' conversions do).  The one
+    comparison of the CPU and the GPU tests; a mismatch reports how many entries differ and the first of them."""
+    want = ref.float()
+    assert torch.equal(want.double(), ref.double()), f"{what}: the reference itself is not exact in f32"
+    if dtype is not None and dtype != torch.float32:
+        want = want.to(dtype)
+    g = got.detach().cpu()
+    assert g.shape == want.shape, f"{what}: shape {tuple(g.shape)} != {tuple(want.shape)}"
+    assert g.dtype == want.dtype, f"{what}: dtype {g.dtype} != {want.dtype}"
+    if torch.equal(g, want):
+        return
+    bad = (g.float() != want.float()) | (g.float().isnan() != want.float().isnan())
+    idx = bad.nonzero()
+    first = tuple(int(i) for i in idx[0])
+    raise AssertionError(f"{what}: {idx.shape[0]} of {bad.numel()} entries differ; first at {first}: got {float(g[first])}, "
+                         f"want {float(want[first])}")
+
+
+def assert_stats_exact(stats, y_ref, squares=True, what=""):
+    """The tile statistics [N, tiles, cout, 2] summed over the tiles in float64 equal the reference's sums exactly."""
+    s = stats.detach().double().sum(1).cpu()
+    r1, r2 = tile_sums_ref(y_ref)
+    require_sum_exact(y_ref)
+    assert torch.equal(s[..., 0], r1), f"{what}: sum of y differs at {int((s[..., 0] != r1).sum())} of {r1.numel()} (n, channel) entries"
+    if squares:
+        require_stats_exact(y_ref)
+        assert torch.equal(s[..., 1], r2), f"{what}: sum of y^2 differs at {int((s[..., 1] != r2).sum())} of {r2.numel()} entries"
+
+
+# ------------------------------------------------------------------------------------------ mirror of csrc/conv_wgrad.hip
+WG_TZ, WG_TY, WG_TX = 4, 4, 16
+
+
+def ceil_div(a, b):
+    return (a + b - 1) // b
+
+
+def wgrad_ntiles(n, d, h, w):
+    return n * ceil_div(d, WG_TZ) * ceil_div(h, WG_TY) * ceil_div(w, WG_TX)
+
+
+def wgrad_nlane(ntiles):
+    nl = 8
+    while nl > 1 and ntiles // nl < 16:
+        nl >>= 1
+    return nl
+
+
+def wgrad_g8(ntiles, cotiles, citiles, ntaps_planes=3):
+    nl = wgrad_nlane(ntiles)
+    g8 = ceil_div(512, ntaps_planes * nl * cotiles * citiles)
+    g8 = min(g8, ceil_div(ntiles, nl))
+    return max(g8, 1)
+
+
+def wgrad_tiles(f32, c1, c2, cout):
+    """(COF, CIF): 16-channel fragments per co / ci tile."""
+    co16 = ceil_div(cout, 16)
+    cof = 3 if co16 % 3 == 0 else (2 if co16 % 2 == 0 else 1)
+    if f32:
+        return cof, 1
+    a, b = ceil_div(c1, 16), (ceil_div(c2, 16) if c2 > 0 else 0)
+
+    def ok(f):
+        return a % f == 0 and (b == 0 or b % f == 0)
+
+    return cof, (3 if ok(3) else (2 if ok(2) else 1))
+
+
+def wgrad_alltaps_ok(mode, bits16, dil, c1, c2, cout, ntiles, ncu):
+    """None, or (g8, kernel name) of the all-taps form the library takes (mode = brats_conv3d_set_wgrad_alltaps)."""
+    cin = c1 + max(c2, 0)
+    narrow = c2 <= 0 and c1 <= 16
+    if not mode or not bits16 or dil != 1:
+        return None
+    wide = False
+    if cout % 48 or (not narrow and (c1 % 48 or (c2 > 0 and c2 % 48))):
+        if cout % 64 or (not narrow and (c1 % 32 or (c2 > 0 and c2 % 32))):
+            return None
+        wide = True
+    blocks = (cout // 64) * (1 if narrow else cin // 32) if wide else (cout // 48) * (1 if narrow else cin // 48)
+    nl = wgrad_nlane(ntiles)
+    g8 = max(ceil_div(ncu, nl * blocks), 1)
+    if ntiles < 4 * nl * g8:
+        return None
+    if wide and narrow:
+        name = "alltaps_kernel<1, 4>"
+    elif wide:
+        name = "alltaps2<4, 2>"
+    elif narrow and c1 % 8 == 0:
+        name = "alltaps2<3, 1>"
+    elif narrow:
+        name = "alltaps_kernel<1>"
+    else:
+        name = "alltaps2<3, 3>"
+    return g8, name
+
+
+def wgrad_reduce_kind(cout, cin, taps):
+    tblocks = (cout * cin // 4 + 31) // 32
+    return "reduce_taps" if (1 < taps <= 32 and tblocks >= 256) else "reduce"
+
+
+def wgrad_plan(bits16, dil, c1, c2, cout, n, d, h, w, mode, ncu):
+    """What brats_conv3d_wgrad does with a 3x3x3 layer: dict(kernel, cof, cif, nlane, nsplit, reduce, ws_bytes, memset)."""
+    c2 = max(c2, 0)
+    ntiles = wgrad_ntiles(n, d, h, w)
+    cof, cif = wgrad_tiles(not bits16, c1, c2, cout)
+    cot = ceil_div(cout, 16 * cof)
+    cit = ceil_div(c1, 16 * cif) + (ceil_div(c2, 16 * cif) if c2 > 0 else 0)
+    nl = wgrad_nlane(ntiles)
+    ns_tap = nl * wgrad_g8(ntiles, cot, cit)
+    at = wgrad_alltaps_ok(mode, bits16, dil, c1, c2, cout, ntiles, ncu)
+    at1 = wgrad_alltaps_ok(mode, bits16, 1, c1, c2, cout, ntiles, ncu)  # (the workspace size does not know the dilation)
+    ns_ws = max(ns_tap, nl * at1[0]) if at1 else ns_tap
+    plan = dict(ntiles=ntiles, cof=cof, cif=cif, nlane=nl, reduce=wgrad_reduce_kind(cout, c1 + c2, 27),
+                ws_bytes=ns_ws * 27 * cout * (c1 + c2) * 4)
+    if at:
+        plan.update(kernel=at[1], nsplit=nl * at[0], memset=False)
+    else:
+        plan.update(kernel=f"tapplane<{'16' if bits16 else 'f32'}, {dil}, {cof}, {cif}>", nsplit=ns_tap,
+                    memset=bool((c1 + c2) % 16 or cout % 16))
+    return plan
+
+
+def wgrad_shift_plan(bits16, ksize, cin, cout, n, d, h, w):
+    """brats_conv3d_wgrad_shift (wgrad_shift_geometry): one workgroup per tap, so the 512-workgroup rule divides by ntaps."""
+    ntiles = wgrad_ntiles(n, d, h, w)
+    ntaps = 27 if ksize == 3 else 1
+    cof, cif = wgrad_tiles(not bits16, cin, 0, cout)
+    cot, cit = ceil_div(cout, 16 * cof), ceil_div(cin, 16 * cif)
+    nl = wgrad_nlane(ntiles)
+    ns = nl * wgrad_g8(ntiles, cot, cit, ntaps)
+    return dict(ntiles=ntiles, cof=cof, cif=cif, nlane=nl, nsplit=ns, reduce=wgrad_reduce_kind(cout, cin, ntaps),
+                kernel=f"shift<{'16' if bits16 else 'f32'}, {cof}, {cif}>", memset=bool(cin % 16 or cout % 16),
+                ws_bytes=ns * ntaps * cout * cin * 4)
+
+
+def smallest_alltaps_volume(c1, c2, cout, ncu, ragged=False):
+    """(n, (d, h, w)) with the fewest voxels at which the mirror says the all-taps form is taken on a device of `ncu` CUs."""
+    if ragged:
+        ds, hs, ws = (6, 10, 18, 34), (6, 14, 30, 62), (18, 34, 66)
+    else:
+        ds, hs, ws = (4, 8, 16, 32), (4, 8, 16, 32, 64), (16, 32, 64)
+    best = None
+    for n in (1, 2, 3):
+        for d in ds:
+            for h in hs:
+                for w in ws:
+                    if wgrad_alltaps_ok(1, True, 1, c1, c2, cout, wgrad_ntiles(n, d, h, w), ncu):
+                        key = (n * d * h * w, n, d, h, w)
+                        if best is None or key < best:
+                            best = key
+    assert best is not None, f"no candidate volume selects the all-taps form for {c1}+{c2} -> {cout} at {ncu} CUs"
+    return best[1], best[2:]
+
+
+# ------------------------------------------------------------------------------------------ shared, unchanged references
+@functools.lru_cache(maxsize=None)
+def wgrad_case(c1, c2, cout, n, size, dil=1, k=3, seed=0):
+    """(x, x2 | None, dy, dW float64, dbias float64) of one weight-gradient problem; computed once, shared, never modified."""
+    x = int_tensor((n, *size, c1), 1000 + seed)
+    x2 = int_tensor((n, *size, c2), 2000 + seed) if c2 else None
+    dy = int_tensor((n, *size, cout), 3000 + seed)
+    require_wgrad_exact(x, dy, x2)
+    return x, x2, dy, wgrad_ref(x, dy, dil, k, x2), dbias_ref(dy)
+
+
+@functools.lru_cache(maxsize=None)
+def fwd_case(c1, c2, cout, n, size, dil=1, k=3, seed=0, thin=False, with_bias=True, real_cin=None):
+    """(x, x2 | None, w, bias | None, y float64) of one forward problem.  thin: x at stats_density(), w in {-1, 0, 1}, so that
+    the sum of y^2 meets its bound.  real_cin: channels [real_cin, c1) of x and w are zero (the padded first layer)."""
+    vox = size[0] * size[1] * size[2]
+    dens = stats_density(c1 + c2, vox) if thin else 1.0
+    x = int_tensor((n, *size, c1), 4000 + seed, dens)
+    x2 = int_tensor((n, *size, c2), 5000 + seed, dens) if c2 else None
+    w = int_tensor((cout, c1 + c2, k, k, k), 6000 + seed, 1.0, 1 if thin else 2)
+    if real_cin is not None:
+        x[..., real_cin:] = 0
+        w[:, real_cin:] = 0
+    bias = int_tensor((cout,), 7000 + seed) if with_bias else None
+    require_fwd_exact(x, w, bias, x2)
+    return x, x2, w, bias, fwd_ref(x, w, bias, dil, x2)
+
+
+@functools.lru_cache(maxsize=None)
+def dgrad_case(cin, cout, n, size, dil=1, k=3, seed=0):
+    """(dy, w, dx float64) of one input-gradient problem."""
+    dy = int_tensor((n, *size, cout), 8000 + seed)
+    w = int_tensor((cout, cin, k, k, k), 9000 + seed)
+    require_fwd_exact(dy, w.transpose(0, 1))
+    return dy, w, dgrad_ref(dy, w, dil)
