@@ -1,4 +1,4 @@
-// Segmentation heads: 1x1x1 conv C -> K (K <= 4) + bias, then trilinear (align_corners) up-sampling to
+// Segmentation heads: 1x1x1 conv C -> K (K <= 16) + bias, then trilinear (align_corners) up-sampling to
 // full resolution, emitted as NCDHW f32 logits for the PyTorch Dice loss (learning/engine.py:312-333).
 // Reference: conv1x1 networks/equiunet2020.py:37-41 (outconv :441, deep heads :443-458).
 // Pure HBM-bound kernels (AI <= 3 FLOP/B): no MFMA on purpose.
@@ -12,7 +12,8 @@ static inline int sgrid(size_t total, int block) {
   size_t b = (total + block - 1) / block;
   return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
-constexpr int HEAD_KMAX = 4;
+constexpr int HEAD_KMAX = 4;    // class tile of the K <= 4 instantiations (the three-class BraTS heads), and the bound of the fused forms
+constexpr int HEAD_KWIDE = 16;  // most classes brats_head_fwd / brats_head_bwd take: wider class tiles (KT) are instantiations of their own
 
 // thread = (voxel, 16-byte channel vector): fully coalesced loads; the K partial dot products of a voxel's
 // C/VW threads are summed through LDS (a thread-per-voxel loop over channels ran at 2.3 TB/s)
@@ -27,13 +28,15 @@ DEVI float head_pre(float x, float sc, float sh, const HeadPre& pre) {
   const float p = x * sc + sh;
   return p > 0.f ? p : p * pre.nslope;
 }
-template <typename T, bool PRE = false>
+// KT: the class tile (4, 8, 16 >= K).  A voxel's channel vector stays in registers while its KT partial dot products are formed; the
+// activations are read once whatever K is.
+template <typename T, bool PRE = false, int KT = HEAD_KMAX>
 __global__ void head_conv_kernel(const T* __restrict__ x, int xpitch, const float* __restrict__ w, const float* __restrict__ b,
                                  float* __restrict__ low, int C, int K, size_t voxels, HeadPre pre) {
   constexpr int VW = 16 / sizeof(T);
   extern __shared__ float sm[];
   float* ws = sm;                       // [K][C]
-  float* red = sm + HEAD_KMAX * C;      // [256][HEAD_KMAX]
+  float* red = sm + KT * C;             // [256][KT]
   for (int i = threadIdx.x; i < K * C; i += blockDim.x) ws[i] = w[i];
   __syncthreads();
   const int n = blockIdx.y;
@@ -51,7 +54,9 @@ __global__ void head_conv_kernel(const T* __restrict__ x, int xpitch, const floa
   }
   for (size_t vbase = (size_t)blockIdx.x * vl_n; vbase < voxels; vbase += (size_t)gridDim.x * vl_n) {
     const size_t v = vbase + myvl;
-    float acc[HEAD_KMAX] = {0.f, 0.f, 0.f, 0.f};
+    float acc[KT];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) acc[k] = 0.f;
     if (myvl < vl_n && v < voxels) {
       float a[VW];
       Vec<T, VW>::load(xb + v * xpitch + c0, a);
@@ -60,20 +65,20 @@ __global__ void head_conv_kernel(const T* __restrict__ x, int xpitch, const floa
         for (int j = 0; j < VW; ++j) a[j] = to_f<T>(from_f<T>(head_pre(a[j], psc[j], psh[j], pre)));
       }
 #pragma unroll
-      for (int k = 0; k < HEAD_KMAX; ++k)
+      for (int k = 0; k < KT; ++k)
         if (k < K) {
 #pragma unroll
           for (int j = 0; j < VW; ++j) acc[k] += a[j] * ws[k * C + c0 + j];
         }
     }
 #pragma unroll
-    for (int k = 0; k < HEAD_KMAX; ++k) red[threadIdx.x * HEAD_KMAX + k] = acc[k];
+    for (int k = 0; k < KT; ++k) red[threadIdx.x * KT + k] = acc[k];
     __syncthreads();
     for (int i = threadIdx.x; i < vl_n * K; i += blockDim.x) {
       const int vl = i / K, k = i % K;
       if (vbase + vl < voxels) {
         float t = b ? b[k] : 0.f;
-        for (int c = 0; c < cv; ++c) t += red[(vl * cv + c) * HEAD_KMAX + k];
+        for (int c = 0; c < cv; ++c) t += red[(vl * cv + c) * KT + k];
         low[((size_t)n * K + k) * voxels + vbase + vl] = t;
       }
     }
@@ -86,7 +91,9 @@ __global__ void head_conv_kernel(const T* __restrict__ x, int xpitch, const floa
 // channels; the B operand of lane (voxel l & 15, q = l >> 4) is one 16-byte load of 8 consecutive channels, so a wave
 // instruction reads 1 KB of contiguous activations, and nothing goes through LDS or a cross-lane reduction (the first form
 // read its weights from LDS per element and reduced six channel-vector threads per voxel through LDS: 2.7 TB/s).
-template <bool PRE = false>
+// WIDE (4 < K <= 16): the same MFMAs -- lane (v, q) feeds class row v of A and the accumulator already holds all 16 rows -- and
+// every lane stores its rows 4q .. 4q + 3 (below K) instead of the lanes q = 0 alone: one sweep over the activations for any K.
+template <bool PRE = false, bool WIDE = false>
 __global__ void __launch_bounds__(256) head_conv_mfma_kernel(const bf16_t* __restrict__ x, int xpitch, const float* __restrict__ w,
                                                              const float* __restrict__ b, float* __restrict__ low, int C, int K,
                                                              size_t voxels, HeadPre pre) {
@@ -154,9 +161,10 @@ __global__ void __launch_bounds__(256) head_conv_mfma_kernel(const bf16_t* __res
 #pragma unroll
     for (int part = 0; part < 3; ++part) wa[part][s] = __builtin_bit_cast(bf16x8, t[part]);
   }
+  const int r0 = WIDE ? 4 * q : 0;  // the lane's first class row
   float bias[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) bias[r] = (b && r < K) ? b[r] : 0.f;
+  for (int r = 0; r < 4; ++r) bias[r] = (b && r0 + r < K) ? b[r0 + r] : 0.f;
   const bf16_t* xb = x + (size_t)n * voxels * xpitch;
   // (the range ends with the last voxel's C channels: a channel-slice view of a wider buffer must not be read past its slice)
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)xb, (short)0, (int)((voxels - 1) * xpitch * 2 + C * 2), 0x00020000);
@@ -188,13 +196,13 @@ __global__ void __launch_bounds__(256) head_conv_mfma_kernel(const bf16_t* __res
         acc = MFMA16_16x16x32(wa[part][1], xb1[i], acc);
       }
       const size_t vv = v0 + 16 * i + v;
-      if (q == 0 && vv < voxels) {
+      if ((WIDE || q == 0) && vv < voxels) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #ifdef BRATS_FP16
-          if (r < K) lowp[(size_t)r * voxels + vv] = acc[r] * winv + bias[r];
+          if (r0 + r < K) lowp[(size_t)(r0 + r) * voxels + vv] = acc[r] * winv + bias[r];
 #else
-          if (r < K) lowp[(size_t)r * voxels + vv] = acc[r] + bias[r];
+          if (r0 + r < K) lowp[(size_t)(r0 + r) * voxels + vv] = acc[r] + bias[r];
 #endif
       }
     }
@@ -285,15 +293,32 @@ static int head_conv_launch(const void* x, int xpitch, const float* w, const flo
   const int cvh = C / vw, vlh = 256 / cvh;
   if (cvh > 256) BRATS_FAIL(BRATS_E_UNSUPPORTED, "head_fwd: C too large");
   dim3 grid(sgrid((vox + vlh - 1) / vlh, 1), N);
-  const size_t ldsh = (size_t)(HEAD_KMAX * C + 256 * HEAD_KMAX) * sizeof(float);
-  if (dtype == BRATS_BF16 && C <= 64 && (double)vox * xpitch * 2 < 2147483648.0) {
+  const int kt = K <= HEAD_KMAX ? HEAD_KMAX : (K <= 8 ? 8 : HEAD_KWIDE);  // the class tile of the plain kernel
+  const size_t ldsh = (size_t)(kt * C + 256 * kt) * sizeof(float);
+  const bool mfma = dtype == BRATS_BF16 && C <= 64 && (double)vox * xpitch * 2 < 2147483648.0;
+  if (!mfma && ldsh > 64 * 1024) BRATS_FAIL(BRATS_E_UNSUPPORTED, "head_fwd: K=%d x C=%d weights do not fit the LDS", K, C);
+  if (mfma) {
     const size_t waves = (vox + 63) / 64;
     const unsigned gx = (unsigned)(waves / 4 < 1 ? 1 : (waves / 4 > 8192 ? 8192 : waves / 4));
-    hipLaunchKernelGGL(head_conv_mfma_kernel<PRE>, dim3(gx, N), dim3(256), 0, st, (const bf16_t*)x, xpitch, w, b, low, C, K, vox, pre);
-  } else if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL((head_conv_kernel<bf16_t, PRE>), grid, dim3(256), ldsh, st, (const bf16_t*)x, xpitch, w, b, low, C, K, vox, pre);
-  else
-    hipLaunchKernelGGL((head_conv_kernel<float, PRE>), grid, dim3(256), ldsh, st, (const float*)x, xpitch, w, b, low, C, K, vox, pre);
+    if (K <= HEAD_KMAX)
+      hipLaunchKernelGGL(head_conv_mfma_kernel<PRE>, dim3(gx, N), dim3(256), 0, st, (const bf16_t*)x, xpitch, w, b, low, C, K, vox, pre);
+    else if constexpr (!PRE)
+      hipLaunchKernelGGL((head_conv_mfma_kernel<false, true>), dim3(gx, N), dim3(256), 0, st, (const bf16_t*)x, xpitch, w, b, low, C, K, vox, pre);
+  } else if (K <= HEAD_KMAX) {
+    if (dtype == BRATS_BF16)
+      hipLaunchKernelGGL((head_conv_kernel<bf16_t, PRE>), grid, dim3(256), ldsh, st, (const bf16_t*)x, xpitch, w, b, low, C, K, vox, pre);
+    else
+      hipLaunchKernelGGL((head_conv_kernel<float, PRE>), grid, dim3(256), ldsh, st, (const float*)x, xpitch, w, b, low, C, K, vox, pre);
+  } else if constexpr (!PRE) {  // (the fused forms stop at K = 4: their entry points refuse more)
+    if (dtype == BRATS_BF16 && kt == 8)
+      hipLaunchKernelGGL((head_conv_kernel<bf16_t, false, 8>), grid, dim3(256), ldsh, st, (const bf16_t*)x, xpitch, w, b, low, C, K, vox, pre);
+    else if (dtype == BRATS_BF16)
+      hipLaunchKernelGGL((head_conv_kernel<bf16_t, false, HEAD_KWIDE>), grid, dim3(256), ldsh, st, (const bf16_t*)x, xpitch, w, b, low, C, K, vox, pre);
+    else if (kt == 8)
+      hipLaunchKernelGGL((head_conv_kernel<float, false, 8>), grid, dim3(256), ldsh, st, (const float*)x, xpitch, w, b, low, C, K, vox, pre);
+    else
+      hipLaunchKernelGGL((head_conv_kernel<float, false, HEAD_KWIDE>), grid, dim3(256), ldsh, st, (const float*)x, xpitch, w, b, low, C, K, vox, pre);
+  }
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -324,8 +349,8 @@ extern "C" int BRATS_API(brats_evonorm_head_fwd)(const void* y, int ypitch, cons
 extern "C" int BRATS_API(brats_head_fwd)(const void* x, int xpitch, const float* w, const float* b, float* lowres, float* out,
                               int dtype, int N, int C, int K, int D, int H, int W, int scale, brats_stream_t s) {
   const int vw = dtype == BRATS_BF16 ? 8 : 4;
-  if (!x || !w || !out || K < 1 || K > HEAD_KMAX || C % vw || xpitch % vw || scale < 1)
-    BRATS_FAIL(BRATS_E_ARG, "head_fwd: bad argument (K<=4, C multiple of %d)", vw);
+  if (!x || !w || !out || K < 1 || K > HEAD_KWIDE || C % vw || xpitch % vw || scale < 1)
+    BRATS_FAIL(BRATS_E_ARG, "head_fwd: bad argument (K<=16, C multiple of %d)", vw);
   if (scale > 1 && !lowres) BRATS_FAIL(BRATS_E_ARG, "head_fwd: lowres workspace required when scale > 1");
   hipStream_t st = (hipStream_t)s;
   const size_t vox = (size_t)D * H * W;
@@ -345,11 +370,13 @@ extern "C" int BRATS_API(brats_head_fwd)(const void* x, int xpitch, const float*
 }
 
 // dx[v][c] = sum_k dlow[k][v]*w[k][c];  dw[k][c] += sum_v dlow[k][v]*x[v][c];  db[k] += sum_v dlow[k][v]
-template <typename T>
-__global__ void __launch_bounds__(256) head_bwd_kernel(const T* __restrict__ x, int xpitch, const float* __restrict__ w, const float* __restrict__ dlow,
+// KT: the class tile (4, 8, 16 >= K); VW: channels per thread -- 16 bytes, but 8 bytes of a 16-bit tensor at KT = 8 and 16, where
+// the thread's KT x VW weights and as many dw accumulators have to stay in registers (KT = 16: 2 x 64 instead of 2 x 128).  The K logit
+// gradients of a voxel are K coalesced plane loads; x is read and dx written once whatever K is.
+template <typename T, int VW = 16 / sizeof(T), int KT = HEAD_KMAX>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) head_bwd_kernel(const T* __restrict__ x, int xpitch, const float* __restrict__ w, const float* __restrict__ dlow,
                                 T* __restrict__ dx, int dxpitch, float* __restrict__ dw /* per-block partials */, int C, int K,
                                 size_t voxels) {
-  constexpr int VW = 16 / sizeof(T);
   extern __shared__ float sm[];
   float* ws = sm;  // [K][C]
   for (int i = threadIdx.x; i < K * C; i += blockDim.x) ws[i] = w[i];
@@ -357,10 +384,10 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const T* __restrict__ x, 
   const int n = blockIdx.y;
   const int cv = C / VW, vl_n = blockDim.x / cv;
   const int mycv = threadIdx.x % cv, myvl = threadIdx.x / cv, c0 = mycv * VW;
-  float aw[HEAD_KMAX][VW];
-  float ab[HEAD_KMAX];
+  float aw[KT][VW];
+  float ab[KT];
 #pragma unroll
-  for (int k = 0; k < HEAD_KMAX; ++k) {
+  for (int k = 0; k < KT; ++k) {
     ab[k] = 0.f;
 #pragma unroll
     for (int j = 0; j < VW; ++j) aw[k][j] = 0.f;
@@ -370,9 +397,9 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const T* __restrict__ x, 
     T* dxb = dx ? dx + (size_t)n * voxels * dxpitch + c0 : nullptr;
     // the thread's channel vector is fixed: its K x VW weights live in registers (read from LDS per element the pass was
     // LDS-bound), two voxels are in flight per iteration
-    float wr[HEAD_KMAX][VW];
+    float wr[KT][VW];
 #pragma unroll
-    for (int k = 0; k < HEAD_KMAX; ++k)
+    for (int k = 0; k < KT; ++k)
 #pragma unroll
       for (int j = 0; j < VW; ++j) wr[k][j] = k < K ? ws[k * C + c0 + j] : 0.f;
     const float* dl = dlow + (size_t)n * K * voxels;
@@ -380,23 +407,39 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const T* __restrict__ x, 
 #pragma unroll
       for (int j = 0; j < VW; ++j) o[j] = 0.f;
 #pragma unroll
-      for (int k = 0; k < HEAD_KMAX; ++k) {
+      for (int k = 0; k < KT; ++k) {
         ab[k] += g[k];
+        if constexpr (KT > HEAD_KMAX) {
+          // 2 x KT x VW multiply-adds per voxel and thread: as separate multiplies and adds (this library's -ffp-contract=off)
+          // the wide tiles are VALU-bound (K = 16 at 2 x 48 x 128^3: 0.58 ms against 0.24 ms of bytes), so they use packed FMAs
+          typedef float f32x2 __attribute__((ext_vector_type(2)));
+          const f32x2 gg = {g[k], g[k]};
 #pragma unroll
-        for (int j = 0; j < VW; ++j) {
-          aw[k][j] += g[k] * a[j];
-          o[j] += g[k] * wr[k][j];
+          for (int j = 0; j < VW; j += 2) {
+            const f32x2 av = {a[j], a[j + 1]}, wv = {wr[k][j], wr[k][j + 1]};
+            f32x2 awv = {aw[k][j], aw[k][j + 1]}, ov = {o[j], o[j + 1]};
+            awv = __builtin_elementwise_fma(gg, av, awv);
+            ov = __builtin_elementwise_fma(gg, wv, ov);
+            aw[k][j] = awv[0]; aw[k][j + 1] = awv[1];
+            o[j] = ov[0]; o[j + 1] = ov[1];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < VW; ++j) {
+            aw[k][j] += g[k] * a[j];
+            o[j] += g[k] * wr[k][j];
+          }
         }
       }
     };
     const size_t stride = (size_t)gridDim.x * vl_n;
     size_t v = (size_t)blockIdx.x * vl_n + myvl;
-    for (; v + stride < voxels; v += 2 * stride) {
-      float a0[VW], a1[VW], o0[VW], o1[VW], g0[HEAD_KMAX], g1[HEAD_KMAX];
+    for (; KT < HEAD_KWIDE && v + stride < voxels; v += 2 * stride) {  // (KT = 16: its own loop below)
+      float a0[VW], a1[VW], o0[VW], o1[VW], g0[KT], g1[KT];
       Vec<T, VW>::load(xb + v * xpitch, a0);
       Vec<T, VW>::load(xb + (v + stride) * xpitch, a1);
 #pragma unroll
-      for (int k = 0; k < HEAD_KMAX; ++k) {
+      for (int k = 0; k < KT; ++k) {
         g0[k] = k < K ? dl[(size_t)k * voxels + v] : 0.f;
         g1[k] = k < K ? dl[(size_t)k * voxels + v + stride] : 0.f;
       }
@@ -407,36 +450,79 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const T* __restrict__ x, 
         Vec<T, VW>::store(dxb + (v + stride) * dxpitch, o1);
       }
     }
-    if (v < voxels) {
-      float a0[VW], o0[VW], g0[HEAD_KMAX];
+    auto one = [&](size_t v) {
+      float a0[VW], o0[VW], g0[KT];
       Vec<T, VW>::load(xb + v * xpitch, a0);
 #pragma unroll
-      for (int k = 0; k < HEAD_KMAX; ++k) g0[k] = k < K ? dl[(size_t)k * voxels + v] : 0.f;
+      for (int k = 0; k < KT; ++k) g0[k] = k < K ? dl[(size_t)k * voxels + v] : 0.f;
       body(a0, g0, o0);
       if (dxb) Vec<T, VW>::store(dxb + v * dxpitch, o0);
-    }
-  }
-  float* scr = sm + K * C;  // [vl_n][K][C] + [vl_n][K]
-  __syncthreads();
-  if (myvl < vl_n) {
-    for (int k = 0; k < K; ++k) {
+    };
+    if constexpr (KT < HEAD_KWIDE) {
+      if (v < voxels) one(v);
+    } else {
+      // the next voxel's channel vector and KT gradients are loaded before this one's FMAs: with two waves per SIMD, one voxel
+      // per thread in flight left the pass latency-bound (1.65 TB/s at 2 x 48 x 128^3, K = 16)
+      // (the K plane bases are uniform -- scalar registers -- and the voxel's byte offset is one 32-bit register: the host
+      // side checks voxels < 2^30)
+      // Classes k >= K re-read plane K - 1 (in bounds, no branch or select per load); their weights are 0 and their sums are
+      // never written out.
+      auto gload = [&](size_t vv, float* g) {
+        const uint32_t off = (uint32_t)vv * 4u;
 #pragma unroll
-      for (int j = 0; j < VW; ++j) scr[(myvl * K + k) * C + c0 + j] = aw[k][j];
-      if (mycv == 0) scr[vl_n * K * C + myvl * K + k] = ab[k];
+        for (int k = 0; k < KT; ++k) g[k] = *(const float*)((const char*)(dl + (size_t)(k < K ? k : K - 1) * voxels) + off);
+      };
+      float a0[VW], g0[KT];
+      if (v < voxels) {
+        Vec<T, VW>::load(xb + v * xpitch, a0);
+        gload(v, g0);
+      }
+      while (v < voxels) {
+        const size_t vn = v + stride;
+        float a1[VW], g1[KT], o0[VW];
+        if (vn < voxels) {
+          Vec<T, VW>::load(xb + vn * xpitch, a1);
+          gload(vn, g1);
+        }
+        body(a0, g0, o0);
+        if (dxb) Vec<T, VW>::store(dxb + v * dxpitch, o0);
+#pragma unroll
+        for (int j = 0; j < VW; ++j) a0[j] = a1[j];
+#pragma unroll
+        for (int k = 0; k < KT; ++k) g0[k] = g1[k];
+        v = vn;
+      }
     }
   }
-  __syncthreads();
-  // one partial vector [K*C + K] per block, added in block order afterwards (no float atomics)
+  // one partial vector [K*C + K] per block, added in block order afterwards (no float atomics).  The threads' sums meet in
+  // LDS four classes at a time -- scr [vl_n][4][C] + [vl_n][4] whatever K is -- and are added in voxel-lane order
+  float* scr = sm + K * C;
   float* part = dw + ((size_t)n * gridDim.x + blockIdx.x) * (K * C + K);
-  for (int i = threadIdx.x; i < K * C; i += blockDim.x) {
-    float t = 0.f;
-    for (int l = 0; l < vl_n; ++l) t += scr[l * K * C + i];
-    part[i] = t;
-  }
-  if ((int)threadIdx.x < K) {
-    float t = 0.f;
-    for (int l = 0; l < vl_n; ++l) t += scr[vl_n * K * C + l * K + threadIdx.x];
-    part[K * C + threadIdx.x] = t;
+#pragma unroll
+  for (int t0 = 0; t0 < KT; t0 += HEAD_KMAX) {
+    if (t0 >= K) break;  // (uniform)
+    const int kn = K - t0 < HEAD_KMAX ? K - t0 : HEAD_KMAX;
+    __syncthreads();
+    if (myvl < vl_n) {
+#pragma unroll
+      for (int kk = 0; kk < HEAD_KMAX; ++kk)
+        if (kk < kn) {
+#pragma unroll
+          for (int j = 0; j < VW; ++j) scr[(myvl * kn + kk) * C + c0 + j] = aw[t0 + kk][j];
+          if (mycv == 0) scr[vl_n * kn * C + myvl * kn + kk] = ab[t0 + kk];
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kn * C; i += blockDim.x) {
+      float t = 0.f;
+      for (int l = 0; l < vl_n; ++l) t += scr[l * kn * C + i];
+      part[t0 * C + i] = t;
+    }
+    if ((int)threadIdx.x < kn) {
+      float t = 0.f;
+      for (int l = 0; l < vl_n; ++l) t += scr[vl_n * kn * C + l * kn + threadIdx.x];
+      part[K * C + t0 + threadIdx.x] = t;
+    }
   }
 }
 
@@ -456,9 +542,9 @@ extern "C" int BRATS_API(brats_head_bwd)(const void* x, int xpitch, const float*
                               float* dw, float* db, int dtype, int N, int C, int K, int D, int H, int W, int scale,
                               brats_stream_t s) {
   const int vw = dtype == BRATS_BF16 ? 8 : 4;
-  if (!x || !w || !dout || !dw || !db || K < 1 || K > HEAD_KMAX || C % vw || xpitch % vw || (dx && dxpitch % vw) ||
+  if (!x || !w || !dout || !dw || !db || K < 1 || K > HEAD_KWIDE || C % vw || xpitch % vw || (dx && dxpitch % vw) ||
       C / vw > 128)
-    BRATS_FAIL(BRATS_E_ARG, "head_bwd: bad argument");
+    BRATS_FAIL(BRATS_E_ARG, "head_bwd: bad argument (K<=16)");
   if (!ws) BRATS_FAIL(BRATS_E_ARG, "head_bwd: workspace required");
   hipStream_t st = (hipStream_t)s;
   const size_t vox = (size_t)D * H * W, p = (size_t)N * K;
@@ -478,19 +564,28 @@ extern "C" int BRATS_API(brats_head_bwd)(const void* x, int xpitch, const float*
     }
     dlow = dl;
   }
-  const int cv = C / vw, vl = 256 / cv;
+  const int kt = K <= HEAD_KMAX ? HEAD_KMAX : (K <= 8 ? 8 : HEAD_KWIDE);  // the class tile
+  const int vwk = kt > HEAD_KMAX ? 4 : vw;                                // channels per thread (head_bwd_kernel)
+  const int cv = C / vwk, vl = 256 / cv;
   size_t gx = (vox + (size_t)vl * 16 - 1) / ((size_t)vl * 16);
   dim3 grid((unsigned)(gx < 1 ? 1 : (gx > HEAD_MAX_BLOCKS ? HEAD_MAX_BLOCKS : gx)), N);
-  const size_t lds = (size_t)(K * C + vl * K * C + vl * K) * sizeof(float);
+  const int kn = K < HEAD_KMAX ? K : HEAD_KMAX;
+  const size_t lds = (size_t)(K * C + vl * kn * C + vl * kn) * sizeof(float);
+  if (lds > 64 * 1024) BRATS_FAIL(BRATS_E_UNSUPPORTED, "head_bwd: K=%d x C=%d weights do not fit the LDS", K, C);
+  if (kt == HEAD_KWIDE && vox >= ((size_t)1 << 30)) BRATS_FAIL(BRATS_E_UNSUPPORTED, "head_bwd: K=%d needs fewer than 2^30 voxels per sample", K);
   float* part = ws + head_lerp_floats(N, K, D, H, W, scale);
-  float* tot = part + (size_t)N * HEAD_MAX_BLOCKS * (K * C + K);
-  if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(head_bwd_kernel<bf16_t>, grid, dim3(256), lds, st, (const bf16_t*)x, xpitch, w, dlow, (bf16_t*)dx,
-                       dxpitch, part, C, K, vox);
-  else
-    hipLaunchKernelGGL(head_bwd_kernel<float>, grid, dim3(256), lds, st, (const float*)x, xpitch, w, dlow, (float*)dx, dxpitch,
-                       part, C, K, vox);
-  (void)tot;
+#define HEAD_BWD_LAUNCH(T, VWK, KT)                                                                                              \
+  hipLaunchKernelGGL((head_bwd_kernel<T, VWK, KT>), grid, dim3(256), lds, st, (const T*)x, xpitch, w, dlow, (T*)dx, dxpitch, part, C, K, vox)
+  if (dtype == BRATS_BF16) {
+    if (kt == HEAD_KMAX) HEAD_BWD_LAUNCH(bf16_t, 8, HEAD_KMAX);
+    else if (kt == 8) HEAD_BWD_LAUNCH(bf16_t, 4, 8);
+    else HEAD_BWD_LAUNCH(bf16_t, 4, HEAD_KWIDE);
+  } else {
+    if (kt == HEAD_KMAX) HEAD_BWD_LAUNCH(float, 4, HEAD_KMAX);
+    else if (kt == 8) HEAD_BWD_LAUNCH(float, 4, 8);
+    else HEAD_BWD_LAUNCH(float, 4, HEAD_KWIDE);
+  }
+#undef HEAD_BWD_LAUNCH
   brats_ordered_sum2(part, dw, K * C, db, N * (int)grid.x, K * C + K, st);  // totals straight into dw [K][C] and db [K]
   BRATS_CHECK_LAUNCH();
   return 0;

@@ -283,6 +283,10 @@ class Evaluator:
     pad to k -> [TTA x] (sliding window | whole volume) -> on-GPU mean of sigmoid -> threshold ->
     background removal -> (labels) -> crop.
 
+    This is the three-channel BraTS chain: the post-processing reads the channels as TC / WT / ET (labels 1 / 2 / 4, cleaning,
+    closest-label replacement), whatever the models could take.  The networks themselves run with 1 to 16 input channels and up to 16 classes; for other label sets use
+    inferers.sliding_window_inference / tta_predict on the model and post-process the probabilities yourself.
+
     ``use_graph`` (default: only with a sliding window, whose patch shape is fixed): the patch step of each model is
     captured into a hipGraph once and replayed; the graphs follow the models' weights (GraphedPredictor re-captures when
     a parameter's address / version or ops' packed-weight generation changed).  Whole-volume evaluation

@@ -121,12 +121,28 @@ class _PackedWeightsModule(nn.Module):
             return (ops.X3F, None) if self.precision == "x3fwd" else (None, ops.X3F)
         return None, None
 
+    MAX_INPLANES = MAX_CLASSES = 16
+
+    def _check_shape_limits(self, inplanes, num_classes, features, width_multiple):
+        """What the kernels cover of the reference's constructor arguments: the layout conversion pads the input to at most 16
+        channels, brats_head_fwd / brats_head_bwd take at most 16 classes, the convolutions whole channel vectors."""
+        if int(inplanes) != inplanes or int(num_classes) != num_classes or inplanes < 1 or num_classes < 1:
+            raise ValueError(f"{self.name}: inplanes and num_classes must be positive integers (got {inplanes!r}, {num_classes!r})")
+        if inplanes > self.MAX_INPLANES:
+            raise NotImplementedError(f"{self.name}: the input layer is built for inplanes <= {self.MAX_INPLANES} (got {inplanes})")
+        if num_classes > self.MAX_CLASSES:
+            raise NotImplementedError(f"{self.name}: the head kernels are built for num_classes <= {self.MAX_CLASSES} (got {num_classes})")
+        if any(c % width_multiple for c in features):
+            raise NotImplementedError(f"{self.name}: the convolution kernels need widths that are multiples of {width_multiple} "
+                                      f"(got {list(features)})")
+        self.inplanes = int(inplanes)
+
     def _run(self, fn, x):
         """forward(x) of both networks; fn: the network's autograd Function."""
         if not x.is_cuda:
             raise BratsHipError(f"brats21_amd.{self.name} runs on the GPU only (no CPU fallback){self._cpu_hint}")
-        if x.dim() != 5 or x.shape[1] != 4 or any(s % 8 for s in x.shape[2:]):
-            raise ValueError("expected input [N, 4, D, H, W] with D, H, W divisible by 8")
+        if x.dim() != 5 or x.shape[1] != self.inplanes or any(s % 8 for s in x.shape[2:]):
+            raise ValueError(f"expected input [N, {self.inplanes}, D, H, W] with D, H, W divisible by 8")
         self._fwd_grad = torch.is_grad_enabled()  # (inside autograd.Function.forward grad mode is always off)
         self._weights_may_have_changed()
         if self.training and self.pack_plan and torch.is_grad_enabled():
@@ -243,6 +259,13 @@ class _Ctx:
 
 
 # ------------------------------------------------------------------------------------------ autograd Function scoping
+def input_cpad(inplanes, dtype):
+    """Channels of the NDHWC network input: inplanes zero-padded to what the first convolution has a channel chunk for -- 8 or 16
+    in the 16-bit and split-precision modes, 4, 8 or 16 in exact f32.  (4 modalities: 8 / 4, one 16-byte vector per voxel.)"""
+    cands = (8, 16) if (ops.is16(dtype) or ops.x3_active()) else (4, 8, 16)
+    return next(c for c in cands if c >= inplanes)
+
+
 def _fn_forward(program, ctx, model, x, dtype, params):
     """forward() of a network's autograd Function around its forward program(ctx, cx, x0) -> tuple of logits."""
     # training: the module packed all layers' weights up front (ops.plan_for); pack_weights() then returns views
@@ -252,7 +275,8 @@ def _fn_forward(program, ctx, model, x, dtype, params):
     with ops.use_plan(ctx.plan), ops.split_precision(ctx.x3[0]):
         ctx.cx = cx = _Ctx(model, dtype, will_bwd=any(ctx.needs_input_grad) and model._fwd_grad)  # (needs_input_grad ignores no_grad)
         cx.start_dropout(x.device)
-        x0 = ops.ncdhw_to_ndhwc(x, dtype, cpad=8 if (ops.is16(dtype) or ops.x3_active()) else 4)
+        x0 = ops.ncdhw_to_ndhwc(x, dtype, cpad=input_cpad(x.shape[1], dtype))
+        x0._net_input = True  # (un-normalised: never an e4m3 operand, whatever its padded width)
         if ops.x3_mode() == ops.X3F:
             # fp16 pairs overflow at |x| >= 65504 (hi = inf, lo = NaN: silently NaN logits).  Every other convolution
             # input is a normalised activation; the network INPUT is whatever the caller passes (un-normalised volumes reach

@@ -156,7 +156,7 @@ def _head(cin, k):
 
 # ------------------------------------------------------------------------------------------ programs
 def _f8_ok(fp8, dtype, x, x2=None):
-    return (bool(fp8) and ops.is16(dtype) and x.shape[1] >= ops.F8_MIN_SIZE and
+    return (bool(fp8) and ops.is16(dtype) and not getattr(x, "_net_input", False) and x.shape[1] >= ops.F8_MIN_SIZE and
             ops.conv_f8_chunk(x.shape[-1], x2.shape[-1] if x2 is not None else 0) > 0)
 
 
@@ -528,8 +528,7 @@ class EquiUnet(_PackedWeightsModule):
             raise NotImplementedError(f"brats21_amd.EquiUnet implements --act relu|leakyrelu|elu|prelu|swish|mish (got {act!r})")
         if refinement:
             raise NotImplementedError("equiunet_ref (RefUnet) is outside the accelerated hot path")
-        if inplanes != 4 or num_classes > 4 or any(c % 8 for c in features):
-            raise NotImplementedError("EquiUnet kernels need inplanes=4, num_classes<=4, widths multiple of 8")
+        self._check_shape_limits(inplanes, num_classes, features, 8)
         print(f"EquiUnet features: {features}")
         self.deep_supervision = deep_supervision
         self.act = act

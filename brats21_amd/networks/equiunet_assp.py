@@ -76,7 +76,8 @@ def _conv_any_fwd(cx, conv, x, dil, want_stats, out=None):
     """conv (3x3x3 with dilation 1 | 2, or 1x1x1) + bias.  Returns (y, stats, saved) with what backward needs."""
     w = conv.weight
     cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
-    if cx.fp8 and k == 3 and x.shape[1] >= ops.F8_MIN_SIZE and ops.conv_f8_chunk(x.shape[-1]) > 0:
+    if (cx.fp8 and k == 3 and not getattr(x, "_net_input", False) and x.shape[1] >= ops.F8_MIN_SIZE
+            and ops.conv_f8_chunk(x.shape[-1]) > 0):
         wpk = ops.pack_weights_f8(w, PACK_FWD, cin_pad=x.shape[-1])
         y, stats = ops.conv3d_f8(x, wpk, cout, dil, bias=_flat(conv.bias), out=out, want_stats=want_stats,
                                  amax=getattr(x, "_amax", None))
@@ -407,8 +408,7 @@ class EquiUnetASSPEvo(_PackedWeightsModule):
         warnings.warn("norm layer and activation specified will not be used ! only EVO !!")
         if refinement:
             raise NotImplementedError("equiunet_assp_evo_ref raises AttributeError in the reference too (SURVEY App. B)")
-        if inplanes != 4 or num_classes > 4 or any(c % 16 for c in features):
-            raise NotImplementedError("EquiUnetASSPEvo needs inplanes=4, num_classes<=4, widths multiple of 16 (F10)")
+        self._check_shape_limits(inplanes, num_classes, features, 16)
         print(f"EquiUnetASSP features: {features}")
         self.deep_supervision = deep_supervision
         self.act = act.upper()

@@ -456,8 +456,9 @@ int brats_upsample_bwd(const void* dy, int dypitch, void* dx, int dxpitch, void*
  * 0 = the three passes through tmp everywhere.  Bit-identical results; returns the previous setting. */
 int brats_upsample_bwd_set_fused(int mode);
 
-/* ---- segmentation heads: 1x1x1 conv C -> K (K <= 4) + bias (conv1x1 equiunet2020.py:37-41,441)
- * followed by trilinear x`scale` up-sampling (deep heads :443-458); output NCDHW f32 logits. */
+/* ---- segmentation heads: 1x1x1 conv C -> K (1 <= K <= 16) + bias (conv1x1 equiunet2020.py:37-41,441)
+ * followed by trilinear x`scale` up-sampling (deep heads :443-458); output NCDHW f32 logits.  The activations are read once
+ * whatever K is.  (The fused forms brats_gn_head_fwd / brats_evonorm_head_fwd below stay at K <= 4.) */
 int brats_head_fwd(const void* x, int xpitch, const float* w /*[K][C]*/, const float* b, float* lowres /*[N][K][D][H][W] ws*/,
                    float* out /*[N][K][D*s][H*s][W*s]*/, int dtype, int N, int C, int K,
                    int D, int H, int W, int scale, brats_stream_t s);
@@ -473,7 +474,7 @@ int brats_gn_head_fwd(const void* y, int ypitch, const float* scale_shift, int a
  * gate1p from brats_evonorm_se_fwd called with out = NULL (statistics pass + gate only): the block's output is never stored. */
 int brats_evonorm_head_fwd(const void* y, int ypitch, const float* scale_shift, const float* w /*[K][C]*/, const float* b,
                            float* out, int dtype, int N, int C, int K, int voxels, brats_stream_t s);
-/* dout [N][K][Ds][Hs][Ws] f32 -> dx (NDHWC dtype, may be NULL), dw [K][C], db [K] (overwritten).
+/* dout [N][K][Ds][Hs][Ws] f32 -> dx (NDHWC dtype, may be NULL), dw [K][C], db [K] (overwritten); K <= 16.
  * ws: f32 workspace of brats_head_bwd_ws_bytes() (up-sampling adjoint temporaries + per-block partial sums of dw / db,
  * added in a fixed order: no float atomics). */
 size_t brats_head_bwd_ws_bytes(int N, int C, int K, int D, int H, int W, int scale);
