@@ -22,6 +22,8 @@ def get_model(args: argparse.Namespace) -> torch.nn.Module:
     }
     if args.model == "equiunet":
         return EquiUnet(**kwargs)
+    if args.model == "equiunet_ref":  # src/definer.py:145-147
+        return EquiUnet(**kwargs, refinement=True)
     if args.model in ("equiunet_assp_evo", "equiunet_assp_evocor"):
         from .networks.equiunet_assp import EquiUnetASSPEvo
 

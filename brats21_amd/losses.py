@@ -26,11 +26,20 @@ class DiceLoss(nn.Module):
         return (1.0 - (2.0 * inter + self.smooth_nr) / (denom + self.smooth_dr)).mean()
 
 
-def deep_supervision_loss(criterion, outputs, target):
-    """mean over [main] + deep heads of criterion(head, label) (learning/engine.py:322-330)."""
+def flatten_heads(outputs):
+    """Every tensor of a network output in order, as the reference's ``flatten`` does (learning/engine.py:322-330):
+    (out, [deep...]) -> [out, deep...]; with the refinement stage ([refined, out], [deep...]) -> [refined, out, deep...]."""
     if isinstance(outputs, (tuple, list)):
-        heads = [outputs[0]] + list(outputs[1])
-        return torch.stack([criterion(h, target) for h in heads]).mean(), outputs[0]
+        return [h for o in outputs for h in flatten_heads(o)]
+    return [outputs]
+
+
+def deep_supervision_loss(criterion, outputs, target):
+    """mean over [main] + deep heads of criterion(head, label) (learning/engine.py:322-330); returns (loss, first head) -- the
+    refined logits where the network has the refinement stage."""
+    if isinstance(outputs, (tuple, list)):
+        heads = flatten_heads(outputs)
+        return torch.stack([criterion(h, target) for h in heads]).mean(), heads[0]
     return criterion(outputs, target), outputs
 
 
@@ -84,7 +93,7 @@ class _FusedDiceFn(torch.autograd.Function):
 
 def fused_deep_supervision_dice(outputs, target, jaccard=False, eps=1e-5):
     """Same value and gradients as deep_supervision_loss(DiceLoss(jaccard), outputs, target), fused."""
-    heads = [outputs[0]] + list(outputs[1]) if isinstance(outputs, (tuple, list)) else [outputs]
+    heads = flatten_heads(outputs)
     return _FusedDiceFn.apply(target, jaccard, eps, *heads)
 
 
@@ -392,6 +401,6 @@ def deep_supervision_prepared_loss(criterion, outputs, target):
     gradients as deep_supervision_loss(criterion, outputs, target), bit for bit."""
     prepared = criterion.prepare(target)
     if isinstance(outputs, (tuple, list)):
-        heads = [outputs[0]] + list(outputs[1])
-        return torch.stack([criterion(h, prepared) for h in heads]).mean(), outputs[0]
+        heads = flatten_heads(outputs)
+        return torch.stack([criterion(h, prepared) for h in heads]).mean(), heads[0]
     return criterion(outputs, prepared), outputs

@@ -143,11 +143,18 @@ class _PackedWeightsModule(nn.Module):
             raise BratsHipError(f"brats21_amd.{self.name} runs on the GPU only (no CPU fallback){self._cpu_hint}")
         if x.dim() != 5 or x.shape[1] != self.inplanes or any(s % 8 for s in x.shape[2:]):
             raise ValueError(f"expected input [N, {self.inplanes}, D, H, W] with D, H, W divisible by 8")
+        refinement = getattr(self, "refinement", False)
+        if refinement and any(s % 16 for s in x.shape[2:]):  # (four pooled levels; the reference fails in torch.cat there)
+            raise ValueError(f"refinement=True: expected input [N, {self.inplanes}, D, H, W] with D, H, W divisible by 16")
+        if refinement and self.conv_fp8:
+            raise NotImplementedError("refinement=True with the e4m3 convolution path (conv_fp8) is not implemented")
         self._fwd_grad = torch.is_grad_enabled()  # (inside autograd.Function.forward grad mode is always off)
         self._weights_may_have_changed()
         if self.training and self.pack_plan and torch.is_grad_enabled():
             ops.plan_for(self, x.device)  # all layers' weights (forward + dgrad layouts) packed by one launch
         outs = fn.apply(self, x.float(), self._dtype(), *self.parameters())
+        if refinement:  # networks/equiunet2020.py:490-498: the first element is the list [refined, out]
+            return ([outs[0], outs[1]], list(outs[2:])) if self.deep_supervision else [outs[0], outs[1]]
         if self.deep_supervision:
             return outs[0], list(outs[1:])
         return outs[0]

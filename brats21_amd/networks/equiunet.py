@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import PACK_DGRAD, PACK_FWD, BratsHipError
-from ._program import _PackedWeightsModule, _fn_backward, _fn_forward, _heads_bwd, _inherit_amax
+from ._program import _PackedWeightsModule, _fn_backward, _fn_forward, _heads_bwd, _inherit_amax, input_cpad
 
 
 # ------------------------------------------------------------------------------------------ parameter holders
@@ -148,6 +148,21 @@ class UBlock(nn.Module):
         super().__init__()
         self.ConvBnRelu1 = ConvBnRelu(inplanes, midplanes, dilation[0], norm, act)
         self.ConvBnRelu2 = ConvBnRelu(midplanes, outplanes, dilation[1], norm, act)
+
+
+class RefUnet(nn.Module):
+    """The refinement stage of ``--model equiunet_ref`` (networks/equiunet2020.py:252-310): a five-level U-Net of ConvBnRelu units
+    at one width between a num_classes -> width convolution (bias, no norm) and a width -> num_classes convolution (bias) whose
+    output is added onto the logits.  Parameter container only -- the programs are _ref_fwd / _ref_bwd below."""
+
+    def __init__(self, in_ch, inc_ch, norm="group", act="relu"):
+        super().__init__()
+        self.conv0 = _ConvParams(in_ch, inc_ch, 3, bias=True)
+        for name in ("hx1", "hx2", "hx3", "hx4", "hx5"):
+            setattr(self, name, ConvBnRelu(inc_ch, inc_ch, 1, norm, act))
+        for name in ("d4", "d3", "d2", "d1"):
+            setattr(self, name, ConvBnRelu(inc_ch * 2, inc_ch, 1, norm, act))
+        self.conv_d0 = _ConvParams(inc_ch, in_ch, 3, bias=True)
 
 
 def _head(cin, k):
@@ -403,6 +418,93 @@ def _cgr_bwd(cx, unit, dz, *, need_dx=True, head=None, pool=None, bst=None):
     return dx[..., :c1], dx[..., c1:]
 
 
+def _level_bwd(cx, unit, down, d_pooled, d_skip, need_dx=True, bst=None):
+    """Backward of the last layer of an encoder level: its output gradient = d_skip + max-pool backward(d_pooled)."""
+    idx = getattr(down, "_pool_argmax", None)
+    kact, slope_t = _unit_act(unit, cx.act)
+    if (idx is not None and cx.m.fold_pool_bwd and cx.drop is None and not unit.batch_norm and slope_t is None
+            and kact in ("relu", "leakyrelu")):
+        return _cgr_bwd(cx, unit, None, need_dx=need_dx, pool=(d_skip, d_pooled, idx), bst=bst)
+    return _cgr_bwd(cx, unit, ops.maxpool2_bwd(down, d_pooled, dx_skip=d_skip), need_dx=need_dx, bst=bst)
+
+
+# ------------------------------------------------------------------------------------------ refinement stage (RefUnet)
+def _ref_cpad(k):
+    """Channels of the zero-padded NDHWC form of a [N, k, D, H, W] gradient that the weight-gradient / dgrad kernels take as dy."""
+    return 8 if k <= 8 else 16
+
+
+def _ref_amax(cx, t):
+    """max|t| for the fp16-pair split of a gradient no producer kernel recorded it for (see _cgr_bwd's amax); None elsewhere."""
+    return ops.absmax(t) if cx.x3s else None
+
+
+def _ref_fwd(ctx, cx, out):
+    """RefUnet.forward on the unrefined logits `out` [N, K, D, H, W] f32 -> refined logits, same shape (networks/equiunet2020.py:
+    277-309).  The nine units are _cgr_fwd -- the up-sampled tensor comes FIRST in the concat, the skip second (:296-305, the
+    opposite of the main decoder) -- conv0 is the first layer's route (class planes zero-padded to a channel vector), and the last
+    convolution, the bias and the residual are one pass of ops.conv3d_narrow."""
+    r, dtype = cx.m.refunet, cx.dtype
+    cgr = functools.partial(_cgr_fwd, cx)
+    k, f0 = out.shape[1], r.conv0.weight.shape[0]
+    x0 = ops.ncdhw_to_ndhwc(out, dtype, cpad=input_cpad(k, dtype))
+    x0._net_input = True
+    amax0 = ops.absmax(x0) if ops.x3_mode() == ops.X3F else None  # (un-normalised, like the network input: _fn_forward)
+    wpk = ops.pack_weights(r.conv0.weight, dtype, PACK_FWD, cin_pad=x0.shape[-1])
+    hx, _ = ops.conv3d(x0, wpk, f0, 3, 1, bias=r.conv0.bias.detach(), amax=amax0)
+    hx1, p = cgr(r.hx1, hx, pool=True)
+    hx2, p = cgr(r.hx2, p, pool=True)
+    hx3, p = cgr(r.hx3, p, pool=True)
+    hx4, p = cgr(r.hx4, p, pool=True)
+    d = cgr(r.hx5, p)
+    for unit, skip in ((r.d4, hx4), (r.d3, hx3), (r.d2, hx2), (r.d1, hx1)):
+        d = cgr(unit, ops.upsample(d, 2), x2=skip)
+    ctx.ref = (x0, hx1, hx2, hx3, hx4, d)
+    return ops.conv3d_narrow(d, ops.pack_weights_narrow(r.conv_d0.weight, PACK_FWD), k, bias=r.conv_d0.bias.detach(), add=out)
+
+
+def _ref_bwd(ctx, cx, d_ref, d_out):
+    """Backward of _ref_fwd: the stage's parameter gradients go to cx.put; returns the whole gradient of the unrefined logits,
+    d_ref (through the residual) + d_out (the loss on the unrefined head) + conv0^T d(hx) -- the last two terms and the
+    transposed convolution are one pass of ops.conv3d_narrow."""
+    r, dtype = cx.m.refunet, cx.dtype
+    cbw = functools.partial(_cgr_bwd, cx)
+    x0, hx1, hx2, hx3, hx4, d1 = ctx.ref
+    ctx.ref = None
+    if d_ref is None:
+        d_ref = torch.zeros(ctx.out_shape, dtype=torch.float32, device=d1.device)
+    d_ref = d_ref.contiguous().float()
+    k, f0 = d_ref.shape[1], d1.shape[-1]
+    # conv_d0: dy = d_ref as NDHWC, class planes zero-padded to a channel vector (the weight rows are padded alike)
+    dy = ops.ncdhw_to_ndhwc(d_ref, dtype, cpad=_ref_cpad(k))
+    amax = _ref_amax(cx, dy)
+    dw, _ = ops.conv3d_wgrad(d1, dy, 3, 1, amax_dy=amax)
+    cx.put(r.conv_d0.weight, dw[:k].contiguous())
+    # (the bias gradients are channel sums: ops.channel_dot streams the tensor once; the weight-gradient entry's own dbias pass is
+    #  one workgroup per channel -- 6.8 ms at 2 x 128^3, measured)
+    cx.put(r.conv_d0.bias, ops.channel_dot(dy).sum(0)[:k].contiguous())
+    wpad = torch.zeros((dy.shape[-1],) + tuple(r.conv_d0.weight.shape[1:]), dtype=torch.float32, device=d1.device)
+    wpad[:k] = r.conv_d0.weight.detach()
+    with ops.use_plan(None):  # (a new tensor every step: not a plan entry)
+        wpk = ops.pack_weights(wpad, dtype, PACK_DGRAD)
+    g, _ = ops.conv3d(dy, wpk, f0, 3, 1, amax=amax)
+    # d1 .. d4 (inputs [up-sampled | skip]), hx5, then the pooled levels
+    skips = []
+    for unit in (r.d1, r.d2, r.d3, r.d4):
+        g_up, g_skip = cbw(unit, g)
+        skips.append(g_skip)
+        g = ops.upsample_bwd(g_up, 2)
+    g = cbw(r.hx5, g)
+    for unit, down in ((r.hx4, hx4), (r.hx3, hx3), (r.hx2, hx2), (r.hx1, hx1)):
+        g = _level_bwd(cx, unit, down, g, skips.pop())
+    # conv0: weight / bias gradients on the padded logits, input gradient + the two other terms of d(out)
+    dw0, _ = ops.conv3d_wgrad(x0, g, 3, 1, amax_dy=_ref_amax(cx, g))
+    cx.put(r.conv0.weight, dw0[:, :k].contiguous())
+    cx.put(r.conv0.bias, ops.channel_dot(g).sum(0))
+    rest = d_ref if d_out is None else d_ref + d_out.float()
+    return ops.conv3d_narrow(g, ops.pack_weights_narrow(r.conv0.weight, PACK_DGRAD), k, add=rest)
+
+
 class _EquiUnetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, dtype, *params):
@@ -460,6 +562,8 @@ class _EquiUnetFn(torch.autograd.Function):
                 outs.append(ops.head(src, hd.weight, hd.bias, sc))
                 ctx.heads.append((hd, src, sc))
         ctx.bufs = (down1, down2, down3, down4, bottom, bottom_2, up3, up2, up1)
+        if m.refinement:  # (networks/equiunet2020.py:490-491: out = [refunet(out), out])
+            outs.insert(0, _ref_fwd(ctx, cx, outs[0]))
         return tuple(outs)
 
     @staticmethod
@@ -468,14 +572,9 @@ class _EquiUnetFn(torch.autograd.Function):
         down1, down2, down3, down4, bottom, bottom_2, up3, up2, up1 = ctx.bufs
         cbw = functools.partial(_cgr_bwd, cx)
 
-        def level_bwd(unit, down, d_pooled, d_skip, need_dx=True, bst=None):
-            """Backward of the last layer of an encoder level: its output gradient = d_skip + max-pool backward(d_pooled)."""
-            idx = getattr(down, "_pool_argmax", None)
-            kact, slope_t = _unit_act(unit, cx.act)
-            if (idx is not None and m.fold_pool_bwd and cx.drop is None and not unit.batch_norm and slope_t is None
-                    and kact in ("relu", "leakyrelu")):
-                return cbw(unit, None, need_dx=need_dx, pool=(d_skip, d_pooled, idx), bst=bst)
-            return cbw(unit, ops.maxpool2_bwd(down, d_pooled, dx_skip=d_skip), need_dx=need_dx, bst=bst)
+        level_bwd = functools.partial(_level_bwd, cx)
+        if m.refinement:  # the stage runs first: (d_refined, d_out, deep...) -> (the whole gradient of out, deep...)
+            douts = (_ref_bwd(ctx, cx, douts[0], douts[1]),) + tuple(douts[2:])
 
         c1, c2 = _blk(m.decoder1)
         # the output head on up1: folded into the GroupNorm backward of the last layer where that is built
@@ -526,11 +625,10 @@ class EquiUnet(_PackedWeightsModule):
             raise NotImplementedError("--norm batch with --act prelu is not implemented")
         if act not in ("relu", "leakyrelu", "elu", "prelu", "swish", "mish"):
             raise NotImplementedError(f"brats21_amd.EquiUnet implements --act relu|leakyrelu|elu|prelu|swish|mish (got {act!r})")
-        if refinement:
-            raise NotImplementedError("equiunet_ref (RefUnet) is outside the accelerated hot path")
         self._check_shape_limits(inplanes, num_classes, features, 8)
         print(f"EquiUnet features: {features}")
         self.deep_supervision = deep_supervision
+        self.refinement = bool(refinement)
         self.act = act
         self.features = list(features)
         # nn.Dropout(p) behind every ConvBnRelu's activation (networks/equiunet2020.py:62; --dropout, src/arguments_train.py:52)
@@ -559,6 +657,10 @@ class EquiUnet(_PackedWeightsModule):
             self.deep_bottom2 = _head(f[2], num_classes)
             self.deep3 = _head(f[1], num_classes)
             self.deep2 = _head(f[0], num_classes)
+        if self.refinement:
+            # registered LAST (networks/equiunet2020.py:460-462): its keys end the state dict, and the dropout streams of the
+            # units above (_unit_ids) are the same with and without it
+            self.refunet = RefUnet(num_classes, f[0], norm=nl, act=act)
         self._unit_ids = {u: i for i, u in enumerate(mod for mod in self.modules() if isinstance(mod, ConvBnRelu))}
         # init_weights(self, "kaiming"), networks/factory.py:203-224: kaiming-normal fan_out on conv weights
         print("initialize network with kaiming")

@@ -536,6 +536,52 @@ def _conv3d(x, packed_w, cout, ksize=3, dil=1, bias=None, out=None, want_stats=F
     return y, stats
 
 
+# ------------------------------------------------------------------------------------------ narrow-output conv
+def pack_weights_narrow(w, mode):
+    """w: torch-layout [Cout, Cin, 3, 3, 3] f32 -> the f32 buffer conv3d_narrow() reads.  PACK_FWD: Cout <= 16 class rows over Cin
+    channels; PACK_DGRAD: Cin <= 16 class rows over Cout channels, transposed with the taps flipped (the input gradient as a
+    convolution of dy).  The channel count must be a multiple of 8.  Cached under no_grad like pack_weights()."""
+    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3):
+        raise _lib.BratsHipError(f"pack_weights_narrow: expected [Cout, Cin, 3, 3, 3], got {tuple(w.shape)}")
+    cout_w, cin_w = w.shape[0], w.shape[1]
+    c, k = (cin_w, cout_w) if mode == PACK_FWD else (cout_w, cin_w)
+    key = None
+    if not torch.is_grad_enabled():
+        key = (id(w), "narrow", mode)
+        hit = _cache_get(key, w)
+        if hit is not None:
+            return hit
+    nbytes = _lib.lib().brats_conv3d_narrow_packed_bytes(c, k)
+    if nbytes == 0:
+        raise _lib.BratsHipError(f"pack_weights_narrow: {c} channels -> {k} rows is outside the kernel (channels % 8 == 0, rows <= 16)")
+    wf = w.detach().contiguous().float()
+    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    _lib.check(_lib.lib().brats_conv3d_narrow_pack(wf.data_ptr(), packed.data_ptr(), mode, cout_w, cin_w, _stream()),
+               "conv3d_narrow_pack")
+    if key is not None:
+        _cache_put(key, w, packed)
+    return packed
+
+
+def conv3d_narrow(x, packed_w, k, bias=None, add=None):
+    """NCDHW f32 [N, k, D, H, W] = add + bias + conv3x3x3(x) (zero padding, dilation 1) of an NDHWC tensor or channel slice x
+    (bf16, fp16 or f32; C a multiple of 8) with weights from pack_weights_narrow(); k <= 16.  bias [k] and add [N, k, D, H, W]
+    (f32, never rounded) are optional.  One pass: x is read once per output tile, the result leaves as f32 planes."""
+    ptr, c, p = _desc(x)
+    n, d, h, w, _ = x.shape
+    if packed_w.numel() * 4 != _lib.lib().brats_conv3d_narrow_packed_bytes(c, k):
+        raise _lib.BratsHipError(f"conv3d_narrow: the packed weights do not belong to a {c} -> {k} layer")
+    if add is not None and tuple(add.shape) != (n, k, d, h, w):
+        raise _lib.BratsHipError(f"conv3d_narrow: add has shape {tuple(add.shape)}, expected {(n, k, d, h, w)}")
+    if bias is not None and bias.numel() != k:
+        raise _lib.BratsHipError(f"conv3d_narrow: bias has {bias.numel()} elements, expected {k}")
+    out = torch.empty((n, k, d, h, w), dtype=torch.float32, device=x.device)
+    with _span("conv_narrow", c, k, n, d, h, w, str(x.dtype)):
+        _lib.check(_lib.lib().brats_conv3d_narrow_fwd(ptr, c, p, packed_w.data_ptr(), _f32(bias), _f32(add), out.data_ptr(),
+                                                      _code(x.dtype), k, n, d, h, w, _stream()), "conv3d_narrow_fwd")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ fp8 conv
 def absmax(x):
     """max|x| of an NDHWC tensor as a 1-element f32 device tensor (no host sync)."""

@@ -54,7 +54,7 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * only (brats_cc_filter, brats_rare_fill + their workspace queries).  Still 7 after further additions only (brats_hausdorff +
  * its workspace query; brats_edt + its workspace query, brats_sigmoid_argmax_onehot, brats_hd_loss_stats / _grad,
  * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk; brats_staple_blocks / _pack /
- * _init / _iterate / _apply): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
  * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
@@ -455,6 +455,19 @@ int brats_upsample_bwd(const void* dy, int dypitch, void* dx, int dxpitch, void*
  * workgroup, the fine box read once, H and W reductions out of LDS) where it tiles: C a multiple of 48, W of 8, D and H of 4;
  * 0 = the three passes through tmp everywhere.  Bit-identical results; returns the previous setting. */
 int brats_upsample_bwd_set_fused(int mode);
+
+/* ---- narrow-output 3x3x3 convolution (csrc/conv_narrow.hip): C input channels (a multiple of 8) -> 1 <= K <= 16 planes, zero
+ * padding, dilation 1:  out[n][k][z][y][x] (f32, NCDHW) = add[n][k][z][y][x] + bias[k] + sum_taps sum_c w[k][c][tap] * x[n][z+dz][y+dy][x+dx][c]
+ * x: NDHWC of dtype BRATS_F32 / BRATS_BF16 / BRATS_F16 (16-byte aligned, xpitch elements between voxels: a channel slice is
+ * fine); bias [K] and add [N][K][D][H][W] are optional (NULL) f32; f32 accumulation, the residual is never rounded.  The input
+ * tile is read once per output tile, the halo comes from LDS.  Users: the last convolution of the refinement stage (add = the
+ * unrefined logits) and the input gradient of its first convolution (weights packed BRATS_PACK_DGRAD, x = dY).
+ * brats_conv3d_narrow_pack: w in torch layout [cout_w][cin_w][3][3][3] f32 -> packed f32 of brats_conv3d_narrow_packed_bytes(C, K)
+ * bytes; BRATS_PACK_FWD: K = cout_w rows, C = cin_w; BRATS_PACK_DGRAD: K = cin_w rows, C = cout_w, transposed, taps flipped. */
+size_t brats_conv3d_narrow_packed_bytes(int C, int K);
+int brats_conv3d_narrow_pack(const float* w, float* packed, int mode, int cout_w, int cin_w, brats_stream_t s);
+int brats_conv3d_narrow_fwd(const void* x, int C, int xpitch, const float* packed_w, const float* bias, const float* add, float* out,
+                            int dtype, int K, int N, int D, int H, int W, brats_stream_t s);
 
 /* ---- segmentation heads: 1x1x1 conv C -> K (1 <= K <= 16) + bias (conv1x1 equiunet2020.py:37-41,441)
  * followed by trilinear x`scale` up-sampling (deep heads :443-458); output NCDHW f32 logits.  The activations are read once
