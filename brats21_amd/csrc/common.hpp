@@ -269,3 +269,63 @@ namespace brats_f16 {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// ---- run-time storage type / streaming form -> template arguments -------------------------------
+// The helpers turn the run-time choice into tag arguments of a generic lambda, so that a launch site writes the kernel's
+// argument list once:   with_storage(dtype, [&](auto t) { using T = typename decltype(t)::type; ...kernel<T>... (const T*)x ... });
+// The flags arrive as std::true_type / std::false_type (decltype(nt)::value).  Each helper enumerates exactly the
+// combinations named in its comment: a kernel form that no entry point launches is not instantiated either.  A helper
+// returns what the lambda returns.
+template <typename T> struct type_tag { using type = T; };
+// f(true_type | false_type)
+template <typename F> static inline auto with_flag(bool on, F&& f) {
+  if (on) return f(std::true_type{});
+  return f(std::false_type{});
+}
+// f(T): bf16_t for BRATS_BF16, float for every other dtype
+template <typename F> static inline auto with_storage(int dtype, F&& f) {
+  if (dtype == BRATS_BF16) return f(type_tag<bf16_t>{});
+  return f(type_tag<float>{});
+}
+// f(T, NT): both storage types x {plain, non-temporal}
+template <typename F> static inline auto with_stream(int dtype, bool nt, F&& f) {
+  return with_storage(dtype, [&](auto t) { return with_flag(nt, [&](auto n) { return f(t, n); }); });
+}
+// f(T, NT): (bf16_t, NT), (bf16_t, plain), (float, plain) -- the kernels that have no f32 non-temporal form
+template <typename F> static inline auto with_stream16(int dtype, bool nt, F&& f) {
+  if (dtype != BRATS_BF16) return f(type_tag<float>{}, std::false_type{});
+  return with_flag(nt, [&](auto n) { return f(type_tag<bf16_t>{}, n); });
+}
+// f(T, HEAVY, NT): (T, light, NT), (T, light, plain), (T, heavy, plain) -- a heavy activation is never streamed non-temporally
+template <typename F> static inline auto with_act_stream(int dtype, bool heavy, bool nt, F&& f) {
+  if (heavy) return with_storage(dtype, [&](auto t) { return f(t, std::true_type{}, std::false_type{}); });
+  return with_stream(dtype, nt, [&](auto t, auto n) { return f(t, std::false_type{}, n); });
+}
+
+// "Big": the tensor cannot stay in the Infinity Cache (stream_nt), so it is streamed non-temporally and on more,
+// shorter-lived blocks.  Two rules, by which non-temporal forms the kernels have:
+// by the bytes of the storage type -- affine_act and the GroupNorm backward passes, which have f32 non-temporal forms (the
+// split-precision mode's f32 tensors are 2 x 128^3 x 48 x 4 B = 805 MB);
+static inline bool big_tensor(int dtype, size_t elems) { return stream_nt(elems * (dtype == BRATS_BF16 ? 2 : 4)); }
+// 16-bit storage only -- the EvoNorm family, channel_dot / channel_scale and affine_act_pool, which have none for f32.
+static inline bool big_tensor16(int dtype, size_t elems) { return dtype == BRATS_BF16 && stream_nt(elems * 2); }
+
+static inline int vec_width(int dtype) { return dtype == BRATS_BF16 ? 8 : 4; }  // elements of a 16-byte vector
+
+// grid of a grid-stride pass over `total` items, `block` per block, at most `cap` blocks
+static inline int stream_grid(size_t total, int block, int cap) {
+  size_t b = (total + block - 1) / block;
+  return (int)(b < 1 ? 1 : (b > (size_t)cap ? (size_t)cap : b));
+}
+
+// The voxel walk of the per-sample streaming passes: 256 threads = cv channel vectors x vl voxel lanes, 8 voxels per lane and
+// block before the cap; grid.y = N.  Valid for C % vw == 0 and C / vw <= 256 (the entry points check first).
+struct Walk {
+  int cv, vl;     // 16-byte channel vectors per voxel, voxel lanes per block
+  size_t blocks;  // per sample, not capped
+  unsigned grid(size_t cap) const { return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks)); }
+};
+static inline Walk voxel_walk(int vw, int voxels, int C) {
+  const int cv = C / vw, vl = 256 / cv;
+  return Walk{cv, vl, ((size_t)voxels + (size_t)vl * 8 - 1) / ((size_t)vl * 8)};
+}
+

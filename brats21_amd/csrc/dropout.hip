@@ -53,21 +53,19 @@ extern "C" int BRATS_API(brats_dropout)(const void* x, int xpitch, void* out, in
   if (!x || !out || !state || C <= 0) BRATS_FAIL(BRATS_E_ARG, "dropout: null pointer / bad size");
   if (!(p >= 0.f && p < 1.f)) BRATS_FAIL(BRATS_E_ARG, "dropout: p = %g must be in [0, 1)", (double)p);
   if (dtype != BRATS_BF16 && dtype != BRATS_F32) BRATS_FAIL(BRATS_E_UNSUPPORTED, "dropout: dtype %d", dtype);
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (C % vw || xpitch % vw || opitch % vw) BRATS_FAIL(BRATS_E_ARG, "dropout: C and pitches must be multiples of %d", vw);
   const size_t total = voxels * (size_t)(C / vw);
   if (!total) return 0;
-  size_t nb = (total + 255) / 256;
-  const unsigned blocks = (unsigned)(nb > 16384 ? 16384 : nb);
+  const unsigned blocks = stream_grid(total, 256, 16384);
   const uint32_t thresh = (uint32_t)((double)p * 16777216.0);  // keep <=> 24 random bits >= p * 2^24
   const float scale = 1.f / (1.f - p);
   hipStream_t st = (hipStream_t)s;
-  if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(dropout_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)x, xpitch, (bf16_t*)out, opitch, voxels, C,
-                       thresh, scale, (const unsigned long long*)state, (uint32_t)unit);
-  else
-    hipLaunchKernelGGL(dropout_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)x, xpitch, (float*)out, opitch, voxels, C,
-                       thresh, scale, (const unsigned long long*)state, (uint32_t)unit);
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dropout_kernel<T>, dim3(blocks), dim3(256), 0, st, (const T*)x, xpitch, (T*)out, opitch, voxels, C, thresh, scale,
+                       (const unsigned long long*)state, (uint32_t)unit);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }

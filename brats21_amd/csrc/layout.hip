@@ -40,29 +40,18 @@ __global__ void ndhwc_to_ncdhw_kernel(const T* __restrict__ src, int pitch, floa
   }
 }
 
-static inline int lgrid(size_t total) {
-  size_t b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
 extern "C" int BRATS_API(brats_ncdhw_to_ndhwc)(const float* src, void* dst, int dtype, int N, int C, int cpad, int dst_pitch, int D,
                                     int H, int W, brats_stream_t s) {
   if (!src || !dst || cpad < C || dst_pitch < cpad) BRATS_FAIL(BRATS_E_ARG, "ncdhw_to_ndhwc: bad argument");
   const size_t vox = (size_t)D * H * W;
-  dim3 grid(lgrid(vox), N);
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
-  if (cpad == vw && dst_pitch % vw == 0 && ((uintptr_t)dst & 15) == 0) {
-    if (dtype == BRATS_BF16)
-      hipLaunchKernelGGL(ncdhw_to_ndhwc_vec_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, src, (bf16_t*)dst, C, dst_pitch, vox);
-    else
-      hipLaunchKernelGGL(ncdhw_to_ndhwc_vec_kernel<float>, grid, dim3(256), 0, (hipStream_t)s, src, (float*)dst, C, dst_pitch, vox);
-    BRATS_CHECK_LAUNCH();
-    return 0;
-  }
-  if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(ncdhw_to_ndhwc_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, src, (bf16_t*)dst, C, cpad, dst_pitch, vox);
-  else
-    hipLaunchKernelGGL(ncdhw_to_ndhwc_kernel<float>, grid, dim3(256), 0, (hipStream_t)s, src, (float*)dst, C, cpad, dst_pitch, vox);
+  dim3 grid(stream_grid(vox, 256, 8192), N);
+  const int vw = vec_width(dtype);
+  const bool vec = cpad == vw && dst_pitch % vw == 0 && ((uintptr_t)dst & 15) == 0;
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (vec) hipLaunchKernelGGL(ncdhw_to_ndhwc_vec_kernel<T>, grid, dim3(256), 0, (hipStream_t)s, src, (T*)dst, C, dst_pitch, vox);
+    else hipLaunchKernelGGL(ncdhw_to_ndhwc_kernel<T>, grid, dim3(256), 0, (hipStream_t)s, src, (T*)dst, C, cpad, dst_pitch, vox);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -71,11 +60,11 @@ extern "C" int BRATS_API(brats_ndhwc_to_ncdhw)(const void* src, int src_pitch, f
                                     brats_stream_t s) {
   if (!src || !dst || src_pitch < C) BRATS_FAIL(BRATS_E_ARG, "ndhwc_to_ncdhw: bad argument");
   const size_t vox = (size_t)D * H * W;
-  dim3 grid(lgrid(vox), N);
-  if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(ndhwc_to_ncdhw_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, (const bf16_t*)src, src_pitch, dst, C, vox);
-  else
-    hipLaunchKernelGGL(ndhwc_to_ncdhw_kernel<float>, grid, dim3(256), 0, (hipStream_t)s, (const float*)src, src_pitch, dst, C, vox);
+  dim3 grid(stream_grid(vox, 256, 8192), N);
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(ndhwc_to_ncdhw_kernel<T>, grid, dim3(256), 0, (hipStream_t)s, (const T*)src, src_pitch, dst, C, vox);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }

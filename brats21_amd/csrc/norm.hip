@@ -6,11 +6,6 @@
 #include "twin_begin.hpp"
 #include "common.hpp"
 
-// beyond the Infinity Cache (256 MB): non-temporal streaming on more, shorter-lived blocks (common.hpp stream_nt); f32 tensors are
-// the split-precision mode's (2 x 128^3 x 48 x 4 B = 805 MB)
-static inline bool big_tensor(int dtype, size_t elems) {
-  return stream_nt(elems * (dtype == BRATS_BF16 ? 2 : 4));
-}
 #include "se.hpp"
 
 // ---- statistics finalize ---------------------------------------------------------------------------
@@ -326,46 +321,21 @@ __global__ void __launch_bounds__(256) affine_act_kernel(const T* __restrict__ y
   if (amax) record_absmax<T>(mx, amax);
 }
 
-static inline int stream_grid(size_t total, int block) {
-  size_t b = (total + block - 1) / block;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
 extern "C" int BRATS_API(brats_affine_act_fwd)(const void* y, int ypitch, const float* scale_shift, void* z, int zpitch,
                                     int dtype, int act, float slope_value, const float* slope_dev, int N, int voxels, int C,
                                     float* amax, brats_stream_t s) {
   const SlopeArg slope{slope_value, slope_dev};
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!y || !z || !scale_shift || C % vw || ypitch % vw || zpitch % vw || C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "affine_act_fwd: C and pitches must be multiples of %d (C <= %d)", vw, 256 * vw);
-  const int vl = 256 / (C / vw);
-  const int gx = (voxels + vl * 8 - 1) / (vl * 8);
   const bool big = big_tensor(dtype, (size_t)N * voxels * C);
-  const int cap = big ? 8192 : 2048;
-  dim3 grid(gx < 1 ? 1 : (gx > cap ? cap : gx), N);  // large tensors: many short-lived blocks stream faster (scripts/probes/stream_rw.hip)
-  hipStream_t st = (hipStream_t)s;
-  uint32_t* am = (uint32_t*)amax;
-  if (dtype == BRATS_BF16 && act <= BRATS_ACT_LEAKY && big) {
-    hipLaunchKernelGGL((affine_act_kernel<bf16_t, false, true>), grid, dim3(256), 0, st, (const bf16_t*)y, ypitch, scale_shift, (bf16_t*)z,
-                       zpitch, act, slope, voxels, C, am);
-  } else if (dtype != BRATS_BF16 && act <= BRATS_ACT_LEAKY && big) {  // (split-precision mode: f32 tensors of 805 MB at the 128^3 level)
-    hipLaunchKernelGGL((affine_act_kernel<float, false, true>), grid, dim3(256), 0, st, (const float*)y, ypitch, scale_shift, (float*)z,
-                       zpitch, act, slope, voxels, C, am);
-  } else if (act > BRATS_ACT_LEAKY) {
-    if (dtype == BRATS_BF16)
-      hipLaunchKernelGGL((affine_act_kernel<bf16_t, true>), grid, dim3(256), 0, st, (const bf16_t*)y, ypitch, scale_shift, (bf16_t*)z,
-                         zpitch, act, slope, voxels, C, am);
-    else
-      hipLaunchKernelGGL((affine_act_kernel<float, true>), grid, dim3(256), 0, st, (const float*)y, ypitch, scale_shift, (float*)z,
-                         zpitch, act, slope, voxels, C, am);
-  } else {
-    if (dtype == BRATS_BF16)
-      hipLaunchKernelGGL((affine_act_kernel<bf16_t, false>), grid, dim3(256), 0, st, (const bf16_t*)y, ypitch, scale_shift, (bf16_t*)z,
-                         zpitch, act, slope, voxels, C, am);
-    else
-      hipLaunchKernelGGL((affine_act_kernel<float, false>), grid, dim3(256), 0, st, (const float*)y, ypitch, scale_shift, (float*)z,
-                         zpitch, act, slope, voxels, C, am);
-  }
+  // large tensors: many short-lived blocks stream faster (scripts/probes/stream_rw.hip)
+  dim3 grid(voxel_walk(vw, voxels, C).grid(big ? 8192 : 2048), N);
+  with_act_stream(dtype, act > BRATS_ACT_LEAKY, big, [&](auto t, auto heavy, auto nt) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((affine_act_kernel<T, decltype(heavy)::value, decltype(nt)::value>), grid, dim3(256), 0, (hipStream_t)s, (const T*)y,
+                       ypitch, scale_shift, (T*)z, zpitch, act, slope, voxels, C, (uint32_t*)amax);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -521,7 +491,7 @@ extern "C" int BRATS_API(brats_affine_act_pool_fwd)(const void* y, int ypitch, c
                                          const float* slope_dev, int N, int D, int H, int W, int C, int with_avg, float* amax,
                                          brats_stream_t s) {
   const SlopeArg slope{slope_value, slope_dev};
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!y || !z || !pooled || !scale_shift || C % vw || ypitch % vw || zpitch % vw || ppitch % vw || C / vw > 256 || ((D | H | W) & 1))
     BRATS_FAIL(BRATS_E_ARG, "affine_act_pool_fwd: C / pitches multiples of %d (C <= %d), even spatial dims", vw, 256 * vw);
   if (act > BRATS_ACT_LEAKY) BRATS_FAIL(BRATS_E_UNSUPPORTED, "affine_act_pool_fwd: relu / leakyrelu only (act=%d)", act);
@@ -529,20 +499,17 @@ extern "C" int BRATS_API(brats_affine_act_pool_fwd)(const void* y, int ypitch, c
   if (xb < 2) BRATS_FAIL(BRATS_E_UNSUPPORTED, "affine_act_pool_fwd: C=%d leaves no pooling pair per block", C);
   if (xb > W) xb = W;
   const size_t items = (size_t)(D / 2) * (H / 2) * ((W + xb - 1) / xb);
-  const bool big = dtype == BRATS_BF16 && stream_nt((size_t)N * D * H * W * C * 2);
-  const size_t cap = big ? 8192 : 2048;
-  dim3 grid((unsigned)(items < 1 ? 1 : (items > cap ? cap : items)), N);
+  const bool big = big_tensor16(dtype, (size_t)N * D * H * W * C);
+  dim3 grid(stream_grid(items, 1, big ? 8192 : 2048), N);
   const size_t lds = (size_t)2 * 256 * 4 * 16;
-  hipStream_t st = (hipStream_t)s;
-  uint32_t* am = (uint32_t*)amax;
-#define POOL_GO(T, NT, AM) hipLaunchKernelGGL((affine_act_pool_kernel<T, NT, AM>), grid, dim3(256), lds, st, (const T*)y, ypitch, scale_shift, \
-                                              (T*)z, zpitch, (T*)pooled, ppitch, act, slope, D, H, W, C, with_avg, am, argmax)
-  if (argmax) {
-    if (big) POOL_GO(bf16_t, true, true); else if (dtype == BRATS_BF16) POOL_GO(bf16_t, false, true); else POOL_GO(float, false, true);
-  } else {
-    if (big) POOL_GO(bf16_t, true, false); else if (dtype == BRATS_BF16) POOL_GO(bf16_t, false, false); else POOL_GO(float, false, false);
-  }
-#undef POOL_GO
+  with_stream16(dtype, big, [&](auto t, auto nt) {
+    with_flag(argmax != nullptr, [&](auto am) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((affine_act_pool_kernel<T, decltype(nt)::value, decltype(am)::value>), grid, dim3(256), lds, (hipStream_t)s,
+                         (const T*)y, ypitch, scale_shift, (T*)z, zpitch, (T*)pooled, ppitch, act, slope, D, H, W, C, with_avg,
+                         (uint32_t*)amax, argmax);
+    });
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -1003,56 +970,43 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(const T* __restrict__
 constexpr int GN_BWD_MAX_BLOCKS = 2048;
 extern "C" size_t BRATS_API(brats_gn_bwd_ws_floats)(int N, int C) { return (size_t)(1 + GN_BWD_MAX_BLOCKS) * N * C * 2; }
 
-template <typename T, bool HEAVY, bool NT, int HK>
-static void gn_bwd_launch(dim3 g1, dim3 g2, size_t lds1, size_t lds2, hipStream_t st, const void* dz, int dzpitch, const void* y,
-                          int ypitch, const float* scale_shift, const float* mean_rstd, const float* gamma, void* dy, int dypitch,
-                          float* red, float* dgamma, float* dbeta, int act, SlopeArg slope, int N, int voxels, int C, int groups,
-                          float* amax, HeadFold hf) {
-  hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, HEAVY, NT, HK>), g1, dim3(256), lds1, st, (const T*)dz, dzpitch, (const T*)y, ypitch,
-                     scale_shift, mean_rstd, red, act, slope, voxels, C, groups, hf);
-  // pass 1 leaves one partial sum per block; gn_bwd_finish_kernel adds them in block order
-  hipLaunchKernelGGL(gn_bwd_finish_kernel, dim3((N * C * 2 + 7) / 8), dim3(256), 0, st, red, (int)g1.x, N * C * 2);
-  hipLaunchKernelGGL((gn_bwd_apply_kernel<T, HEAVY, NT, HK>), g2, dim3(256), lds2, st, (const T*)dz, dzpitch, (const T*)y, ypitch,
-                     scale_shift, mean_rstd, gamma, red, (T*)dy, dypitch, dgamma, dbeta, act, slope, N, voxels, C, groups,
-                     (uint32_t*)amax, hf);
+// f(HK): the fold a backward pass composes its output gradient from (HeadFold): 3 logit planes of the output head (fold > 0),
+// the pooling backward (fold < 0), none (0)
+template <typename F> static inline void with_fold(int fold, F&& f) {
+  if (fold > 0) f(std::integral_constant<int, 3>{});
+  else if (fold < 0) f(std::integral_constant<int, -1>{});
+  else f(std::integral_constant<int, 0>{});
 }
 
 static int gn_act_bwd_impl(const void* dz, int dzpitch, const void* y, int ypitch, const float* scale_shift, const float* mean_rstd,
                            const float* gamma, void* dy, int dypitch, float* red, float* dgamma, float* dbeta, int dtype, int act,
                            SlopeArg slope, int N, int voxels, int C, int groups, float* amax, HeadFold hf, int K, hipStream_t st) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (C % vw || C % groups || dzpitch % vw || ypitch % vw || dypitch % vw || C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "gn_act_bwd: C=%d / pitches must be multiples of %d", C, vw);
-  const int cv = C / vw, vl = 256 / cv;
-  const int gx = (int)(((size_t)voxels + vl * 8 - 1) / (vl * 8));
+  const Walk w = voxel_walk(vw, voxels, C);
   const bool big = big_tensor(dtype, (size_t)N * voxels * C);
-  const int cap1 = big ? GN_BWD_MAX_BLOCKS : 512;
-  dim3 g1(gx < 1 ? 1 : (gx > cap1 ? cap1 : gx), N);
-  const size_t lds1 = (size_t)(vl * C * 2 + (K > 0 ? vl * K : 0)) * sizeof(float);
-  dim3 g2(gx < 1 ? 1 : (gx > (big ? 8192 : 2048) ? (big ? 8192 : 2048) : gx), N);
+  dim3 g1(w.grid(big ? GN_BWD_MAX_BLOCKS : 512), N), g2(w.grid(big ? 8192 : 2048), N);
+  const size_t lds1 = (size_t)(w.vl * C * 2 + (K > 0 ? w.vl * K : 0)) * sizeof(float);
   const size_t lds2 = (size_t)2 * groups * sizeof(float);
-#define GN_BWD_GO(T, HEAVY, NT, HK) gn_bwd_launch<T, HEAVY, NT, HK>(g1, g2, lds1, lds2, st, dz, dzpitch, y, ypitch, scale_shift, mean_rstd, \
-                                                                  gamma, dy, dypitch, red, dgamma, dbeta, act, slope, N, voxels, C, groups, amax, hf)
-  if (K < 0) {  // the pool-source form (relu / leakyrelu: checked by the caller)
-    if (big && dtype == BRATS_BF16) GN_BWD_GO(bf16_t, false, true, -1);
-    else if (big) GN_BWD_GO(float, false, true, -1);
-    else if (dtype == BRATS_BF16) GN_BWD_GO(bf16_t, false, false, -1);
-    else GN_BWD_GO(float, false, false, -1);
-  } else if (K) {  // (relu / leakyrelu, three logit planes: checked by the caller)
-    if (big && dtype == BRATS_BF16) GN_BWD_GO(bf16_t, false, true, 3);
-    else if (big) GN_BWD_GO(float, false, true, 3);
-    else if (dtype == BRATS_BF16) GN_BWD_GO(bf16_t, false, false, 3);
-    else GN_BWD_GO(float, false, false, 3);
-  } else if (big && act <= BRATS_ACT_LEAKY && dtype == BRATS_BF16) GN_BWD_GO(bf16_t, false, true, 0);
-  else if (big && act <= BRATS_ACT_LEAKY) GN_BWD_GO(float, false, true, 0);
-  else if (act > BRATS_ACT_LEAKY) {
-    if (dtype == BRATS_BF16) GN_BWD_GO(bf16_t, true, false, 0);
-    else GN_BWD_GO(float, true, false, 0);
-  } else {
-    if (dtype == BRATS_BF16) GN_BWD_GO(bf16_t, false, false, 0);
-    else GN_BWD_GO(float, false, false, 0);
-  }
-#undef GN_BWD_GO
+  auto go = [&](auto t, auto heavy, auto nt, auto hk) {
+    using T = typename decltype(t)::type;
+    constexpr bool HEAVY = decltype(heavy)::value, NT = decltype(nt)::value;
+    constexpr int HK = decltype(hk)::value;
+    hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, HEAVY, NT, HK>), g1, dim3(256), lds1, st, (const T*)dz, dzpitch, (const T*)y, ypitch,
+                       scale_shift, mean_rstd, red, act, slope, voxels, C, groups, hf);
+    // pass 1 leaves one partial sum per block; gn_bwd_finish_kernel adds them in block order
+    hipLaunchKernelGGL(gn_bwd_finish_kernel, dim3((N * C * 2 + 7) / 8), dim3(256), 0, st, red, (int)g1.x, N * C * 2);
+    hipLaunchKernelGGL((gn_bwd_apply_kernel<T, HEAVY, NT, HK>), g2, dim3(256), lds2, st, (const T*)dz, dzpitch, (const T*)y, ypitch,
+                       scale_shift, mean_rstd, gamma, red, (T*)dy, dypitch, dgamma, dbeta, act, slope, N, voxels, C, groups,
+                       (uint32_t*)amax, hf);
+  };
+  with_fold(K, [&](auto hk) {
+    if constexpr (decltype(hk)::value != 0)  // the head and pool folds: relu / leakyrelu only (checked by the caller)
+      with_stream(dtype, big, [&](auto t, auto nt) { go(t, std::false_type{}, nt, hk); });
+    else
+      with_act_stream(dtype, act > BRATS_ACT_LEAKY, big, [&](auto t, auto heavy, auto nt) { go(t, heavy, nt, hk); });
+  });
   BRATS_CHECK_LAUNCH();
   return (int)g1.x;  // > 0: the number of pass-1 blocks per sample (the head partials' count)
 }
@@ -1103,7 +1057,7 @@ extern "C" int BRATS_API(brats_gn_act_bwd_tiles)(const float* tile_stats, int ti
     BRATS_FAIL(BRATS_E_ARG, "gn_act_bwd_tiles: null pointer");
   if (dtype != BRATS_BF16 && dtype != BRATS_F32) BRATS_FAIL(BRATS_E_UNSUPPORTED, "gn_act_bwd_tiles: 16-bit or f32 (split-precision mode) activations");
   if (act != BRATS_ACT_RELU && act != BRATS_ACT_LEAKY) BRATS_FAIL(BRATS_E_UNSUPPORTED, "gn_act_bwd_tiles: relu / leakyrelu only (act %d)", act);
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (C % vw || C % groups || dzpitch % vw || ypitch % vw || dypitch % vw || C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "gn_act_bwd_tiles: C=%d / pitches must be multiples of %d", C, vw);
   hipStream_t st = (hipStream_t)s;
@@ -1112,24 +1066,15 @@ extern "C" int BRATS_API(brats_gn_act_bwd_tiles)(const float* tile_stats, int ti
   const int splits = gn_splits(tiles_per_sample);
   hipLaunchKernelGGL(gn_chan_reduce_kernel, dim3((C + 15) / 16, N, splits), dim3(256), 0, st, tile_stats, tiles_per_sample, C, part);
   hipLaunchKernelGGL(gn_bwd_tiles_finish_kernel, dim3((N * C + 255) / 256), dim3(256), 0, st, part, splits, N, C, groups, mean_rstd, red);
-  const int cv = C / vw, vl = 256 / cv;
-  const int gx = (int)(((size_t)voxels + vl * 8 - 1) / (vl * 8));
   const bool big = big_tensor(dtype, (size_t)N * voxels * C);
-  dim3 g2(gx < 1 ? 1 : (gx > (big ? 8192 : 2048) ? (big ? 8192 : 2048) : gx), N);
+  dim3 g2(voxel_walk(vw, voxels, C).grid(big ? 8192 : 2048), N);
   const size_t lds2 = (size_t)2 * groups * sizeof(float);
-  const SlopeArg sl{slope, nullptr};
-  if (dtype == BRATS_F32 && big)
-    hipLaunchKernelGGL((gn_bwd_apply_kernel<float, false, true, 0>), g2, dim3(256), lds2, st, (const float*)dz, dzpitch, (const float*)y, ypitch,
-                       scale_shift, mean_rstd, gamma, red, (float*)dy, dypitch, dgamma, dbeta, act, sl, N, voxels, C, groups, (uint32_t*)amax, HeadFold{});
-  else if (dtype == BRATS_F32)
-    hipLaunchKernelGGL((gn_bwd_apply_kernel<float, false, false, 0>), g2, dim3(256), lds2, st, (const float*)dz, dzpitch, (const float*)y, ypitch,
-                       scale_shift, mean_rstd, gamma, red, (float*)dy, dypitch, dgamma, dbeta, act, sl, N, voxels, C, groups, (uint32_t*)amax, HeadFold{});
-  else if (big)
-    hipLaunchKernelGGL((gn_bwd_apply_kernel<bf16_t, false, true, 0>), g2, dim3(256), lds2, st, (const bf16_t*)dz, dzpitch, (const bf16_t*)y, ypitch,
-                       scale_shift, mean_rstd, gamma, red, (bf16_t*)dy, dypitch, dgamma, dbeta, act, sl, N, voxels, C, groups, (uint32_t*)amax, HeadFold{});
-  else
-    hipLaunchKernelGGL((gn_bwd_apply_kernel<bf16_t, false, false, 0>), g2, dim3(256), lds2, st, (const bf16_t*)dz, dzpitch, (const bf16_t*)y, ypitch,
-                       scale_shift, mean_rstd, gamma, red, (bf16_t*)dy, dypitch, dgamma, dbeta, act, sl, N, voxels, C, groups, (uint32_t*)amax, HeadFold{});
+  with_stream(dtype, big, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((gn_bwd_apply_kernel<T, false, decltype(nt)::value, 0>), g2, dim3(256), lds2, st, (const T*)dz, dzpitch, (const T*)y,
+                       ypitch, scale_shift, mean_rstd, gamma, red, (T*)dy, dypitch, dgamma, dbeta, act, SlopeArg{slope, nullptr}, N, voxels,
+                       C, groups, (uint32_t*)amax, HeadFold{});
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -1165,7 +1110,7 @@ extern "C" int BRATS_API(brats_gn_act_bwd_pool)(const void* dskip, int dskip_pit
                                      const float* mean_rstd, const float* gamma, void* dy, int dypitch, float* red, float* dgamma,
                                      float* dbeta, int dtype, int act, float slope_value, int N, int D, int H, int W, int C,
                                      int groups, float* amax, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!dskip || !dpool || !argmax || !y || !dy || !red || !scale_shift || !mean_rstd || !gamma)
     BRATS_FAIL(BRATS_E_ARG, "gn_act_bwd_pool: null pointer");
   if (act > BRATS_ACT_LEAKY || ((D | H | W) & 1) || dskip_pitch % vw || dpool_pitch % vw)
@@ -1225,19 +1170,16 @@ constexpr int PRELU_MAX_BLOCKS = 1024;
 extern "C" size_t BRATS_API(brats_prelu_ws_floats)(int N) { return (size_t)N * PRELU_MAX_BLOCKS; }
 extern "C" int BRATS_API(brats_prelu_slope_grad)(const void* dz, int dzpitch, const void* y, int ypitch, const float* scale_shift, float* ws,
                                       float* dslope, int dtype, int N, int voxels, int C, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!dz || !y || !scale_shift || !ws || !dslope || C % vw || dzpitch % vw || ypitch % vw || C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "prelu_slope_grad: bad argument");
   hipStream_t st = (hipStream_t)s;
-  const int vl = 256 / (C / vw);
-  size_t gx = ((size_t)voxels + (size_t)vl * 8 - 1) / ((size_t)vl * 8);
-  gx = gx < 1 ? 1 : (gx > PRELU_MAX_BLOCKS ? PRELU_MAX_BLOCKS : gx);
-  if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(prelu_slope_grad_kernel<bf16_t>, dim3((unsigned)gx, N), dim3(256), 0, st, (const bf16_t*)dz, dzpitch,
-                       (const bf16_t*)y, ypitch, scale_shift, ws, voxels, C);
-  else
-    hipLaunchKernelGGL(prelu_slope_grad_kernel<float>, dim3((unsigned)gx, N), dim3(256), 0, st, (const float*)dz, dzpitch,
-                       (const float*)y, ypitch, scale_shift, ws, voxels, C);
+  const unsigned gx = voxel_walk(vw, voxels, C).grid(PRELU_MAX_BLOCKS);
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(prelu_slope_grad_kernel<T>, dim3(gx, N), dim3(256), 0, st, (const T*)dz, dzpitch, (const T*)y, ypitch, scale_shift,
+                       ws, voxels, C);
+  });
   BRATS_CHECK_LAUNCH();
   return brats_ordered_sum(ws, dslope, N * (int)gx, 1, st);
 }
@@ -1321,23 +1263,18 @@ extern "C" size_t BRATS_API(brats_chan_ws_floats)(int N, int C, int vals) { retu
 extern "C" int BRATS_API(brats_evonorm_fwd)(const void* x, int xpitch, const float* mean_rstd, const float* gamma, const float* beta,
                                  void* z, int zpitch, float* chansum, int dtype, int N, int voxels, int C, int groups,
                                  float* amax, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!x || !z || !mean_rstd || !gamma || !beta || C % vw || C % groups || xpitch % vw || zpitch % vw || C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "evonorm_fwd: bad argument (C, pitches multiples of %d)", vw);
   hipStream_t st = (hipStream_t)s;
-  const int cv = C / vw, vl = 256 / cv;
-  size_t gx = ((size_t)voxels + (size_t)vl * 8 - 1) / ((size_t)vl * 8);
-  dim3 grid((unsigned)(gx < 1 ? 1 : (gx > CHAN_MAX_BLOCKS ? CHAN_MAX_BLOCKS : gx)), N);
-  const size_t lds = (size_t)(2 * C + vl * C) * sizeof(float);
-  if (dtype == BRATS_BF16 && stream_nt((size_t)N * voxels * C * 2))  // (beyond the Infinity Cache: non-temporal streaming, common.hpp)
-    hipLaunchKernelGGL((evonorm_fwd_kernel<bf16_t, true>), grid, dim3(256), lds, st, (const bf16_t*)x, xpitch, mean_rstd, gamma, beta,
-                       (bf16_t*)z, zpitch, chansum, voxels, C, groups, (uint32_t*)amax, (const float*)nullptr);
-  else if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(evonorm_fwd_kernel<bf16_t>, grid, dim3(256), lds, st, (const bf16_t*)x, xpitch, mean_rstd, gamma, beta,
-                       (bf16_t*)z, zpitch, chansum, voxels, C, groups, (uint32_t*)amax, (const float*)nullptr);
-  else
-    hipLaunchKernelGGL(evonorm_fwd_kernel<float>, grid, dim3(256), lds, st, (const float*)x, xpitch, mean_rstd, gamma, beta,
-                       (float*)z, zpitch, chansum, voxels, C, groups, (uint32_t*)amax, (const float*)nullptr);
+  const Walk w = voxel_walk(vw, voxels, C);
+  dim3 grid(w.grid(CHAN_MAX_BLOCKS), N);
+  const size_t lds = (size_t)(2 * C + w.vl * C) * sizeof(float);
+  with_stream16(dtype, big_tensor16(dtype, (size_t)N * voxels * C), [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((evonorm_fwd_kernel<T, decltype(nt)::value>), grid, dim3(256), lds, st, (const T*)x, xpitch, mean_rstd, gamma, beta,
+                       (T*)z, zpitch, chansum, voxels, C, groups, (uint32_t*)amax, (const float*)nullptr);
+  });
   if (chansum) brats_ordered_sum(chansum + (size_t)N * C, chansum, (int)grid.x, N * C, st);
   BRATS_CHECK_LAUNCH();
   return 0;
@@ -1394,24 +1331,20 @@ extern "C" int BRATS_API(brats_evonorm_se_fwd)(const void* x, int xpitch, const 
                                     const float* w1, const float* b1, const float* w2, const float* b2, void* out, int opitch,
                                     float* ws, float* chansum_out, float* gate1p, float* hidden, int Ch, int dtype, int N,
                                     int voxels, int C, int groups, float* amax, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!x || !mean_rstd || !gamma || !beta || !ws || !chansum_out || !gate1p || !hidden)
     BRATS_FAIL(BRATS_E_ARG, "evonorm_se_fwd: null pointer");
   if (C % vw || C % groups || xpitch % vw || opitch % vw || C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "evonorm_se_fwd: bad argument (C, pitches multiples of %d)", vw);
   hipStream_t st = (hipStream_t)s;
-  const int cv = C / vw, vl = 256 / cv;
-  size_t gx = ((size_t)voxels + (size_t)vl * 8 - 1) / ((size_t)vl * 8);
-  const bool big = dtype == BRATS_BF16 && stream_nt((size_t)N * voxels * C * 2);
-  const size_t cap = big ? CHAN_MAX_BLOCKS : 512;
-  dim3 g1((unsigned)(gx < 1 ? 1 : (gx > cap ? cap : gx)), N);
-  const size_t lds1 = (size_t)vl * C * sizeof(float);
-  if (big)
-    hipLaunchKernelGGL((evonorm_numsum_kernel<bf16_t, true>), g1, dim3(256), lds1, st, (const bf16_t*)x, xpitch, ws, voxels, C);
-  else if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(evonorm_numsum_kernel<bf16_t>, g1, dim3(256), lds1, st, (const bf16_t*)x, xpitch, ws, voxels, C);
-  else
-    hipLaunchKernelGGL(evonorm_numsum_kernel<float>, g1, dim3(256), lds1, st, (const float*)x, xpitch, ws, voxels, C);
+  const Walk w = voxel_walk(vw, voxels, C);
+  const bool big = big_tensor16(dtype, (size_t)N * voxels * C);
+  dim3 g1(w.grid(big ? CHAN_MAX_BLOCKS : 512), N);
+  const size_t lds1 = (size_t)w.vl * C * sizeof(float);
+  with_stream16(dtype, big, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((evonorm_numsum_kernel<T, decltype(nt)::value>), g1, dim3(256), lds1, st, (const T*)x, xpitch, ws, voxels, C);
+  });
   BRATS_CHECK_LAUNCH();
   brats_ordered_sum(ws + (size_t)N * C, ws, (int)g1.x, N * C, st);
   SeFwdFold fold;
@@ -1419,17 +1352,13 @@ extern "C" int BRATS_API(brats_evonorm_se_fwd)(const void* x, int xpitch, const 
   fold.groups = groups; fold.voxels = (float)voxels;
   if (int rc = brats_se_fwd_launch(nullptr, fold, 1.f / (float)voxels, w1, b1, w2, b2, gate1p, hidden, N, C, Ch, st)) return rc;
   if (!out) return 0;  // (the consumer applies the gated EvoNorm on load: brats_evonorm_head_fwd)
-  dim3 g2((unsigned)(gx < 1 ? 1 : (gx > CHAN_MAX_BLOCKS ? CHAN_MAX_BLOCKS : gx)), N);
-  const size_t lds2 = (size_t)(2 * C + vl * C) * sizeof(float);
-  if (big)
-    hipLaunchKernelGGL((evonorm_fwd_kernel<bf16_t, true>), g2, dim3(256), lds2, st, (const bf16_t*)x, xpitch, mean_rstd, gamma, beta,
-                       (bf16_t*)out, opitch, (float*)nullptr, voxels, C, groups, (uint32_t*)amax, (const float*)gate1p);
-  else if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(evonorm_fwd_kernel<bf16_t>, g2, dim3(256), lds2, st, (const bf16_t*)x, xpitch, mean_rstd, gamma, beta,
-                       (bf16_t*)out, opitch, (float*)nullptr, voxels, C, groups, (uint32_t*)amax, (const float*)gate1p);
-  else
-    hipLaunchKernelGGL(evonorm_fwd_kernel<float>, g2, dim3(256), lds2, st, (const float*)x, xpitch, mean_rstd, gamma, beta,
-                       (float*)out, opitch, (float*)nullptr, voxels, C, groups, (uint32_t*)amax, (const float*)gate1p);
+  dim3 g2(w.grid(CHAN_MAX_BLOCKS), N);
+  const size_t lds2 = (size_t)(2 * C + w.vl * C) * sizeof(float);
+  with_stream16(dtype, big, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((evonorm_fwd_kernel<T, decltype(nt)::value>), g2, dim3(256), lds2, st, (const T*)x, xpitch, mean_rstd, gamma, beta,
+                       (T*)out, opitch, (float*)nullptr, voxels, C, groups, (uint32_t*)amax, (const float*)gate1p);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -1774,39 +1703,28 @@ extern "C" int BRATS_API(brats_evonorm_bwd)(const void* dz, int dzpitch, const v
                                  const float* gamma, void* dx, int dxpitch, float* red, float* dgamma, float* dbeta,
                                  const double* chan_sums, float* dconvbias, int dtype, int N, int voxels, int C, int groups,
                                  float* amax, const float* gscale, const float* gadd, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!dz || !x || !dx || !red || !mean_rstd || !gamma) BRATS_FAIL(BRATS_E_ARG, "evonorm_bwd: null pointer");
   if (dconvbias && !chan_sums) BRATS_FAIL(BRATS_E_ARG, "evonorm_bwd: dconvbias needs the forward per-channel sums");
   if (C % vw || C % groups || dzpitch % vw || xpitch % vw || dxpitch % vw || C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "evonorm_bwd: C=%d / pitches must be multiples of %d", C, vw);
   hipStream_t st = (hipStream_t)s;
-  const int cv = C / vw, vl = 256 / cv;
-  size_t gx = ((size_t)voxels + (size_t)vl * 8 - 1) / ((size_t)vl * 8);
-  const bool big = dtype == BRATS_BF16 && stream_nt((size_t)N * voxels * C * 2);
-  const size_t cap1 = big ? CHAN_MAX_BLOCKS : 512, cap2 = big ? 8192 : 2048;  // large tensors: many short-lived blocks stream faster
-  dim3 g1((unsigned)(gx < 1 ? 1 : (gx > cap1 ? cap1 : gx)), N);  // one partial per block, added in block order
-  const size_t lds1 = (size_t)(vl * C) * sizeof(float);  // (one value plane at a time: lane_reduce_plane)
-  dim3 g2((unsigned)(gx < 1 ? 1 : (gx > cap2 ? cap2 : gx)), N);
+  const Walk w = voxel_walk(vw, voxels, C);
+  const bool big = big_tensor16(dtype, (size_t)N * voxels * C);  // large tensors: many short-lived blocks stream faster
+  dim3 g1(w.grid(big ? CHAN_MAX_BLOCKS : 512), N);  // one partial per block, added in block order
+  const size_t lds1 = (size_t)(w.vl * C) * sizeof(float);  // (one value plane at a time: lane_reduce_plane)
+  dim3 g2(w.grid(big ? 8192 : 2048), N);
   const size_t lds2 = (size_t)3 * C * sizeof(float);
-  if (big) {
-    hipLaunchKernelGGL((evonorm_bwd_reduce_kernel<bf16_t, true>), g1, dim3(256), lds1, st, (const bf16_t*)dz, dzpitch, (const bf16_t*)x,
-                       xpitch, red, voxels, C, gscale, gadd, EvoHead{});
+  with_stream16(dtype, big, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    constexpr bool NT = decltype(nt)::value;
+    hipLaunchKernelGGL((evonorm_bwd_reduce_kernel<T, NT>), g1, dim3(256), lds1, st, (const T*)dz, dzpitch, (const T*)x, xpitch, red, voxels,
+                       C, gscale, gadd, EvoHead{});
     brats_ordered_sum(red + (size_t)N * C * 3, red, (int)g1.x, N * C * 3, st);
-    hipLaunchKernelGGL((evonorm_bwd_apply_kernel<bf16_t, true>), g2, dim3(256), lds2, st, (const bf16_t*)dz, dzpitch, (const bf16_t*)x,
-                       xpitch, mean_rstd, gamma, red, (bf16_t*)dx, dxpitch, dgamma, dbeta, chan_sums, dconvbias, N, voxels, C, groups, (uint32_t*)amax, gscale, gadd, HeadFold{});
-  } else if (dtype == BRATS_BF16) {
-    hipLaunchKernelGGL(evonorm_bwd_reduce_kernel<bf16_t>, g1, dim3(256), lds1, st, (const bf16_t*)dz, dzpitch, (const bf16_t*)x,
-                       xpitch, red, voxels, C, gscale, gadd, EvoHead{});
-    brats_ordered_sum(red + (size_t)N * C * 3, red, (int)g1.x, N * C * 3, st);
-    hipLaunchKernelGGL(evonorm_bwd_apply_kernel<bf16_t>, g2, dim3(256), lds2, st, (const bf16_t*)dz, dzpitch, (const bf16_t*)x,
-                       xpitch, mean_rstd, gamma, red, (bf16_t*)dx, dxpitch, dgamma, dbeta, chan_sums, dconvbias, N, voxels, C, groups, (uint32_t*)amax, gscale, gadd, HeadFold{});
-  } else {
-    hipLaunchKernelGGL(evonorm_bwd_reduce_kernel<float>, g1, dim3(256), lds1, st, (const float*)dz, dzpitch, (const float*)x,
-                       xpitch, red, voxels, C, gscale, gadd, EvoHead{});
-    brats_ordered_sum(red + (size_t)N * C * 3, red, (int)g1.x, N * C * 3, st);
-    hipLaunchKernelGGL(evonorm_bwd_apply_kernel<float>, g2, dim3(256), lds2, st, (const float*)dz, dzpitch, (const float*)x,
-                       xpitch, mean_rstd, gamma, red, (float*)dx, dxpitch, dgamma, dbeta, chan_sums, dconvbias, N, voxels, C, groups, (uint32_t*)amax, gscale, gadd, HeadFold{});
-  }
+    hipLaunchKernelGGL((evonorm_bwd_apply_kernel<T, NT>), g2, dim3(256), lds2, st, (const T*)dz, dzpitch, (const T*)x, xpitch, mean_rstd,
+                       gamma, red, (T*)dx, dxpitch, dgamma, dbeta, chan_sums, dconvbias, N, voxels, C, groups, (uint32_t*)amax, gscale,
+                       gadd, HeadFold{});
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -1954,7 +1872,7 @@ extern "C" int BRATS_API(brats_evonorm_bwd_tiles)(const float* tile_stats, int t
     BRATS_FAIL(BRATS_E_ARG, "evonorm_bwd_tiles: null pointer");
   if (dtype != BRATS_BF16 && dtype != BRATS_F32) BRATS_FAIL(BRATS_E_UNSUPPORTED, "evonorm_bwd_tiles: 16-bit or f32 (split-precision mode) activations");
   if (dconvbias && !chan_sums) BRATS_FAIL(BRATS_E_ARG, "evonorm_bwd_tiles: dconvbias needs the forward per-channel sums");
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (C % vw || C % groups || dzpitch % vw || xpitch % vw || dxpitch % vw || C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "evonorm_bwd_tiles: C=%d / pitches must be multiples of %d", C, vw);
   hipStream_t st = (hipStream_t)s;
@@ -1965,21 +1883,15 @@ extern "C" int BRATS_API(brats_evonorm_bwd_tiles)(const float* tile_stats, int t
   const int splits = gn_splits(tiles_per_sample);
   hipLaunchKernelGGL(gn_chan_reduce_kernel, dim3((C + 15) / 16, N, splits), dim3(256), 0, st, tile_stats, tiles_per_sample, C, part);
   hipLaunchKernelGGL(evonorm_bwd_tiles_prep_kernel, dim3((N * C + 255) / 256), dim3(256), 0, st, part, splits, N, C, groups, mean_rstd, beta, s12);
-  const int cv = C / vw, vl = 256 / cv;
-  size_t gx = ((size_t)voxels + (size_t)vl * 8 - 1) / ((size_t)vl * 8);
-  const bool big = dtype == BRATS_BF16 && stream_nt((size_t)N * voxels * C * 2);
-  const size_t cap = big ? EVO_SIDE_MAX_BLOCKS : 512;
-  dim3 g2((unsigned)(gx < 1 ? 1 : (gx > cap ? cap : gx)), N);
-  const size_t lds2 = (size_t)(3 * C + vl * C) * sizeof(float);
-  if (dtype == BRATS_F32)
-    hipLaunchKernelGGL((evonorm_bwd_apply_side_kernel<float, false>), g2, dim3(256), lds2, st, (const float*)dz, dzpitch, (const float*)x, xpitch,
-                       mean_rstd, gamma, s12, (float*)dx, dxpitch, side_part, voxels, C, groups, (uint32_t*)amax);
-  else if (big)
-    hipLaunchKernelGGL((evonorm_bwd_apply_side_kernel<bf16_t, true>), g2, dim3(256), lds2, st, (const bf16_t*)dz, dzpitch, (const bf16_t*)x, xpitch,
-                       mean_rstd, gamma, s12, (bf16_t*)dx, dxpitch, side_part, voxels, C, groups, (uint32_t*)amax);
-  else
-    hipLaunchKernelGGL((evonorm_bwd_apply_side_kernel<bf16_t, false>), g2, dim3(256), lds2, st, (const bf16_t*)dz, dzpitch, (const bf16_t*)x, xpitch,
-                       mean_rstd, gamma, s12, (bf16_t*)dx, dxpitch, side_part, voxels, C, groups, (uint32_t*)amax);
+  const Walk w = voxel_walk(vw, voxels, C);
+  const bool big = big_tensor16(dtype, (size_t)N * voxels * C);
+  dim3 g2(w.grid(big ? EVO_SIDE_MAX_BLOCKS : 512), N);
+  const size_t lds2 = (size_t)(3 * C + w.vl * C) * sizeof(float);
+  with_stream16(dtype, big, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((evonorm_bwd_apply_side_kernel<T, decltype(nt)::value>), g2, dim3(256), lds2, st, (const T*)dz, dzpitch, (const T*)x,
+                       xpitch, mean_rstd, gamma, s12, (T*)dx, dxpitch, side_part, voxels, C, groups, (uint32_t*)amax);
+  });
   BRATS_CHECK_LAUNCH();
   if (int rc = brats_ordered_sum(side_part, side, (int)g2.x, N * C * 2, st)) return rc;
   hipLaunchKernelGGL(evonorm_bwd_tiles_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, st, s12, side, mean_rstd, gamma, chan_sums, dgamma,
@@ -2002,31 +1914,31 @@ static int evonorm_se_bwd_impl(const void* dout, int dopitch, const void* x, int
                                const float* gate1p, const float* w1, const float* w2, float* gadd, float* dw1, float* db1, float* dw2,
                                float* db2, int Ch, EvoHead eh, int mode, int K, float* dhw, float* dhb, int dtype, int N, int voxels,
                                int C, int groups, float* amax, hipStream_t st) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   const bool head = mode > 0;
   if (!x || !dx || !ws || !mean_rstd || !gamma || !beta || !gate1p || !gadd) BRATS_FAIL(BRATS_E_ARG, "evonorm_se_bwd: null pointer");
   if (dconvbias && !chan_sums) BRATS_FAIL(BRATS_E_ARG, "evonorm_se_bwd: dconvbias needs the forward per-channel sums");
   if (C % vw || C % groups || (mode == 0 && dopitch % vw) || xpitch % vw || dxpitch % vw || C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "evonorm_se_bwd: C=%d / pitches must be multiples of %d", C, vw);
-  const int cv = C / vw, vl = 256 / cv;
-  size_t gx = ((size_t)voxels + (size_t)vl * 8 - 1) / ((size_t)vl * 8);
-  const bool big = dtype == BRATS_BF16 && stream_nt((size_t)N * voxels * C * 2);
-  const size_t cap1 = big ? CHAN_MAX_BLOCKS : 512, cap2 = big ? 8192 : 2048;
-  dim3 g1((unsigned)(gx < 1 ? 1 : (gx > cap1 ? cap1 : gx)), N);
-  const size_t lds1 = (size_t)(vl * C + (head ? vl * K : 0)) * sizeof(float);  // (one value plane at a time)
-  dim3 g2((unsigned)(gx < 1 ? 1 : (gx > cap2 ? cap2 : gx)), N);
+  const Walk w = voxel_walk(vw, voxels, C);
+  const bool big = big_tensor16(dtype, (size_t)N * voxels * C);
+  dim3 g1(w.grid(big ? CHAN_MAX_BLOCKS : 512), N);
+  const size_t lds1 = (size_t)(w.vl * C + (head ? w.vl * K : 0)) * sizeof(float);  // (one value plane at a time)
+  dim3 g2(w.grid(big ? 8192 : 2048), N);
   const size_t lds2 = (size_t)3 * C * sizeof(float);
   float* raw5 = ws;
   float* red3 = ws + (size_t)(1 + CHAN_MAX_BLOCKS) * N * C * 5;
   eh.mean_rstd = mean_rstd; eh.gamma = gamma; eh.beta = beta; eh.gate1p = gate1p; eh.groups = groups;
   const float* nof = nullptr;
-#define EVO_P1(T, NT, HK) hipLaunchKernelGGL((evonorm_bwd_reduce_kernel<T, NT, true, HK>), g1, dim3(256), lds1, st, (const T*)dout, dopitch, \
-                                             (const T*)x, xpitch, raw5, voxels, C, nof, nof, eh)
-#define EVO_P2(T, NT, HK) hipLaunchKernelGGL((evonorm_bwd_apply_kernel<T, NT, HK>), g2, dim3(256), lds2, st, (const T*)dout, dopitch, \
-                                             (const T*)x, xpitch, mean_rstd, gamma, red3, (T*)dx, dxpitch, dgamma, dbeta, chan_sums, \
-                                             dconvbias, N, voxels, C, groups, (uint32_t*)amax, gate1p, gadd, eh.hf)
-#define EVO_ALL(P, HK) do { if (big) P(bf16_t, true, HK); else if (dtype == BRATS_BF16) P(bf16_t, false, HK); else P(float, false, HK); } while (0)
-  if (mode > 0) EVO_ALL(EVO_P1, 3); else if (mode < 0) EVO_ALL(EVO_P1, -1); else EVO_ALL(EVO_P1, 0);
+  // pass(T, NT, HK) for the form this call takes
+  auto with_form = [&](auto&& pass) {
+    with_fold(mode, [&](auto hk) { with_stream16(dtype, big, [&](auto t, auto nt) { pass(t, nt, hk); }); });
+  };
+  with_form([&](auto t, auto nt, auto hk) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((evonorm_bwd_reduce_kernel<T, decltype(nt)::value, true, decltype(hk)::value>), g1, dim3(256), lds1, st,
+                       (const T*)dout, dopitch, (const T*)x, xpitch, raw5, voxels, C, nof, nof, eh);
+  });
   BRATS_CHECK_LAUNCH();
   brats_ordered_sum(raw5 + (size_t)N * C * 5, raw5, (int)g1.x, N * C * 5, st);
   if (head) brats_ordered_sum2(eh.hf.hpart, dhw, K * C, dhb, N * (int)g1.x, K * C + K, st);  // totals into dhw [K][C], dhb [K]
@@ -2036,10 +1948,12 @@ static int evonorm_se_bwd_impl(const void* dout, int dopitch, const void* x, int
   if (int rc = brats_se_bwd_launch(nullptr, fold, se_chansum, 1.f / (float)voxels, hidden, gate1p, w1, w2, gadd, dw1, db1, dw2, db2,
                                    N, C, Ch, st))
     return rc;
-  if (mode > 0) EVO_ALL(EVO_P2, 3); else if (mode < 0) EVO_ALL(EVO_P2, -1); else EVO_ALL(EVO_P2, 0);
-#undef EVO_ALL
-#undef EVO_P1
-#undef EVO_P2
+  with_form([&](auto t, auto nt, auto hk) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((evonorm_bwd_apply_kernel<T, decltype(nt)::value, decltype(hk)::value>), g2, dim3(256), lds2, st, (const T*)dout,
+                       dopitch, (const T*)x, xpitch, mean_rstd, gamma, red3, (T*)dx, dxpitch, dgamma, dbeta, chan_sums, dconvbias, N,
+                       voxels, C, groups, (uint32_t*)amax, gate1p, gadd, eh.hf);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -2076,7 +1990,7 @@ extern "C" int BRATS_API(brats_evonorm_se_bwd_pool)(const void* dskip, int dskip
                                          const float* se_chansum, const float* hidden, const float* gate1p, const float* w1,
                                          const float* w2, float* gadd, float* dw1, float* db1, float* dw2, float* db2, int Ch,
                                          int dtype, int N, int C, int groups, float* amax, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!dskip || !dpool || !argmax || ((D | H | W) & 1) || dskip_pitch % vw || dpool_pitch % vw)
     BRATS_FAIL(BRATS_E_ARG, "evonorm_se_bwd_pool: null pointer / odd spatial size / pitch not a multiple of %d", vw);
   EvoHead eh;
@@ -2157,21 +2071,18 @@ __global__ void channel_dot_kernel(const T* __restrict__ a, int apitch, const T*
 
 extern "C" int BRATS_API(brats_channel_dot)(const void* a, int apitch, const void* b, int bpitch, float* out, int dtype, int N, int voxels,
                                  int C, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!a || !out || C % vw || apitch % vw || (b && bpitch % vw) || C / vw > 256) BRATS_FAIL(BRATS_E_ARG, "channel_dot: bad argument");
   hipStream_t st = (hipStream_t)s;
-  const int cv = C / vw, vl = 256 / cv;
-  size_t gx = ((size_t)voxels + (size_t)vl * 8 - 1) / ((size_t)vl * 8);
-  const bool big = dtype == BRATS_BF16 && stream_nt((size_t)N * voxels * C * 2);
-  const size_t cap = big ? CHAN_MAX_BLOCKS : 512;
-  dim3 grid((unsigned)(gx < 1 ? 1 : (gx > cap ? cap : gx)), N);
-  const size_t lds = (size_t)vl * C * sizeof(float);
-  if (big)
-    hipLaunchKernelGGL((channel_dot_kernel<bf16_t, true>), grid, dim3(256), lds, st, (const bf16_t*)a, apitch, (const bf16_t*)b, bpitch, out, voxels, C);
-  else if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(channel_dot_kernel<bf16_t>, grid, dim3(256), lds, st, (const bf16_t*)a, apitch, (const bf16_t*)b, bpitch, out, voxels, C);
-  else
-    hipLaunchKernelGGL(channel_dot_kernel<float>, grid, dim3(256), lds, st, (const float*)a, apitch, (const float*)b, bpitch, out, voxels, C);
+  const Walk w = voxel_walk(vw, voxels, C);
+  const bool big = big_tensor16(dtype, (size_t)N * voxels * C);
+  dim3 grid(w.grid(big ? CHAN_MAX_BLOCKS : 512), N);
+  const size_t lds = (size_t)w.vl * C * sizeof(float);
+  with_stream16(dtype, big, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((channel_dot_kernel<T, decltype(nt)::value>), grid, dim3(256), lds, st, (const T*)a, apitch, (const T*)b, bpitch, out,
+                       voxels, C);
+  });
   brats_ordered_sum(out + (size_t)N * C, out, (int)grid.x, N * C, st);
   BRATS_CHECK_LAUNCH();
   return 0;
@@ -2229,19 +2140,15 @@ __global__ void channel_scale_kernel(const T* __restrict__ a, int apitch, const 
 
 extern "C" int BRATS_API(brats_channel_scale)(const void* a, int apitch, const float* scale, const float* add, void* dst, int dpitch,
                                    int dtype, int N, int voxels, int C, float* amax, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!a || !scale || !dst || C % vw || apitch % vw || dpitch % vw) BRATS_FAIL(BRATS_E_ARG, "channel_scale: bad argument");
-  const bool big = dtype == BRATS_BF16 && stream_nt((size_t)N * voxels * C * 2);
-  dim3 grid(stream_grid((size_t)voxels * (C / vw), 256) * (big ? 2 : 1), N);  // (4096 blocks per sample; 8192 for the large tensors)
-  if (big)
-    hipLaunchKernelGGL((channel_scale_kernel<bf16_t, true>), grid, dim3(256), 2 * C * sizeof(float), (hipStream_t)s, (const bf16_t*)a, apitch,
-                       scale, add, (bf16_t*)dst, dpitch, voxels, C, (uint32_t*)amax);
-  else if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(channel_scale_kernel<bf16_t>, grid, dim3(256), 2 * C * sizeof(float), (hipStream_t)s, (const bf16_t*)a, apitch,
-                       scale, add, (bf16_t*)dst, dpitch, voxels, C, (uint32_t*)amax);
-  else
-    hipLaunchKernelGGL(channel_scale_kernel<float>, grid, dim3(256), 2 * C * sizeof(float), (hipStream_t)s, (const float*)a, apitch,
-                       scale, add, (float*)dst, dpitch, voxels, C, (uint32_t*)amax);
+  const bool big = big_tensor16(dtype, (size_t)N * voxels * C);
+  dim3 grid(stream_grid((size_t)voxels * (C / vw), 256, 4096) * (big ? 2 : 1), N);  // (4096 blocks per sample; 8192 for the large tensors)
+  with_stream16(dtype, big, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((channel_scale_kernel<T, decltype(nt)::value>), grid, dim3(256), 2 * C * sizeof(float), (hipStream_t)s, (const T*)a,
+                       apitch, scale, add, (T*)dst, dpitch, voxels, C, (uint32_t*)amax);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }

@@ -5,10 +5,7 @@
 #include "twin_begin.hpp"
 #include "common.hpp"
 
-static inline int stream_grid(size_t total, int block) {
-  size_t b = (total + block - 1) / block;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+constexpr int POOL_MAX_BLOCKS = 8192;  // of the grid-stride passes (stream_grid)
 
 // ---- pooling -----------------------------------------------------------------------------------
 // argmax (optional): one byte per (pooled voxel, channel) = the window index 0..7 (d, h, w order) of torch's first arg-max;
@@ -181,36 +178,34 @@ __global__ void __launch_bounds__(256) maxpool2_bwd_idx_kernel(const uint8_t* __
 extern "C" int BRATS_API(brats_maxpool2_bwd_idx)(const unsigned char* argmax, const void* dy, int dypitch, const void* dx_skip,
                                       int dxskip_pitch, void* dx, int dxpitch, int dtype, int N, int C, int D, int H, int W,
                                       int with_avg, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!argmax || !dy || !dx || C % vw || dypitch % vw || dxpitch % vw || (dx_skip && dxskip_pitch % vw) || ((D | H | W) & 1) ||
       C / vw > 256)
     BRATS_FAIL(BRATS_E_ARG, "maxpool2_bwd_idx: bad argument");
   int xb = 256 / (C / vw);
   if (xb > W) xb = W;
   const size_t items = (size_t)(D / 2) * (H / 2) * ((W + xb - 1) / xb);
-  dim3 grid((unsigned)(items < 1 ? 1 : (items > 8192 ? 8192 : items)), N);
-  if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(maxpool2_bwd_idx_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, argmax, (const bf16_t*)dy, dypitch,
-                       (const bf16_t*)dx_skip, dxskip_pitch, (bf16_t*)dx, dxpitch, C, D, H, W, with_avg);
-  else
-    hipLaunchKernelGGL(maxpool2_bwd_idx_kernel<float>, grid, dim3(256), 0, (hipStream_t)s, argmax, (const float*)dy, dypitch,
-                       (const float*)dx_skip, dxskip_pitch, (float*)dx, dxpitch, C, D, H, W, with_avg);
+  dim3 grid(stream_grid(items, 1, POOL_MAX_BLOCKS), N);
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(maxpool2_bwd_idx_kernel<T>, grid, dim3(256), 0, (hipStream_t)s, argmax, (const T*)dy, dypitch, (const T*)dx_skip,
+                       dxskip_pitch, (T*)dx, dxpitch, C, D, H, W, with_avg);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int BRATS_API(brats_maxpool2_fwd)(const void* x, int xpitch, void* y, int ypitch, unsigned char* argmax, int dtype, int N,
                                   int C, int D, int H, int W, int with_avg, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!x || !y || C % vw || xpitch % vw || ypitch % vw || (D | H | W) & 1)
     BRATS_FAIL(BRATS_E_ARG, "maxpool2_fwd: C/pitch multiple of %d and even spatial dims required", vw);
   const size_t total = (size_t)N * (D / 2) * (H / 2) * (W / 2) * (C / vw);
-  if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(maxpool2_fwd_kernel<bf16_t>, dim3(stream_grid(total, 256)), dim3(256), 0, (hipStream_t)s,
-                       (const bf16_t*)x, xpitch, (bf16_t*)y, ypitch, N, C, D, H, W, with_avg, argmax);
-  else
-    hipLaunchKernelGGL(maxpool2_fwd_kernel<float>, dim3(stream_grid(total, 256)), dim3(256), 0, (hipStream_t)s,
-                       (const float*)x, xpitch, (float*)y, ypitch, N, C, D, H, W, with_avg, argmax);
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(maxpool2_fwd_kernel<T>, dim3(stream_grid(total, 256, POOL_MAX_BLOCKS)), dim3(256), 0, (hipStream_t)s, (const T*)x,
+                       xpitch, (T*)y, ypitch, N, C, D, H, W, with_avg, argmax);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -219,19 +214,16 @@ extern "C" int BRATS_API(brats_maxpool2_bwd)(const void* x, int xpitch, const vo
                                   const void* dx_skip, int dxskip_pitch, void* dx, int dxpitch, int dtype, int N, int C,
                                   int D, int H, int W, int with_avg, brats_stream_t s) {
   (void)y; (void)ypitch;  // arg-max is recomputed from x
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!x || !dy || !dx || C % vw || xpitch % vw || dypitch % vw || dxpitch % vw || (dx_skip && dxskip_pitch % vw) ||
       (D | H | W) & 1)
     BRATS_FAIL(BRATS_E_ARG, "maxpool2_bwd: bad argument");
   const size_t total = (size_t)N * (D / 2) * (H / 2) * (W / 2) * (C / vw);
-  if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(maxpool2_bwd_kernel<bf16_t>, dim3(stream_grid(total, 128)), dim3(128), 0, (hipStream_t)s,
-                       (const bf16_t*)x, xpitch, (const bf16_t*)dy, dypitch, (const bf16_t*)dx_skip, dxskip_pitch,
-                       (bf16_t*)dx, dxpitch, N, C, D, H, W, with_avg);
-  else
-    hipLaunchKernelGGL(maxpool2_bwd_kernel<float>, dim3(stream_grid(total, 128)), dim3(128), 0, (hipStream_t)s,
-                       (const float*)x, xpitch, (const float*)dy, dypitch, (const float*)dx_skip, dxskip_pitch, (float*)dx,
-                       dxpitch, N, C, D, H, W, with_avg);
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(maxpool2_bwd_kernel<T>, dim3(stream_grid(total, 128, POOL_MAX_BLOCKS)), dim3(128), 0, (hipStream_t)s, (const T*)x,
+                       xpitch, (const T*)dy, dypitch, (const T*)dx_skip, dxskip_pitch, (T*)dx, dxpitch, N, C, D, H, W, with_avg);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -400,7 +392,7 @@ __global__ void __launch_bounds__(256) upsample2_fwd_kernel(const T* __restrict_
 
 extern "C" int BRATS_API(brats_upsample_fwd)(const void* x, int xpitch, void* y, int ypitch, int dtype, int N, int C, int D, int H,
                                   int W, int scale, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!x || !y || C % vw || xpitch % vw || ypitch % vw || scale < 1)
     BRATS_FAIL(BRATS_E_ARG, "upsample_fwd: C/pitch must be multiples of %d", vw);
   const size_t rows = (size_t)N * D * scale * H * scale;
@@ -409,37 +401,29 @@ extern "C" int BRATS_API(brats_upsample_fwd)(const void* x, int xpitch, void* y,
   if (scale == 2 && H % 2 == 0 && N <= 65535 && D <= 65535) {
     const dim3 g2(H / 2, D, N);  // (Ho / 4, Do / 2, N)
     const size_t ldsx = (size_t)12 * W * C * 2;
+    const bool big = big_tensor16(dtype, (size_t)N * D * H * W * 8 * C);  // output beyond the Infinity Cache: non-temporal stores
+    auto go = [&](auto t, auto nt, auto in_lds) {
+      using T = typename decltype(t)::type;
+      constexpr bool LDSX = decltype(in_lds)::value;
+      hipLaunchKernelGGL((upsample2_fwd_kernel<T, decltype(nt)::value, LDSX>), g2, dim3(256), LDSX ? ldsx : 0, (hipStream_t)s, (const T*)x,
+                         xpitch, (T*)y, ypitch, C, D, H, W, sd, sh, sw);
+    };
     if (dtype == BRATS_BF16 && ldsx <= 80 * 1024) {  // two blocks per CU with their input rows in LDS
       static std::atomic<uint64_t> attr_a{0}, attr_b{0};
       BRATS_ENSURE_LDS_ATTR((upsample2_fwd_kernel<bf16_t, true, true>), 80 * 1024, attr_a);
       BRATS_ENSURE_LDS_ATTR((upsample2_fwd_kernel<bf16_t, false, true>), 80 * 1024, attr_b);
-      if (stream_nt((size_t)N * D * H * W * 8 * C * 2))
-        hipLaunchKernelGGL((upsample2_fwd_kernel<bf16_t, true, true>), g2, dim3(256), ldsx, (hipStream_t)s, (const bf16_t*)x, xpitch, (bf16_t*)y,
-                           ypitch, C, D, H, W, sd, sh, sw);
-      else
-        hipLaunchKernelGGL((upsample2_fwd_kernel<bf16_t, false, true>), g2, dim3(256), ldsx, (hipStream_t)s, (const bf16_t*)x, xpitch, (bf16_t*)y,
-                           ypitch, C, D, H, W, sd, sh, sw);
-      BRATS_CHECK_LAUNCH();
-      return 0;
+      with_flag(big, [&](auto nt) { go(type_tag<bf16_t>{}, nt, std::true_type{}); });
+    } else {
+      with_stream16(dtype, big, [&](auto t, auto nt) { go(t, nt, std::false_type{}); });
     }
-    if (dtype == BRATS_BF16 && stream_nt((size_t)N * D * H * W * 8 * C * 2))  // output beyond the Infinity Cache: non-temporal stores
-      hipLaunchKernelGGL((upsample2_fwd_kernel<bf16_t, true>), g2, dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, xpitch, (bf16_t*)y, ypitch,
-                         C, D, H, W, sd, sh, sw);
-    else if (dtype == BRATS_BF16)
-      hipLaunchKernelGGL(upsample2_fwd_kernel<bf16_t>, g2, dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, xpitch, (bf16_t*)y, ypitch,
-                         C, D, H, W, sd, sh, sw);
-    else
-      hipLaunchKernelGGL(upsample2_fwd_kernel<float>, g2, dim3(256), 0, (hipStream_t)s, (const float*)x, xpitch, (float*)y, ypitch,
-                         C, D, H, W, sd, sh, sw);
     BRATS_CHECK_LAUNCH();
     return 0;
   }
-  if (dtype == BRATS_BF16)
-    hipLaunchKernelGGL(upsample_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, xpitch,
-                       (bf16_t*)y, ypitch, N, C, D, H, W, scale, sd, sh, sw);
-  else
-    hipLaunchKernelGGL(upsample_fwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const float*)x, xpitch,
-                       (float*)y, ypitch, N, C, D, H, W, scale, sd, sh, sw);
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(upsample_fwd_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)x, xpitch, (T*)y, ypitch, N, C, D, H, W,
+                       scale, sd, sh, sw);
+  });
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -494,12 +478,12 @@ int brats_lerp_adjoint_f32_planes(const float* in, float* out, size_t outer, int
   if (inner % 4 == 0 && (((size_t)in | (size_t)out) & 15) == 0) {
     // four neighbouring inner elements per thread (16-byte loads): these planes are bound by the NUMBER of vector-memory
     // instructions (one per candidate l per thread), not by their bytes
-    hipLaunchKernelGGL((lerp_adjoint_kernel<float, float, 4>), dim3(stream_grid(total / 4, 256)), dim3(256), 0, st, in, 4, out, 4,
-                       outer, Lout, Lin, inner / 4, 4, ac_scale(Lin, Lout));
+    hipLaunchKernelGGL((lerp_adjoint_kernel<float, float, 4>), dim3(stream_grid(total / 4, 256, POOL_MAX_BLOCKS)), dim3(256), 0, st, in, 4,
+                       out, 4, outer, Lout, Lin, inner / 4, 4, ac_scale(Lin, Lout));
     BRATS_CHECK_LAUNCH();
     return 0;
   }
-  hipLaunchKernelGGL((lerp_adjoint_kernel<float, float, 1>), dim3(stream_grid(total, 256)), dim3(256), 0, st, in, 1, out, 1,
+  hipLaunchKernelGGL((lerp_adjoint_kernel<float, float, 1>), dim3(stream_grid(total, 256, POOL_MAX_BLOCKS)), dim3(256), 0, st, in, 1, out, 1,
                      outer, Lout, Lin, inner, 1, ac_scale(Lin, Lout));
   BRATS_CHECK_LAUNCH();
   return 0;
@@ -911,15 +895,15 @@ static int upsample_bwd_t(const T* dy, int dypitch, T* dx, int dxpitch, char* tm
   T* t2 = (T*)(tmp + ((a_elems * sizeof(T) + 255) / 256 * 256));
   // D axis: [N][Do][Ho*Wo][C] -> [N][D][Ho*Wo][C]
   size_t total = (size_t)N * D * Ho * Wo * (C / VW);
-  hipLaunchKernelGGL((lerp_adjoint_kernel<T, T, VW>), dim3(stream_grid(total, 256)), dim3(256), 0, st, dy, dypitch, t1, C,
+  hipLaunchKernelGGL((lerp_adjoint_kernel<T, T, VW>), dim3(stream_grid(total, 256, POOL_MAX_BLOCKS)), dim3(256), 0, st, dy, dypitch, t1, C,
                      (size_t)N, Do, D, (size_t)Ho * Wo, C, ac_scale(D, Do));
   // H axis: [N*D][Ho][Wo][C] -> [N*D][H][Wo][C]
   total = (size_t)N * D * H * Wo * (C / VW);
-  hipLaunchKernelGGL((lerp_adjoint_kernel<T, T, VW>), dim3(stream_grid(total, 256)), dim3(256), 0, st, (const T*)t1, C, t2, C,
+  hipLaunchKernelGGL((lerp_adjoint_kernel<T, T, VW>), dim3(stream_grid(total, 256, POOL_MAX_BLOCKS)), dim3(256), 0, st, (const T*)t1, C, t2, C,
                      (size_t)N * D, Ho, H, (size_t)Wo, C, ac_scale(H, Ho));
   // W axis: [N*D*H][Wo][1][C] -> [N*D*H][W][1][C(pitch)]
   total = (size_t)N * D * H * W * (C / VW);
-  hipLaunchKernelGGL((lerp_adjoint_kernel<T, T, VW>), dim3(stream_grid(total, 256)), dim3(256), 0, st, (const T*)t2, C, dx,
+  hipLaunchKernelGGL((lerp_adjoint_kernel<T, T, VW>), dim3(stream_grid(total, 256, POOL_MAX_BLOCKS)), dim3(256), 0, st, (const T*)t2, C, dx,
                      dxpitch, (size_t)N * D * H, Wo, W, (size_t)1, C, ac_scale(W, Wo));
   BRATS_CHECK_LAUNCH();
   return 0;
@@ -927,12 +911,11 @@ static int upsample_bwd_t(const T* dy, int dypitch, T* dx, int dxpitch, char* tm
 
 extern "C" int BRATS_API(brats_upsample_bwd)(const void* dy, int dypitch, void* dx, int dxpitch, void* tmp, int dtype, int N, int C,
                                   int D, int H, int W, int scale, brats_stream_t s) {
-  const int vw = dtype == BRATS_BF16 ? 8 : 4;
+  const int vw = vec_width(dtype);
   if (!dy || !dx || !tmp || C % vw || dypitch % vw || dxpitch % vw) BRATS_FAIL(BRATS_E_ARG, "upsample_bwd: bad argument");
-  if (dtype == BRATS_BF16)
-    return upsample_bwd_t<bf16_t>((const bf16_t*)dy, dypitch, (bf16_t*)dx, dxpitch, (char*)tmp, N, C, D, H, W, scale,
-                                  (hipStream_t)s);
-  return upsample_bwd_t<float>((const float*)dy, dypitch, (float*)dx, dxpitch, (char*)tmp, N, C, D, H, W, scale,
-                               (hipStream_t)s);
+  return with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return upsample_bwd_t<T>((const T*)dy, dypitch, (T*)dx, dxpitch, (char*)tmp, N, C, D, H, W, scale, (hipStream_t)s);
+  });
 }
 #include "twin_end.hpp"

@@ -1,6 +1,6 @@
 """-m gpu: the size-selected forms of the streaming norm / pool / up-sampling kernels, one op at a time.
 
-From 256 MiB on (csrc/common.hpp stream_nt(), csrc/norm.hip big_tensor()) these kernels run another template instantiation
+From 256 MiB on (csrc/common.hpp stream_nt(), big_tensor(), big_tensor16()) these kernels run another template instantiation
 (non-temporal loads and stores) under other grid caps; the statistics finalize takes two launches from 32768 (tile, channel)
 pairs per group on, and the slab reduction has more than one slab from 128 tiles on.  The other op-level tests run 1 - 3
 blocks per sample and reach none of this, so every op is run here at the smallest shape that crosses its switch, on both
@@ -28,7 +28,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-BIG = 256 << 20            # bytes; csrc/common.hpp:128 stream_nt() (csrc/norm.hip:11 big_tensor()): >= BIG takes the large form
+BIG = 256 << 20            # bytes; csrc/common.hpp stream_nt() (big_tensor(), big_tensor16()): >= BIG takes the large form
 S = (112, 112, 112)        # 1,404,928 voxels: x 48 channels x 2 B = 134.9 MB (N = 1: normal, capped grids), 269.7 MB (N = 2: big)
 S32 = (80, 80, 80)         # f32 x 48 channels = 98.3 MB: the normal form of f32 tensors with gx = 3048 > 2048 blocks
 G = 8                      # groups
