@@ -269,6 +269,18 @@ namespace brats_f16 {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// compute units of the current device, asked once; 256 (an MI355X) where no device answers: the workspace-size functions run
+// without one
+static inline int device_cus() {
+  static int ncu = 0;
+  if (!ncu) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+  }
+  return ncu;
+}
+
 // ---- run-time storage type / streaming form -> template arguments -------------------------------
 // The helpers turn the run-time choice into tag arguments of a generic lambda, so that a launch site writes the kernel's
 // argument list once:   with_storage(dtype, [&](auto t) { using T = typename decltype(t)::type; ...kernel<T>... (const T*)x ... });

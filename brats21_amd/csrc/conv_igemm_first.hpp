@@ -209,13 +209,7 @@ static int conv_launch_first(const ConvParams& p, hipStream_t st) {
   static std::atomic<uint64_t> attr_done{0};
   BRATS_ENSURE_LDS_ATTR(kern, FirstGeom::LDS_BYTES, attr_done);
   const int ntiles = p.N * p.tz * p.ty * p.tx;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-  }
+  const int cus = device_cus();
   const int grid = (ntiles < 2 * cus ? ntiles : 2 * cus) & ~7;  // (a multiple of 8: the same number of workgroups on every XCD; conv_first_ok wants >= 2048 tiles)
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), FirstGeom::LDS_BYTES, st, p, ntiles);
   BRATS_CHECK_LAUNCH();

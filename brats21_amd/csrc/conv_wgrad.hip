@@ -1053,25 +1053,73 @@ __global__ void dbias_kernel(const T* __restrict__ dy, int pitch, float* __restr
   }
   if (threadIdx.x == 0) db[c] = red[0];
 }
+static void wgrad_dbias_launch(int dtype, const void* dy, int dypitch, float* dbias, size_t vox, int cout, hipStream_t st) {
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dbias_kernel<T>, dim3(cout), dim3(256), 0, st, (const T*)dy, dypitch, dbias, vox, cout);
+  });
+}
 
-// spatial groups: nlane tile ranges (8 = one per XCD) x g8 interleaved sub-groups; total workgroups of the tap-plane
-// kernel = 3 (tap planes) * nlane * g8 * cot * cit ~ 2 per CU.  Every (range, sub-group) pair writes its own f32 slab of
-// the whole dW, so small volumes (16^3 levels: 32 tiles, 27 x 384 x 384 weights) use fewer ranges: with 8 the slab
-// traffic (127 MB written + read) cost as much as the MFMAs.
+// ---- host side: one problem, one plan ------------------------------------------------------------------------------
+// the operands and the shape of one weight-gradient problem (x2 / c2 / p2: the second source of a concatenated input, or 0)
+struct WgradArgs {
+  const void* x1; int c1, p1;
+  const void* x2; int c2, p2;
+  const void* dy; int dyp;
+  int N, D, H, W, cout;
+  int cin() const { return c1 + c2; }
+  size_t vox() const { return (size_t)N * D * H * W; }
+};
+// the shape alone, as the workspace-size functions know it
+static WgradArgs wgrad_shape(int N, int D, int H, int W, int c1, int c2, int cout) {
+  return WgradArgs{nullptr, c1, 0, nullptr, c2 > 0 ? c2 : 0, 0, nullptr, 0, N, D, H, W, cout};
+}
+// staged pieces are addressed by 32-bit byte offsets inside one sample (buffer_load voffset): 0, or the pitch that breaks it
+static int wgrad_sample_overflow(const WgradArgs& a, int esize) {
+  const int mp = a.p1 > a.p2 ? (a.p1 > a.dyp ? a.p1 : a.dyp) : (a.p2 > a.dyp ? a.p2 : a.dyp);
+  return (double)a.D * a.H * a.W * mp * esize >= 2147483648.0 ? mp : 0;
+}
+
+struct WgradTileGrid { int tz, ty, tx, ntiles; };
+static WgradTileGrid wgrad_tile_grid(const WgradArgs& a, int TZ = WG_TZ, int TY = WG_TY, int TX = WG_TX) {
+  WgradTileGrid t{ceil_div(a.D, TZ), ceil_div(a.H, TY), ceil_div(a.W, TX), 0};
+  t.ntiles = a.N * t.tz * t.ty * t.tx;
+  return t;
+}
+static WgradParams wgrad_params(const WgradArgs& a, float* ws, const WgradTileGrid& t, int nlane, int nsplit, int ntaps, int dil) {
+  WgradParams p{};
+  p.x1 = a.x1; p.x2 = a.x2; p.c1 = a.c1; p.c2 = a.c2; p.p1 = a.p1; p.p2 = a.p2;
+  p.dy = a.dy; p.dyp = a.dyp; p.ws = ws;
+  p.N = a.N; p.D = a.D; p.H = a.H; p.W = a.W; p.cin = a.cin(); p.cout = a.cout;
+  p.tz = t.tz; p.ty = t.ty; p.tx = t.tx; p.ntiles = t.ntiles;
+  p.nlane = nlane; p.nsplit = nsplit; p.ntaps = ntaps; p.dil = dil;
+  return p;
+}
+
+// spatial groups: nlane tile ranges (8 = one per XCD) x g8 interleaved sub-groups.  Every (range, sub-group) pair writes its
+// own f32 slab of the whole dW, so small volumes (16^3 levels: 32 tiles, 27 x 384 x 384 weights) use fewer ranges: with 8
+// the slab traffic (127 MB written + read) cost as much as the MFMAs.
 static int wgrad_nlane(int ntiles) {
   int nl = 8;
   while (nl > 1 && ntiles / nl < 16) nl >>= 1;
   return nl;
 }
-static int wgrad_g8(int ntiles, int cotiles, int citiles) {
-  const int nl = wgrad_nlane(ntiles);
-  int g8 = ceil_div(512, 3 * nl * cotiles * citiles);
-  const int cap = ceil_div(ntiles, nl);
+// split rule of the tap-plane and shifted-tap kernels, whose workgroups own one of `groups` tap groups (3 tap planes, or
+// ntaps shifted taps) of one channel block: groups * nlane * g8 * cot * cit ~ 512 workgroups = 2 per CU
+static int wgrad_split_g8(int ntiles, int nlane, int groups, int cot, int cit) {
+  int g8 = ceil_div(512, groups * nlane * cot * cit);
+  const int cap = ceil_div(ntiles, nlane);
   if (g8 > cap) g8 = cap;
-  if (g8 < 1) g8 = 1;
-  return g8;
+  return g8 < 1 ? 1 : g8;
 }
-static int wgrad_nsplit(int ntiles, int cotiles, int citiles) { return wgrad_nlane(ntiles) * wgrad_g8(ntiles, cotiles, citiles); }
+// blocks rule of the all-taps kernels (16-bit and e4m3), whose persistent workgroups own all 27 taps of one channel block:
+// nlane * g8 * blocks ~ one workgroup per CU.  false: too few tiles per workgroup to amortise 132 accumulators x 27 taps of slab
+static bool wgrad_blocks_g8(int ntiles, int blocks, int* nlane, int* g8) {
+  *nlane = wgrad_nlane(ntiles);
+  *g8 = ceil_div(device_cus(), *nlane * blocks);
+  if (*g8 < 1) *g8 = 1;
+  return ntiles >= 4 * *nlane * *g8;
+}
 static void wgrad_tiles(int dtype, int c1, int c2, int cout, int* cof, int* cif) {
   const int co16 = ceil_div(cout, 16);
   *cof = co16 % 3 == 0 ? 3 : (co16 % 2 == 0 ? 2 : 1);
@@ -1082,62 +1130,84 @@ static void wgrad_tiles(int dtype, int c1, int c2, int cout, int* cof, int* cif)
   *cif = ok(3) ? 3 : (ok(2) ? 2 : 1);
 }
 
-// all-taps kernel: 48 x 48 channel blocks only, one persistent workgroup per CU in total (8 XCD ranges x g8)
 int g_wgrad_alltaps_mode = -1;  // brats_conv3d_set_wgrad_alltaps(): -1 = environment / default (on), 0 = off, 1 = on
-static bool wgrad_alltaps_ok(int dtype, int dil, int c1, int c2, int cout, int ntiles, int* g8_out, int* wide_out = nullptr) {
-  static int env_mode = -1, ncu = 0;
-  if (env_mode < 0) {
-    const char* e = getenv("BRATS_WGRAD_ALLTAPS");
-    env_mode = e ? atoi(e) : 1;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  const int mode = g_wgrad_alltaps_mode >= 0 ? g_wgrad_alltaps_mode : env_mode;
-  const int cin = c1 + (c2 > 0 ? c2 : 0);
-  const bool narrow = c2 <= 0 && c1 <= 16;  // the first layer: one 16-channel ci block
-  if (!mode || dtype != BRATS_BF16 || dil != 1) return false;
-  // block shape: 48 co x 48 ci, or 64 co x 32 ci for widths that are multiples of 64 but not of 48 (LDS-DMA form only)
-  bool wide = false;
-  if (cout % 48 || (!narrow && (c1 % 48 || (c2 > 0 && c2 % 48)))) {
-    if (cout % 64 || (!narrow && (c1 % 32 || (c2 > 0 && c2 % 32)))) return false;
-    wide = true;  // (narrow + wide: the first layer of a width-64 network, 64 co x 16 ci blocks)
-  }
-  const int blocks = wide ? (cout / 64) * (narrow ? 1 : cin / 32) : (cout / 48) * (narrow ? 1 : cin / 48);
-  const int nl = wgrad_nlane(ntiles);
-  int g8 = ceil_div(ncu, nl * blocks);
-  if (g8 < 1) g8 = 1;
-  if (ntiles < 4 * nl * g8) return false;  // too few tiles per workgroup to amortise 132 accumulators x 27 taps of slab
-  *g8_out = g8;
-  if (wide_out) *wide_out = wide ? 1 : 0;
-  return true;
-}
 extern "C" int BRATS_API(brats_conv3d_set_wgrad_alltaps)(int mode) {
   const int old = g_wgrad_alltaps_mode;
   g_wgrad_alltaps_mode = mode < 0 ? -1 : (mode ? 1 : 0);
   return old;
 }
-
-static size_t x3_align(size_t b);
-static size_t wgrad_x3_fused_ws_bytes(int N, int D, int H, int W, int c1, int c2, int cout);
-extern "C" size_t BRATS_API(brats_conv3d_wgrad_ws_bytes)(int dtype, int ksize, int N, int D, int H, int W, int c1, int c2, int cout) {
-  if (ksize != 3) return 0;
-  if (dtype == BRATS_X3_BF16) {
-    // split precision: three groups of 16-bit slabs + the hi / lo tensors of x1, x2 and dy (wgrad_x3)
-    const size_t vox = (size_t)N * D * H * W;
-    const size_t slab = BRATS_API(brats_conv3d_wgrad_ws_bytes)(BRATS_BF16, 3, N, D, H, W, c1, c2, cout) * 3;
-    auto sp = [&](int c) { return c > 0 ? 2 * x3_align(vox * c * 2) : (size_t)0; };
-    const size_t three = x3_align(slab) + sp(c1) + sp(c2) + sp(cout), fused = wgrad_x3_fused_ws_bytes(N, D, H, W, c1, c2, cout);
-    return three > fused ? three : fused;
+static int wgrad_alltaps_mode() {
+  static int env_mode = -1;
+  if (env_mode < 0) {
+    const char* e = getenv("BRATS_WGRAD_ALLTAPS");
+    env_mode = e ? atoi(e) : 1;
   }
-  int cof, cif;
-  wgrad_tiles(dtype, c1, c2, cout, &cof, &cif);
-  const int ntiles = N * ceil_div(D, WG_TZ) * ceil_div(H, WG_TY) * ceil_div(W, WG_TX);
-  const int cin_tiles = ceil_div(c1, 16 * cif) + (c2 > 0 ? ceil_div(c2, 16 * cif) : 0);
-  int ns = wgrad_nsplit(ntiles, ceil_div(cout, 16 * cof), cin_tiles);
-  int g8 = 0;
-  if (wgrad_alltaps_ok(dtype, 1, c1, c2, cout, ntiles, &g8) && wgrad_nlane(ntiles) * g8 > ns) ns = wgrad_nlane(ntiles) * g8;  // the dilation is not known here
-  return (size_t)ns * 27 * cout * (c1 + (c2 > 0 ? c2 : 0)) * sizeof(float);
+  return g_wgrad_alltaps_mode >= 0 ? g_wgrad_alltaps_mode : env_mode;
+}
+
+// every kernel form the host launches, and everything it decides for one problem.  wgrad_plan() and wgrad_f8_plan() are the
+// only places where a form is chosen: the workspace-size functions and the launchers both read the plan.
+enum WgradForm {
+  WG_TAP_PLANE, WG_SHIFTED_TAP,                             // conv_wgrad_kernel<T, DIL, cof, cif, KS = 3 | 1>, 16-bit and f32
+  WG_ALLTAPS2_33, WG_ALLTAPS2_42, WG_ALLTAPS2_31,           // conv_wgrad_alltaps2_kernel<cof, cif>, 16-bit
+  WG_ALLTAPS_1, WG_ALLTAPS_1_4,                             // conv_wgrad_alltaps_kernel<1>, <1, 4> (the first layer of a width-64 network: 64 co x 16 ci), 16-bit
+  WG_F8_33, WG_F8_42                                        // conv_wgrad_alltaps_f8_kernel<cof, cif>
+};
+struct WgradPlan {
+  WgradForm form;
+  int cof, cif;            // 16-channel fragments per co / ci block
+  int cot, cit;            // co / ci blocks = grid.y, grid.z
+  int nlane, g8, nsplit;   // nsplit = nlane * g8 slabs
+  int ntaps, groups;       // grid.x = groups * nsplit (tap-plane: 3 tap planes, shifted-tap: ntaps, all-taps: 1)
+  bool clear;              // slab entries of padded ci / co lanes are never written: clear the slabs first
+  WgradTileGrid tiles;
+  size_t per;              // floats of one slab [ntaps][cout][cin]
+  size_t slab_bytes() const { return nsplit * per * sizeof(float); }
+};
+
+// the plan of one 16-bit / f32 problem: 3x3x3 at dilation 1 | 2 (all-taps where it is built and pays, else tap planes), or
+// with `shifted` the shifted-tap form (1x1x1, and 3x3x3 at any dilation)
+static WgradPlan wgrad_plan(int dtype, bool shifted, int ksize, int dil, const WgradArgs& a) {
+  WgradPlan pl;
+  const int c1 = a.c1, c2 = a.c2, cin = a.cin(), cout = a.cout;
+  pl.tiles = wgrad_tile_grid(a);
+  pl.ntaps = ksize == 3 ? 27 : 1;
+  pl.per = (size_t)pl.ntaps * cout * cin;
+  // all-taps kernels: blocks of 48 co x 48 ci, or 64 co x 32 ci for widths that are multiples of 64 but not of 48 (LDS-DMA
+  // form only); the first layer (narrow: one source of <= 16 channels) is one 16-channel ci block
+  const bool narrow = c2 == 0 && c1 <= 16;
+  auto blocks_of = [&](int co, int ci) { return cout % co == 0 && (narrow || (c1 % ci == 0 && c2 % ci == 0)); };
+  if (!shifted && wgrad_alltaps_mode() && dtype == BRATS_BF16 && dil == 1 && (blocks_of(48, 48) || blocks_of(64, 32))) {
+    const bool wide = !blocks_of(48, 48);
+    pl.cof = wide ? 4 : 3; pl.cif = narrow ? 1 : (wide ? 2 : 3);
+    pl.cot = cout / (16 * pl.cof); pl.cit = narrow ? 1 : cin / (16 * pl.cif);
+    if (wgrad_blocks_g8(pl.tiles.ntiles, pl.cot * pl.cit, &pl.nlane, &pl.g8)) {
+      // WG_ALLTAPS2_31: the first layer on the LDS-DMA form -- two X buffers of 16-channel rows, the next tile's loads in flight
+      // behind the MFMA phase: this layer is all loads (dY: 24 KB per tile against 1.5 k cycles of MFMA per wave)
+      pl.form = wide ? (narrow ? WG_ALLTAPS_1_4 : WG_ALLTAPS2_42) : narrow ? (c1 % 8 == 0 ? WG_ALLTAPS2_31 : WG_ALLTAPS_1) : WG_ALLTAPS2_33;
+      pl.groups = 1;
+      pl.clear = false;  // (narrow: the slab columns of the padded ci lanes (c1 < 16) are never written and never read: cin = c1)
+      pl.nsplit = pl.nlane * pl.g8;
+      return pl;
+    }
+  }
+  pl.form = shifted ? WG_SHIFTED_TAP : WG_TAP_PLANE;
+  wgrad_tiles(dtype, c1, c2, cout, &pl.cof, &pl.cif);
+  pl.cot = ceil_div(cout, 16 * pl.cof);
+  pl.cit = ceil_div(c1, 16 * pl.cif) + (c2 > 0 ? ceil_div(c2, 16 * pl.cif) : 0);
+  pl.groups = shifted ? pl.ntaps : 3;
+  pl.nlane = wgrad_nlane(pl.tiles.ntiles);
+  pl.g8 = wgrad_split_g8(pl.tiles.ntiles, pl.nlane, pl.groups, pl.cot, pl.cit);
+  pl.nsplit = pl.nlane * pl.g8;
+  pl.clear = cin % 16 || cout % 16;
+  return pl;
+}
+// slab bytes a caller must provide for that problem.  The size functions are not told the dilation of a 3x3x3 problem: the
+// larger of the plans at dilation 1 and 2 (the shifted-tap plan does not depend on it)
+static size_t wgrad_slab_room(int dtype, bool shifted, int ksize, const WgradArgs& a) {
+  const size_t d1 = wgrad_plan(dtype, shifted, ksize, 1, a).slab_bytes();
+  const size_t d2 = shifted ? 0 : wgrad_plan(dtype, shifted, ksize, 2, a).slab_bytes();
+  return d1 > d2 ? d1 : d2;
 }
 
 template <typename T, int DIL, int COF, int CIF, int KS = 3>
@@ -1162,64 +1232,42 @@ static int wgrad_dispatch(const WgradParams& p, int cof, int cif, dim3 grid, hip
   BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad: unsupported tile %dx%d", cof, cif);
 }
 
-// launches the MFMA kernel of one weight-gradient problem (16-bit or f32 operands as `dtype` says) into the split-K slabs at
-// ws; *nsplit_out = number of slabs written ([split][27][cout][cin] f32 each)
-static int wgrad_mfma(const void* x1, int c1, int pitch1, const void* x2, int c2, int pitch2, const void* dy, int dypitch, float* ws,
-                      int dtype, int dil, int N, int D, int H, int W, int cout, hipStream_t st, int* nsplit_out) {
-  int cof, cif;
-  wgrad_tiles(dtype, c1, c2, cout, &cof, &cif);
-  WgradParams p;
-  p.x1 = x1; p.x2 = x2; p.c1 = c1; p.c2 = c2; p.p1 = pitch1; p.p2 = pitch2;
-  p.dy = dy; p.dyp = dypitch; p.ws = ws;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.cin = c1 + c2; p.cout = cout;
-  p.tz = ceil_div(D, WG_TZ); p.ty = ceil_div(H, WG_TY); p.tx = ceil_div(W, WG_TX);
-  p.ntiles = N * p.tz * p.ty * p.tx;
-  const int cot = ceil_div(cout, 16 * cof);
-  const int cit = ceil_div(c1, 16 * cif) + (c2 > 0 ? ceil_div(c2, 16 * cif) : 0);
-  p.nsplit = wgrad_nsplit(p.ntiles, cot, cit);
-  p.nlane = wgrad_nlane(p.ntiles);
-  // ci tiles of x2 start at tile index ceil(c1/CI_T): only exact when c1 % CI_T == 0 or c2 == 0
-  if (c2 > 0 && c1 % (16 * cif)) BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad: c1=%d must be a multiple of the ci tile %d", c1, 16 * cif);
-  int g8a = 0, wide = 0;
-  const bool alltaps = wgrad_alltaps_ok(dtype, dil, c1, c2, cout, p.ntiles, &g8a, &wide);
-  // tap-plane kernel: slab entries of padded ci / co lanes are never written: clear the slab
-  if (!alltaps && ((c1 + c2) % 16 || cout % 16)) {
-    hipError_t e = hipMemsetAsync(ws, 0, (size_t)p.nsplit * 27 * cout * p.cin * sizeof(float), st);
-    if (e != hipSuccess) BRATS_FAIL(BRATS_E_HIP, "wgrad: memset: %s", hipGetErrorString(e));
-  }
-  dim3 grid(3 * p.nsplit, cot, cit);  // x = lane + nlane*(3*gsub + tzg)
-  int rc;
-  if (alltaps) {
-    p.nsplit = p.nlane * g8a;
-    constexpr int lds_48 = Wg3b<3, 3>::LDS, lds_wide = Wg3b<4, 2>::LDS;
-    static std::atomic<uint64_t> attr_b{0}, attr_c{0}, attr_d{0}, attr_e{0};
-    BRATS_ENSURE_LDS_ATTR(conv_wgrad_alltaps_kernel<1>, Wg3<1>::LDS, attr_b);
-    BRATS_ENSURE_LDS_ATTR((conv_wgrad_alltaps_kernel<1, 4>), (Wg3<1, 4>::LDS), attr_e);
-    BRATS_ENSURE_LDS_ATTR((conv_wgrad_alltaps2_kernel<3, 3>), lds_48, attr_c);
-    BRATS_ENSURE_LDS_ATTR((conv_wgrad_alltaps2_kernel<4, 2>), lds_wide, attr_d);
-    if (wide && c2 <= 0 && c1 <= 16) {
-      hipLaunchKernelGGL((conv_wgrad_alltaps_kernel<1, 4>), dim3(p.nsplit, cout / 64, 1), dim3(512), (Wg3<1, 4>::LDS), st, p);
-    } else if (wide) {
-      hipLaunchKernelGGL((conv_wgrad_alltaps2_kernel<4, 2>), dim3(p.nsplit, cout / 64, p.cin / 32), dim3(512), lds_wide, st, p);
-    } else if (c2 <= 0 && c1 <= 16 && c1 % 8 == 0) {
-      // the first layer on the LDS-DMA form (round 6): two X buffers of 16-channel rows, the next tile's loads in flight behind
-      // the MFMA phase -- this layer is all loads (dY: 24 KB per tile against 1.5 k cycles of MFMA per wave)
-      static std::atomic<uint64_t> attr_f{0};
-      BRATS_ENSURE_LDS_ATTR((conv_wgrad_alltaps2_kernel<3, 1>), (Wg3b<3, 1>::LDS), attr_f);
-      hipLaunchKernelGGL((conv_wgrad_alltaps2_kernel<3, 1>), dim3(p.nsplit, cout / 48, 1), dim3(512), (Wg3b<3, 1>::LDS), st, p);
-    } else if (c2 <= 0 && c1 <= 16) {
-      // the slab columns of the padded ci lanes (c1 < 16) are never written and never read (cin = c1)
-      hipLaunchKernelGGL(conv_wgrad_alltaps_kernel<1>, dim3(p.nsplit, cout / 48, 1), dim3(512), Wg3<1>::LDS, st, p);
-    } else {
-      hipLaunchKernelGGL((conv_wgrad_alltaps2_kernel<3, 3>), dim3(p.nsplit, cout / 48, p.cin / 48), dim3(512), lds_48, st, p);
-    }
-    rc = 0;
-  } else if (dtype == BRATS_BF16) rc = dil == 1 ? wgrad_dispatch<bf16_t, 1>(p, cof, cif, grid, st) : wgrad_dispatch<bf16_t, 2>(p, cof, cif, grid, st);
-  else rc = dil == 1 ? wgrad_dispatch<float, 1>(p, cof, cif, grid, st) : wgrad_dispatch<float, 2>(p, cof, cif, grid, st);
-  if (rc) return rc;
+template <auto KERN, int LDS>
+static int wgrad_alltaps_launch(const WgradParams& p, dim3 grid, hipStream_t st) {
+  static std::atomic<uint64_t> attr_done{0};
+  BRATS_ENSURE_LDS_ATTR(KERN, LDS, attr_done);
+  hipLaunchKernelGGL(KERN, grid, dim3(512), LDS, st, p);
   BRATS_CHECK_LAUNCH();
-  *nsplit_out = p.nsplit;
   return 0;
+}
+
+// runs the MFMA kernel of one planned problem (16-bit or f32 operands as `dtype` says) into the pl.nsplit slabs at ws
+// ([split][ntaps][cout][cin] f32 each); `room` = the bytes the workspace-size function promises the caller for them
+static int wgrad_run(const WgradPlan& pl, int dtype, int dil, const WgradArgs& a, float* ws, size_t room, hipStream_t st) {
+  const char* who = pl.form == WG_SHIFTED_TAP ? "wgrad_shift" : "wgrad";
+  // ci tiles of x2 start at tile index ceil(c1/CI_T): only exact when c1 % CI_T == 0 or c2 == 0
+  if (a.c2 > 0 && a.c1 % (16 * pl.cif)) BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad: c1=%d must be a multiple of the ci tile %d", a.c1, 16 * pl.cif);
+  if (pl.slab_bytes() > room) BRATS_FAIL(BRATS_E_ARG, "%s: the plan's %zu bytes of slabs exceed the workspace size %zu", who, pl.slab_bytes(), room);
+  const WgradParams p = wgrad_params(a, ws, pl.tiles, pl.nlane, pl.nsplit, pl.ntaps, dil);
+  if (pl.clear) {
+    hipError_t e = hipMemsetAsync(ws, 0, pl.slab_bytes(), st);
+    if (e != hipSuccess) BRATS_FAIL(BRATS_E_HIP, "%s: memset: %s", who, hipGetErrorString(e));
+  }
+  const dim3 grid(pl.groups * pl.nsplit, pl.cot, pl.cit);  // tap-plane: x = lane + nlane*(3*gsub + tzg)
+  const bool bf = dtype == BRATS_BF16;
+  switch (pl.form) {
+    case WG_TAP_PLANE:
+      if (bf) return dil == 1 ? wgrad_dispatch<bf16_t, 1>(p, pl.cof, pl.cif, grid, st) : wgrad_dispatch<bf16_t, 2>(p, pl.cof, pl.cif, grid, st);
+      return dil == 1 ? wgrad_dispatch<float, 1>(p, pl.cof, pl.cif, grid, st) : wgrad_dispatch<float, 2>(p, pl.cof, pl.cif, grid, st);
+    case WG_SHIFTED_TAP:
+      return bf ? wgrad_dispatch<bf16_t, 1, 1>(p, pl.cof, pl.cif, grid, st) : wgrad_dispatch<float, 1, 1>(p, pl.cof, pl.cif, grid, st);
+    case WG_ALLTAPS2_33: return wgrad_alltaps_launch<conv_wgrad_alltaps2_kernel<3, 3>, Wg3b<3, 3>::LDS>(p, grid, st);
+    case WG_ALLTAPS2_42: return wgrad_alltaps_launch<conv_wgrad_alltaps2_kernel<4, 2>, Wg3b<4, 2>::LDS>(p, grid, st);
+    case WG_ALLTAPS2_31: return wgrad_alltaps_launch<conv_wgrad_alltaps2_kernel<3, 1>, Wg3b<3, 1>::LDS>(p, grid, st);
+    case WG_ALLTAPS_1: return wgrad_alltaps_launch<conv_wgrad_alltaps_kernel<1>, Wg3<1>::LDS>(p, grid, st);
+    case WG_ALLTAPS_1_4: return wgrad_alltaps_launch<conv_wgrad_alltaps_kernel<1, 4>, Wg3<1, 4>::LDS>(p, grid, st);
+    default: BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad: form %d is not a 16-bit / f32 kernel", (int)pl.form);
+  }
 }
 
 // ---- split precision (BRATS_X3_*): f32 X and dY, three 16-bit MFMA products -----------------------------------------
@@ -1270,7 +1318,6 @@ __global__ void __launch_bounds__(256) x3_split_kernel(const float* __restrict__
   }
 }
 static size_t x3_align(size_t b) { return (b + 255) / 256 * 256; }
-static size_t wgrad_x3_split_bytes(size_t voxels, int c) { return c > 0 ? x3_align(voxels * c * 2) : 0; }  // one of hi / lo
 static void x3_split_launch(const float* src, int pitch, bf16_t* hi, bf16_t* lo, size_t vox, int c, const float* amax, hipStream_t st) {
   const size_t total = vox * (c / 8);
   size_t nb = (total + 511) / 512;  // two pieces per thread
@@ -1278,37 +1325,44 @@ static void x3_split_launch(const float* src, int pitch, bf16_t* hi, bf16_t* lo,
   hipLaunchKernelGGL(x3_split_kernel<0>, dim3(blocks), dim3(256), 0, st, src, pitch, hi, lo, vox, c, amax);
 }
 
-static int wgrad_x3(const void* x1, int c1, int pitch1, const void* x2, int c2, int pitch2, const void* dy, int dypitch,
-                    const float* amax_dy, float* ws, float* dw, size_t slab_bytes, int dil, int N, int D, int H, int W, int cout,
-                    hipStream_t st) {
-  const size_t vox = (size_t)N * D * H * W;
-  char* b = (char*)ws + x3_align(slab_bytes);
-  bf16_t* h1 = (bf16_t*)b; b += wgrad_x3_split_bytes(vox, c1);
-  bf16_t* l1 = (bf16_t*)b; b += wgrad_x3_split_bytes(vox, c1);
-  bf16_t* h2 = (bf16_t*)b; b += wgrad_x3_split_bytes(vox, c2);
-  bf16_t* l2 = (bf16_t*)b; b += wgrad_x3_split_bytes(vox, c2);
-  bf16_t* hy = (bf16_t*)b; b += wgrad_x3_split_bytes(vox, cout);
-  bf16_t* ly = (bf16_t*)b;
-  auto split = [&](const void* src, int pitch, bf16_t* hi, bf16_t* lo, int c, const float* amax) {
-    x3_split_launch((const float*)src, pitch, hi, lo, vox, c, amax, st);
-  };
-  split(x1, pitch1, h1, l1, c1, nullptr);
-  if (c2 > 0) split(x2, pitch2, h2, l2, c2, nullptr);
-  split(dy, dypitch, hy, ly, cout, amax_dy);  // (dY * 2^k: undone by the reduction)
+// the split-precision workspace: [three groups of 16-bit slabs | hi1 | lo1 | hi2 | lo2 | hiY | loY], every region a multiple
+// of 256 bytes (x2: empty when c2 == 0).  The size functions return bytes(), the launcher takes its pointers from at().
+struct X3Carve {
+  size_t off[7];  // byte offsets of hi1, lo1, hi2, lo2, hiY, loY and of the end
+  X3Carve(size_t room16, const WgradArgs& a) {  // room16 = wgrad_slab_room() of the 16-bit problem
+    const int c[3] = {a.c1, a.c2, a.cout};
+    size_t b = x3_align(3 * room16);
+    for (int i = 0; i < 6; ++i) {
+      off[i] = b;
+      b += c[i / 2] > 0 ? x3_align(a.vox() * c[i / 2] * 2) : 0;
+    }
+    off[6] = b;
+  }
+  size_t bytes() const { return off[6]; }
+  bf16_t* at(float* ws, int i) const { return (bf16_t*)((char*)ws + off[i]); }
+};
+
+// the three-launch form: one streaming pass per operand writes its hi / lo tensors, the planned 16-bit problem runs three
+// times into three groups of slabs, one reduction (times 2^-k) sums all of them
+static int wgrad_x3(const WgradPlan& pl, int dil, const WgradArgs& a, const float* amax_dy, float* ws, float* dw, size_t room16,
+                          hipStream_t st) {
+  const X3Carve cv(room16, a);
+  bf16_t *h1 = cv.at(ws, 0), *l1 = cv.at(ws, 1), *h2 = cv.at(ws, 2), *l2 = cv.at(ws, 3), *hy = cv.at(ws, 4), *ly = cv.at(ws, 5);
+  x3_split_launch((const float*)a.x1, a.p1, h1, l1, a.vox(), a.c1, nullptr, st);
+  if (a.c2 > 0) x3_split_launch((const float*)a.x2, a.p2, h2, l2, a.vox(), a.c2, nullptr, st);
+  x3_split_launch((const float*)a.dy, a.dyp, hy, ly, a.vox(), a.cout, amax_dy, st);  // (dY * 2^k: undone by the reduction)
   BRATS_CHECK_LAUNCH();
-  int ns = 0, total = 0;
-  const size_t per = (size_t)27 * cout * (c1 + c2);
-  // (small terms first: the reduction adds the slabs in this order)
-  int rc = wgrad_mfma(l1, c1, c1, c2 > 0 ? l2 : nullptr, c2, c2, hy, cout, ws, BRATS_BF16, dil, N, D, H, W, cout, st, &ns);
-  if (rc) return rc;
-  total += ns;
-  rc = wgrad_mfma(h1, c1, c1, c2 > 0 ? h2 : nullptr, c2, c2, ly, cout, ws + (size_t)total * per, BRATS_BF16, dil, N, D, H, W, cout, st, &ns);
-  if (rc) return rc;
-  total += ns;
-  rc = wgrad_mfma(h1, c1, c1, c2 > 0 ? h2 : nullptr, c2, c2, hy, cout, ws + (size_t)total * per, BRATS_BF16, dil, N, D, H, W, cout, st, &ns);
-  if (rc) return rc;
-  total += ns;
-  wgrad_reduce_launch((const float*)ws, dw, total, cout, c1 + c2, 27, st, amax_dy);
+  WgradArgs t = a;  // the dense 16-bit tensors
+  t.p1 = a.c1; t.p2 = a.c2; t.dyp = a.cout;
+  const bool xlo[3] = {true, false, false}, ylo[3] = {false, true, false};  // Xlo (x) dYhi, Xhi (x) dYlo, Xhi (x) dYhi
+  for (int k = 0; k < 3; ++k) {  // (small terms first: the reduction adds the slabs in this order)
+    t.x1 = xlo[k] ? l1 : h1;
+    t.x2 = a.c2 > 0 ? (xlo[k] ? l2 : h2) : nullptr;
+    t.dy = ylo[k] ? ly : hy;
+    const int rc = wgrad_run(pl, BRATS_BF16, dil, t, ws + (size_t)k * pl.nsplit * pl.per, room16, st);
+    if (rc) return rc;
+  }
+  wgrad_reduce_launch((const float*)ws, dw, 3 * pl.nsplit, a.cout, a.cin(), pl.ntaps, st, amax_dy);
   return 0;
 }
 
@@ -1319,42 +1373,49 @@ extern "C" int BRATS_API(brats_conv3d_set_x3_wgrad_fused)(int mode) {  // (here,
   return old;
 }
 
-static int wgrad_impl(const void* x1, int c1, int pitch1, const void* x2, int c2, int pitch2, const void* dy, int dypitch,
-                      const float* amax_dy, float* ws, float* dw, float* dbias, int dtype, int ksize, int dil, int N, int D, int H,
-                      int W, int cout, brats_stream_t s) {
-  if (!x1 || !dy || !ws || !dw || c1 <= 0 || cout <= 0) BRATS_FAIL(BRATS_E_ARG, "wgrad: null pointer / bad size");
-  if (ksize != 3 || (dil != 1 && dil != 2)) BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad: ksize=%d dil=%d unsupported", ksize, dil);
-  if (c2 < 0) c2 = 0;
-  if (c2 > 0 && !x2) BRATS_FAIL(BRATS_E_ARG, "wgrad: c2 > 0 but x2 NULL");
+// ---- entry points: 3x3x3 at dilation 1 | 2 (tap planes / all taps), and the shifted-tap form: 1x1x1 convolutions and 3x3x3
+// convolutions at any dilation (ASPP d = 4, 6) ------------------------------------------------------------------------
+static size_t wgrad_ws_bytes(int dtype, bool shifted, int ksize, const WgradArgs& a) {
+  if (dtype != BRATS_X3_BF16) return wgrad_slab_room(dtype, shifted, ksize, a);
+  const size_t three = X3Carve(wgrad_slab_room(BRATS_BF16, shifted, ksize, a), a).bytes();
+  const size_t fused = shifted ? 0 : wgrad_x3_fused_ws_bytes(a);
+  return three > fused ? three : fused;
+}
+extern "C" size_t BRATS_API(brats_conv3d_wgrad_ws_bytes)(int dtype, int ksize, int N, int D, int H, int W, int c1, int c2, int cout) {
+  return ksize == 3 ? wgrad_ws_bytes(dtype, false, 3, wgrad_shape(N, D, H, W, c1, c2, cout)) : 0;
+}
+extern "C" size_t BRATS_API(brats_conv3d_wgrad_shift_ws_bytes)(int dtype, int ksize, int N, int D, int H, int W, int cin, int cout) {
+  return ksize == 1 || ksize == 3 ? wgrad_ws_bytes(dtype, true, ksize, wgrad_shape(N, D, H, W, cin, 0, cout)) : 0;
+}
+
+static int wgrad_impl(bool shifted, WgradArgs a, const float* amax_dy, float* ws, float* dw, float* dbias, int dtype, int ksize, int dil,
+                      brats_stream_t s) {
+  const char* who = shifted ? "wgrad_shift" : "wgrad";
+  if (!a.x1 || !a.dy || !ws || !dw || a.c1 <= 0 || a.cout <= 0 || (shifted && (a.N <= 0 || a.D <= 0 || a.H <= 0 || a.W <= 0)))
+    BRATS_FAIL(BRATS_E_ARG, "%s: null pointer / bad size", who);
+  if (shifted ? (ksize != 1 && ksize != 3) || dil < 1 : ksize != 3 || (dil != 1 && dil != 2))
+    BRATS_FAIL(BRATS_E_UNSUPPORTED, "%s: ksize=%d dil=%d unsupported", who, ksize, dil);
+  if (shifted && dtype != BRATS_BF16 && dtype != BRATS_F32 && dtype != BRATS_X3_BF16) BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad_shift: dtype %d", dtype);
+  if (a.c2 < 0) a.c2 = 0;
+  if (a.c2 > 0 && !a.x2) BRATS_FAIL(BRATS_E_ARG, "wgrad: c2 > 0 but x2 NULL");
   const bool x3 = dtype == BRATS_X3_BF16;
-  const int epl = dtype == BRATS_BF16 ? 8 : 4;
-  if (pitch1 % epl || (c2 && pitch2 % epl) || dypitch % epl || c1 % epl || c2 % epl || cout % epl)
-    BRATS_FAIL(BRATS_E_ARG, "wgrad: channel counts / pitches must be multiples of %d", epl);
-  if (x3 && (c1 % 8 || c2 % 8 || cout % 8)) BRATS_FAIL(BRATS_E_ARG, "wgrad (split precision): channel counts must be multiples of 8");
-  {  // staged pieces are addressed by 32-bit byte offsets inside one sample (buffer_load voffset)
-    const int mp = pitch1 > pitch2 ? (pitch1 > dypitch ? pitch1 : dypitch) : (pitch2 > dypitch ? pitch2 : dypitch);
-    if ((double)D * H * W * mp * (dtype == BRATS_BF16 ? 2 : 4) >= 2147483648.0)
-      BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad: one sample of %dx%dx%d x pitch %d exceeds the 2 GiB buffer-offset range", D, H, W, mp);
-  }
+  const int epl = vec_width(dtype);
+  if (a.p1 % epl || (a.c2 && a.p2 % epl) || a.dyp % epl || a.c1 % epl || a.c2 % epl || a.cout % epl)
+    BRATS_FAIL(BRATS_E_ARG, "%s: channel counts / pitches must be multiples of %d", who, epl);
+  if (x3 && (a.c1 % 8 || a.c2 % 8 || a.cout % 8)) BRATS_FAIL(BRATS_E_ARG, "%s (split precision): channel counts must be multiples of 8", who);
+  if (const int mp = wgrad_sample_overflow(a, dtype == BRATS_BF16 ? 2 : 4))
+    BRATS_FAIL(BRATS_E_UNSUPPORTED, "%s: one sample of %dx%dx%d x pitch %d exceeds the 2 GiB buffer-offset range", who, a.D, a.H, a.W, mp);
   hipStream_t st = (hipStream_t)s;
-  if (x3) {
-    int rc = wgrad_x3_fused(x1, c1, pitch1, x2, c2, pitch2, dy, dypitch, amax_dy, ws, dw, dil, N, D, H, W, cout, st);
-    if (rc == 1) {  // not a layer of the fused kernel: the split pass + three 16-bit launches
-      const size_t slab = BRATS_API(brats_conv3d_wgrad_ws_bytes)(BRATS_BF16, 3, N, D, H, W, c1, c2, cout) * 3;
-      rc = wgrad_x3(x1, c1, pitch1, x2, c2, pitch2, dy, dypitch, amax_dy, ws, dw, slab, dil, N, D, H, W, cout, st);
-    }
-    if (rc) return rc;
-  } else {
-    int nsplit = 0;
-    const int rc = wgrad_mfma(x1, c1, pitch1, x2, c2, pitch2, dy, dypitch, ws, dtype, dil, N, D, H, W, cout, st, &nsplit);
-    if (rc) return rc;
-    wgrad_reduce_launch((const float*)ws, dw, nsplit, cout, c1 + c2, 27, st);
+  int rc = x3 && !shifted ? wgrad_x3_fused(a, amax_dy, ws, dw, dil, st) : 1;
+  if (rc == 1) {  // (split precision: not a layer of the fused kernel)
+    const int dt = x3 ? BRATS_BF16 : dtype;  // the operand type of the kernels
+    const WgradPlan pl = wgrad_plan(dt, shifted, ksize, dil, a);
+    const size_t room = wgrad_slab_room(dt, shifted, ksize, a);
+    if (x3) rc = wgrad_x3(pl, dil, a, amax_dy, ws, dw, room, st);
+    else if (!(rc = wgrad_run(pl, dtype, dil, a, ws, room, st))) wgrad_reduce_launch((const float*)ws, dw, pl.nsplit, a.cout, a.cin(), pl.ntaps, st);
   }
-  if (dbias) {
-    const size_t vox = (size_t)N * D * H * W;
-    if (dtype == BRATS_BF16) hipLaunchKernelGGL(dbias_kernel<bf16_t>, dim3(cout), dim3(256), 0, st, (const bf16_t*)dy, dypitch, dbias, vox, cout);
-    else hipLaunchKernelGGL(dbias_kernel<float>, dim3(cout), dim3(256), 0, st, (const float*)dy, dypitch, dbias, vox, cout);
-  }
+  if (rc) return rc;
+  if (dbias) wgrad_dbias_launch(dtype, a.dy, a.dyp, dbias, a.vox(), a.cout, st);
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -1362,170 +1423,55 @@ static int wgrad_impl(const void* x1, int c1, int pitch1, const void* x2, int c2
 extern "C" int BRATS_API(brats_conv3d_wgrad)(const void* x1, int c1, int pitch1, const void* x2, int c2, int pitch2, const void* dy,
                                   int dypitch, float* ws, float* dw, float* dbias, int dtype, int ksize, int dil, int N,
                                   int D, int H, int W, int cout, brats_stream_t s) {
-  return wgrad_impl(x1, c1, pitch1, x2, c2, pitch2, dy, dypitch, nullptr, ws, dw, dbias, dtype, ksize, dil, N, D, H, W, cout, s);
+  return wgrad_impl(false, WgradArgs{x1, c1, pitch1, x2, c2, pitch2, dy, dypitch, N, D, H, W, cout}, nullptr, ws, dw, dbias, dtype, ksize, dil, s);
 }
 extern "C" int BRATS_API(brats_conv3d_x3_wgrad)(const void* x1, int c1, int pitch1, const void* x2, int c2, int pitch2, const void* dy,
                                      int dypitch, const float* amax_dy, float* ws, float* dw, float* dbias, int dtype, int dil,
                                      int N, int D, int H, int W, int cout, brats_stream_t s) {
   if (dtype != BRATS_X3_BF16) BRATS_FAIL(BRATS_E_ARG, "conv3d_x3_wgrad: dtype must be BRATS_X3_F16 or BRATS_X3_BF16");
-  return wgrad_impl(x1, c1, pitch1, x2, c2, pitch2, dy, dypitch, amax_dy, ws, dw, dbias, dtype, 3, dil, N, D, H, W, cout, s);
+  return wgrad_impl(false, WgradArgs{x1, c1, pitch1, x2, c2, pitch2, dy, dypitch, N, D, H, W, cout}, amax_dy, ws, dw, dbias, dtype, 3, dil, s);
 }
-
-// ---- shifted-tap form: 1x1x1 convolutions, and 3x3x3 convolutions at any dilation (ASPP d = 4, 6) ------------------
-static int wgrad_shift_geometry(int dtype, int ksize, int N, int D, int H, int W, int cin, int cout, WgradParams* p, int* cof,
-                                int* cif, int* cot, int* cit) {
-  wgrad_tiles(dtype, cin, 0, cout, cof, cif);
-  p->N = N; p->D = D; p->H = H; p->W = W; p->cin = cin; p->cout = cout;
-  p->tz = ceil_div(D, WG_TZ); p->ty = ceil_div(H, WG_TY); p->tx = ceil_div(W, WG_TX);
-  p->ntiles = N * p->tz * p->ty * p->tx;
-  p->ntaps = ksize == 3 ? 27 : 1;
-  *cot = ceil_div(cout, 16 * *cof);
-  *cit = ceil_div(cin, 16 * *cif);
-  p->nlane = wgrad_nlane(p->ntiles);
-  int g8 = ceil_div(512, p->ntaps * p->nlane * *cot * *cit);
-  const int cap = ceil_div(p->ntiles, p->nlane);
-  if (g8 > cap) g8 = cap;
-  if (g8 < 1) g8 = 1;
-  p->nsplit = p->nlane * g8;
-  return 0;
-}
-
-extern "C" size_t BRATS_API(brats_conv3d_wgrad_shift_ws_bytes)(int dtype, int ksize, int N, int D, int H, int W, int cin, int cout) {
-  if (ksize != 1 && ksize != 3) return 0;
-  if (dtype == BRATS_X3_BF16) {  // split precision: three groups of 16-bit slabs + the hi / lo tensors of x and dy (wgrad_shift_x3)
-    const size_t vox = (size_t)N * D * H * W;
-    const size_t slab = BRATS_API(brats_conv3d_wgrad_shift_ws_bytes)(BRATS_BF16, ksize, N, D, H, W, cin, cout) * 3;
-    return x3_align(slab) + 2 * wgrad_x3_split_bytes(vox, cin) + 2 * wgrad_x3_split_bytes(vox, cout);
-  }
-  WgradParams p;
-  int cof, cif, cot, cit;
-  wgrad_shift_geometry(dtype, ksize, N, D, H, W, cin, cout, &p, &cof, &cif, &cot, &cit);
-  return (size_t)p.nsplit * p.ntaps * cout * cin * sizeof(float);
-}
-
-// launches the shifted-tap MFMA kernel of one problem into the slabs at ws; *nsplit_out = slabs written ([split][taps][cout][cin])
-static int wgrad_shift_mfma(const void* x, int cin, int xpitch, const void* dy, int dypitch, float* ws, int dtype, int ksize, int dil,
-                            int N, int D, int H, int W, int cout, hipStream_t st, int* nsplit_out, int* ntaps_out) {
-  WgradParams p;
-  int cof, cif, cot, cit;
-  wgrad_shift_geometry(dtype, ksize, N, D, H, W, cin, cout, &p, &cof, &cif, &cot, &cit);
-  p.x1 = x; p.x2 = nullptr; p.c1 = cin; p.c2 = 0; p.p1 = xpitch; p.p2 = 0;
-  p.dy = dy; p.dyp = dypitch; p.ws = ws; p.dil = dil;
-  if (cin % 16 || cout % 16) {  // slab entries of padded ci / co lanes are never written
-    hipError_t e = hipMemsetAsync(ws, 0, (size_t)p.nsplit * p.ntaps * cout * cin * sizeof(float), st);
-    if (e != hipSuccess) BRATS_FAIL(BRATS_E_HIP, "wgrad_shift: memset: %s", hipGetErrorString(e));
-  }
-  dim3 grid(p.ntaps * p.nsplit, cot, cit);
-  const int rc = dtype == BRATS_BF16 ? wgrad_dispatch<bf16_t, 1, 1>(p, cof, cif, grid, st) : wgrad_dispatch<float, 1, 1>(p, cof, cif, grid, st);
-  if (rc) return rc;
-  *nsplit_out = p.nsplit;
-  *ntaps_out = p.ntaps;
-  return 0;
-}
-
-static int wgrad_shift_impl(const void* x, int cin, int xpitch, const void* dy, int dypitch, const float* amax_dy, float* ws, float* dw,
-                            float* dbias, int dtype, int ksize, int dil, int N, int D, int H, int W, int cout, brats_stream_t s) {
-  if (!x || !dy || !ws || !dw || cin <= 0 || cout <= 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0)
-    BRATS_FAIL(BRATS_E_ARG, "wgrad_shift: null pointer / bad size");
-  if ((ksize != 1 && ksize != 3) || dil < 1) BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad_shift: ksize=%d dil=%d unsupported", ksize, dil);
-  if (dtype != BRATS_BF16 && dtype != BRATS_F32 && dtype != BRATS_X3_BF16) BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad_shift: dtype %d", dtype);
-  const bool x3 = dtype == BRATS_X3_BF16;
-  const int epl = dtype == BRATS_BF16 ? 8 : 4;
-  if (xpitch % epl || dypitch % epl || cin % epl || cout % epl)
-    BRATS_FAIL(BRATS_E_ARG, "wgrad_shift: channel counts / pitches must be multiples of %d", epl);
-  if (x3 && (cin % 8 || cout % 8)) BRATS_FAIL(BRATS_E_ARG, "wgrad_shift (split precision): channel counts must be multiples of 8");
-  {
-    const int mp = xpitch > dypitch ? xpitch : dypitch;
-    if ((double)D * H * W * mp * (dtype == BRATS_BF16 ? 2 : 4) >= 2147483648.0)
-      BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad_shift: one sample of %dx%dx%d x pitch %d exceeds the 2 GiB buffer-offset range", D, H, W, mp);
-  }
-  hipStream_t st = (hipStream_t)s;
-  int ns = 0, ntaps = 0;
-  if (x3) {
-    // split precision (see wgrad_x3): hi / lo tensors of x and of dy * 2^k, three runs of the 16-bit kernel, one reduction
-    const size_t vox = (size_t)N * D * H * W;
-    const size_t slab = BRATS_API(brats_conv3d_wgrad_shift_ws_bytes)(BRATS_BF16, ksize, N, D, H, W, cin, cout) * 3;
-    char* b = (char*)ws + x3_align(slab);
-    bf16_t* hx = (bf16_t*)b; b += wgrad_x3_split_bytes(vox, cin);
-    bf16_t* lx = (bf16_t*)b; b += wgrad_x3_split_bytes(vox, cin);
-    bf16_t* hy = (bf16_t*)b; b += wgrad_x3_split_bytes(vox, cout);
-    bf16_t* ly = (bf16_t*)b;
-    x3_split_launch((const float*)x, xpitch, hx, lx, vox, cin, nullptr, st);
-    x3_split_launch((const float*)dy, dypitch, hy, ly, vox, cout, amax_dy, st);
-    BRATS_CHECK_LAUNCH();
-    int total = 0;
-    const size_t per = (size_t)(ksize == 3 ? 27 : 1) * cout * cin;
-    const bf16_t* xs[3] = {lx, hx, hx};
-    const bf16_t* ys[3] = {hy, ly, hy};
-    for (int t = 0; t < 3; ++t) {  // (small terms first: the reduction adds the slabs in this order)
-      const int rc = wgrad_shift_mfma(xs[t], cin, cin, ys[t], cout, ws + (size_t)total * per, BRATS_BF16, ksize, dil, N, D, H, W, cout, st, &ns, &ntaps);
-      if (rc) return rc;
-      total += ns;
-    }
-    wgrad_reduce_launch((const float*)ws, dw, total, cout, cin, ntaps, st, amax_dy);
-  } else {
-    const int rc = wgrad_shift_mfma(x, cin, xpitch, dy, dypitch, ws, dtype, ksize, dil, N, D, H, W, cout, st, &ns, &ntaps);
-    if (rc) return rc;
-    wgrad_reduce_launch((const float*)ws, dw, ns, cout, cin, ntaps, st);
-  }
-  if (dbias) {
-    const size_t vox = (size_t)N * D * H * W;
-    if (dtype == BRATS_BF16) hipLaunchKernelGGL(dbias_kernel<bf16_t>, dim3(cout), dim3(256), 0, st, (const bf16_t*)dy, dypitch, dbias, vox, cout);
-    else hipLaunchKernelGGL(dbias_kernel<float>, dim3(cout), dim3(256), 0, st, (const float*)dy, dypitch, dbias, vox, cout);
-  }
-  BRATS_CHECK_LAUNCH();
-  return 0;
-}
-
 extern "C" int BRATS_API(brats_conv3d_wgrad_shift)(const void* x, int cin, int xpitch, const void* dy, int dypitch, float* ws, float* dw,
                                         float* dbias, int dtype, int ksize, int dil, int N, int D, int H, int W, int cout,
                                         brats_stream_t s) {
-  return wgrad_shift_impl(x, cin, xpitch, dy, dypitch, nullptr, ws, dw, dbias, dtype, ksize, dil, N, D, H, W, cout, s);
+  return wgrad_impl(true, WgradArgs{x, cin, xpitch, nullptr, 0, 0, dy, dypitch, N, D, H, W, cout}, nullptr, ws, dw, dbias, dtype, ksize, dil, s);
 }
 extern "C" int BRATS_API(brats_conv3d_x3_wgrad_shift)(const void* x, int cin, int xpitch, const void* dy, int dypitch, const float* amax_dy,
                                            float* ws, float* dw, float* dbias, int dtype, int ksize, int dil, int N, int D, int H,
                                            int W, int cout, brats_stream_t s) {
   if (dtype != BRATS_X3_BF16) BRATS_FAIL(BRATS_E_ARG, "conv3d_x3_wgrad_shift: dtype must be BRATS_X3_F16 or BRATS_X3_BF16");
-  return wgrad_shift_impl(x, cin, xpitch, dy, dypitch, amax_dy, ws, dw, dbias, dtype, ksize, dil, N, D, H, W, cout, s);
+  return wgrad_impl(true, WgradArgs{x, cin, xpitch, nullptr, 0, 0, dy, dypitch, N, D, H, W, cout}, amax_dy, ws, dw, dbias, dtype, ksize, dil, s);
 }
 
 // ---- e4m3 weight gradient (all-taps blocks only; everything else stays on the bf16 kernels) --------------------------
-// block shape (co fragments, ci fragments) and workgroups per XCD range; false = not built for this layer
-static bool wgrad_f8_shape(int N, int D, int H, int W, int c1, int c2, int cout, int* cof, int* cif, int* g8_out, int* nl_out, int* ntiles_out) {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  if (c2 < 0) c2 = 0;
+// 48 co x 48 ci or 64 co x 32 ci blocks under the all-taps blocks rule; false = not built for this layer
+static bool wgrad_f8_plan(const WgradArgs& a, WgradPlan* pl) {
+  const int c1 = a.c1, c2 = a.c2, cout = a.cout;
   if (c1 <= 0 || cout <= 0) return false;
-  if (cout % 48 == 0 && c1 % 48 == 0 && c2 % 48 == 0) { *cof = 3; *cif = 3; }
-  else if (cout % 64 == 0 && c1 % 32 == 0 && c2 % 32 == 0) { *cof = 4; *cif = 2; }
+  if (cout % 48 == 0 && c1 % 48 == 0 && c2 % 48 == 0) { pl->form = WG_F8_33; pl->cof = 3; pl->cif = 3; }
+  else if (cout % 64 == 0 && c1 % 32 == 0 && c2 % 32 == 0) { pl->form = WG_F8_42; pl->cof = 4; pl->cif = 2; }
   else return false;
-  const int ntiles = N * ceil_div(D, WG_TZ) * ceil_div(H, WG_TY) * ceil_div(W, WG_TX);
-  const int blocks = (cout / (16 * *cof)) * ((c1 + c2) / (16 * *cif));
-  const int nl = wgrad_nlane(ntiles);
-  int g8 = ceil_div(ncu, nl * blocks);
-  if (g8 < 1) g8 = 1;
-  if (ntiles < 4 * nl * g8) return false;  // too few tiles per workgroup to amortise the 27-tap slab
-  *g8_out = g8; *nl_out = nl; *ntiles_out = ntiles;
+  pl->tiles = wgrad_tile_grid(a);
+  pl->cot = cout / (16 * pl->cof); pl->cit = a.cin() / (16 * pl->cif);
+  if (!wgrad_blocks_g8(pl->tiles.ntiles, pl->cot * pl->cit, &pl->nlane, &pl->g8)) return false;
+  pl->nsplit = pl->nlane * pl->g8;
+  pl->ntaps = 27; pl->groups = 1; pl->clear = false;
+  pl->per = (size_t)27 * cout * a.cin();
   return true;
 }
 
 extern "C" size_t BRATS_API(brats_conv3d_wgrad_f8_ws_bytes)(int N, int D, int H, int W, int c1, int c2, int cout) {
-  int cof, cif, g8, nl, nt;
-  if (!wgrad_f8_shape(N, D, H, W, c1, c2, cout, &cof, &cif, &g8, &nl, &nt)) return 0;  // 0 = not supported: use brats_conv3d_wgrad
-  return (size_t)nl * g8 * 27 * cout * (c1 + (c2 > 0 ? c2 : 0)) * sizeof(float);
+  WgradPlan pl;
+  return wgrad_f8_plan(wgrad_shape(N, D, H, W, c1, c2, cout), &pl) ? pl.slab_bytes() : 0;  // 0 = not supported: use brats_conv3d_wgrad
 }
 
 template <int COF, int CIF>
-static int wgrad_f8_launch(const WgradF8Params& pp, hipStream_t st) {
+static int wgrad_f8_launch(const WgradF8Params& pp, dim3 grid, hipStream_t st) {
   using G = Wg3f<COF, CIF>;
   auto kern = conv_wgrad_alltaps_f8_kernel<COF, CIF>;
   static std::atomic<uint64_t> attr_done{0};
   BRATS_ENSURE_LDS_ATTR(kern, G::LDS, attr_done);
-  hipLaunchKernelGGL(kern, dim3(pp.w.nsplit, pp.w.cout / G::CO, pp.w.cin / G::CI), dim3(512), G::LDS, st, pp);
+  hipLaunchKernelGGL(kern, grid, dim3(512), G::LDS, st, pp);
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -1536,30 +1482,19 @@ extern "C" int BRATS_API(brats_conv3d_wgrad_f8)(const void* x1, int c1, int pitc
   if (!x1 || !dy || !ws || !dw || !amax1 || !amax_dy || c1 <= 0 || cout <= 0) BRATS_FAIL(BRATS_E_ARG, "wgrad_f8: null pointer / bad size");
   if (c2 < 0) c2 = 0;
   if (c2 > 0 && (!x2 || !amax2)) BRATS_FAIL(BRATS_E_ARG, "wgrad_f8: c2 > 0 needs x2 and its |max|");
-  int cof, cif, g8, nl, nt;
-  if (!wgrad_f8_shape(N, D, H, W, c1, c2, cout, &cof, &cif, &g8, &nl, &nt))
+  const WgradArgs a{x1, c1, pitch1, x2, c2, pitch2, dy, dypitch, N, D, H, W, cout};
+  WgradPlan pl;
+  if (!wgrad_f8_plan(a, &pl))
     BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad_f8: built for 48 x 48 / 64 x 32 channel blocks of layers with enough tiles "
                "(brats_conv3d_wgrad_f8_ws_bytes() == 0 otherwise): use brats_conv3d_wgrad");
   if (pitch1 % 8 || (c2 && pitch2 % 8) || dypitch % 8) BRATS_FAIL(BRATS_E_ARG, "wgrad_f8: pitches must be multiples of 8");
-  {
-    const int mp = pitch1 > pitch2 ? (pitch1 > dypitch ? pitch1 : dypitch) : (pitch2 > dypitch ? pitch2 : dypitch);
-    if ((double)D * H * W * mp * 2 >= 2147483648.0) BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad_f8: sample exceeds the 2 GiB buffer-offset range");
-  }
-  WgradF8Params pp;
-  WgradParams& p = pp.w;
-  p.x1 = x1; p.x2 = x2; p.c1 = c1; p.c2 = c2; p.p1 = pitch1; p.p2 = pitch2;
-  p.dy = dy; p.dyp = dypitch; p.ws = ws;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.cin = c1 + c2; p.cout = cout;
-  p.tz = ceil_div(D, WG_TZ); p.ty = ceil_div(H, WG_TY); p.tx = ceil_div(W, WG_TX);
-  p.ntiles = nt;
-  p.nlane = nl;
-  p.ntaps = 27; p.dil = 1;
-  p.nsplit = nl * g8;
-  pp.amax_x1 = amax1; pp.amax_x2 = c2 ? amax2 : nullptr; pp.amax_dy = amax_dy;
+  if (wgrad_sample_overflow(a, 2)) BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad_f8: sample exceeds the 2 GiB buffer-offset range");
+  const WgradF8Params pp{wgrad_params(a, ws, pl.tiles, pl.nlane, pl.nsplit, 27, 1), amax1, c2 ? amax2 : nullptr, amax_dy};
   hipStream_t st = (hipStream_t)s;
-  const int rc = cof == 3 ? wgrad_f8_launch<3, 3>(pp, st) : wgrad_f8_launch<4, 2>(pp, st);
+  const dim3 grid(pl.nsplit, pl.cot, pl.cit);
+  const int rc = pl.form == WG_F8_33 ? wgrad_f8_launch<3, 3>(pp, grid, st) : wgrad_f8_launch<4, 2>(pp, grid, st);
   if (rc) return rc;
-  wgrad_reduce_launch((const float*)ws, dw, p.nsplit, cout, p.cin, 27, st);
+  wgrad_reduce_launch((const float*)ws, dw, pl.nsplit, cout, a.cin(), 27, st);
   BRATS_CHECK_LAUNCH();
   return 0;
 }

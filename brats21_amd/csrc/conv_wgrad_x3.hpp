@@ -401,25 +401,26 @@ __global__ __launch_bounds__(512, CIF == 1 ? 4 : 2) void conv_wgrad_x3_zwalk_ker
 // Is the fused kernel built for this layer?  dilation 1, Cout a multiple of 48, input channels in 48-blocks per source (or the
 // first layer: one source of <= 16 channels), enough half tiles per workgroup to amortise its 27-tap slab.
 int g_x3_wgrad_fused_mode = -1;  // brats_conv3d_set_x3_wgrad_fused(): -1 = environment / default (1), 0 = off, 1 = on, 2 = any tile count
-struct X3Shape { int nl, g8, nseg, nsegz, seglen, narrow; };
-static bool wgrad_x3_fused_shape(int dil, int N, int D, int H, int W, int c1, int c2, int cout, X3Shape* o) {
-  static int env_mode = -1, ncu = 0;
+struct X3Shape {
+  int nl, g8, nseg, nsegz, seglen, narrow;
+  WgradTileGrid tiles;  // half tiles (Wg3z); ntiles = nseg: the kernel walks segments
+};
+static bool wgrad_x3_fused_shape(int dil, const WgradArgs& a, X3Shape* o) {
+  static int env_mode = -1;
   if (env_mode < 0) {
     const char* e = getenv("BRATS_X3_WGRAD_FUSED");  // 0: round 4's split pass + three 16-bit launches, for same-box A/B runs
     env_mode = e ? atoi(e) : 1;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
   }
   const int mode = g_x3_wgrad_fused_mode >= 0 ? g_x3_wgrad_fused_mode : env_mode;
+  const int c1 = a.c1, c2 = a.c2, cout = a.cout;
   if (!mode || dil != 1 || cout % 48) return false;
-  if (c2 < 0) c2 = 0;
   const bool narrow = c2 == 0 && c1 <= 16;
   if (!narrow && (c1 % 48 || c2 % 48)) return false;
   using G = Wg3z<3>;
-  const int tz = ceil_div(D, G::TZ), cols = N * ceil_div(H, G::TY) * ceil_div(W, G::TX);
+  o->tiles = wgrad_tile_grid(a, G::TZ, G::TY, G::TX);
+  const int tz = o->tiles.tz, cols = a.N * o->tiles.ty * o->tiles.tx;
   const int blocks = (cout / 48) * (narrow ? 1 : (c1 + c2) / 48);
-  const int want = ceil_div((narrow ? 2 : 1) * ncu, blocks);  // workgroups along x (first layer: two per CU)
+  const int want = ceil_div((narrow ? 2 : 1) * device_cus(), blocks);  // workgroups along x (first layer: two per CU)
   // columns are cut into nsegz segments when there are fewer columns than workgroups; a segment re-loads two planes, so it
   // stays >= 4 tiles long
   int nsegz = 1;
@@ -433,37 +434,30 @@ static bool wgrad_x3_fused_shape(int dil, int N, int D, int H, int W, int c1, in
   int g8 = ceil_div(want, nl);
   while (g8 > 1 && nl * g8 > nseg) --g8;
   o->nl = nl; o->g8 = g8; o->nseg = nseg; o->nsegz = nsegz; o->seglen = seglen; o->narrow = narrow ? 1 : 0;
+  o->tiles.ntiles = nseg;
   return true;
 }
 
-static size_t wgrad_x3_fused_ws_bytes(int N, int D, int H, int W, int c1, int c2, int cout) {
+static size_t wgrad_x3_fused_ws_bytes(const WgradArgs& a) {
   X3Shape sh;
-  if (!wgrad_x3_fused_shape(1, N, D, H, W, c1, c2, cout, &sh)) return 0;
-  return (size_t)sh.nl * sh.g8 * 27 * cout * (c1 + (c2 > 0 ? c2 : 0)) * sizeof(float);
+  if (!wgrad_x3_fused_shape(1, a, &sh)) return 0;
+  return (size_t)sh.nl * sh.g8 * 27 * a.cout * a.cin() * sizeof(float);
 }
 
-
 // one launch + the fixed-order reduction; returns 1 when the layer is not taken (the caller falls back to wgrad_x3)
-static int wgrad_x3_fused(const void* x1, int c1, int pitch1, const void* x2, int c2, int pitch2, const void* dy, int dypitch,
-                          const float* amax_dy, float* ws, float* dw, int dil, int N, int D, int H, int W, int cout, hipStream_t st) {
+static int wgrad_x3_fused(const WgradArgs& a, const float* amax_dy, float* ws, float* dw, int dil, hipStream_t st) {
   X3Shape sh;
-  if (!wgrad_x3_fused_shape(dil, N, D, H, W, c1, c2, cout, &sh)) return 1;
-  using G = Wg3z<3>;
-  WgradParams p;
-  p.x1 = x1; p.x2 = x2; p.c1 = c1; p.c2 = c2; p.p1 = pitch1; p.p2 = pitch2;
-  p.dy = dy; p.dyp = dypitch; p.ws = ws;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.cin = c1 + c2; p.cout = cout;
-  p.tz = ceil_div(D, G::TZ); p.ty = ceil_div(H, G::TY); p.tx = ceil_div(W, G::TX);
-  p.ntiles = sh.nseg; p.nlane = sh.nl; p.nsplit = sh.nl * sh.g8; p.ntaps = 27; p.dil = 1;
+  if (!wgrad_x3_fused_shape(dil, a, &sh)) return 1;
+  WgradParams p = wgrad_params(a, ws, sh.tiles, sh.nl, sh.nl * sh.g8, 27, 1);
   p.seglen = sh.seglen; p.nsegz = sh.nsegz;
   static std::atomic<uint64_t> attr_a{0}, attr_b{0};
   BRATS_ENSURE_LDS_ATTR(conv_wgrad_x3_zwalk_kernel<3>, Wg3z<3>::LDS, attr_a);
   BRATS_ENSURE_LDS_ATTR(conv_wgrad_x3_zwalk_kernel<1>, Wg3z<1>::LDS, attr_b);
   if (sh.narrow)  // the slab columns of the padded ci lanes (c1 < 16) are never written and never read (cin = c1)
-    hipLaunchKernelGGL(conv_wgrad_x3_zwalk_kernel<1>, dim3(p.nsplit, cout / 48, 1), dim3(512), Wg3z<1>::LDS, st, p, amax_dy);
+    hipLaunchKernelGGL(conv_wgrad_x3_zwalk_kernel<1>, dim3(p.nsplit, a.cout / 48, 1), dim3(512), Wg3z<1>::LDS, st, p, amax_dy);
   else
-    hipLaunchKernelGGL(conv_wgrad_x3_zwalk_kernel<3>, dim3(p.nsplit, cout / 48, p.cin / 48), dim3(512), Wg3z<3>::LDS, st, p, amax_dy);
+    hipLaunchKernelGGL(conv_wgrad_x3_zwalk_kernel<3>, dim3(p.nsplit, a.cout / 48, p.cin / 48), dim3(512), Wg3z<3>::LDS, st, p, amax_dy);
   BRATS_CHECK_LAUNCH();
-  wgrad_reduce_launch((const float*)ws, dw, p.nsplit, cout, p.cin, 27, st, amax_dy);
+  wgrad_reduce_launch((const float*)ws, dw, p.nsplit, a.cout, p.cin, 27, st, amax_dy);
   return 0;
 }

@@ -9,8 +9,8 @@ even of an exact integer.  The bounds are preconditions asserted on the operands
 The references are float64 shifted GEMMs, one per tap, independent of torch's convolution.  Activations are channels-last
 [N, D, H, W, C] CPU float32 tensors (the layout the kernels read), weights torch's [Cout, Cin, k, k, k].
 
-The second half mirrors the host selection rules of csrc/conv_wgrad.hip (wgrad_nlane, wgrad_g8, wgrad_tiles,
-wgrad_alltaps_ok, wgrad_reduce_launch, wgrad_shift_geometry) -- the arithmetic is copied, so that a change of a rule makes the
+The second half mirrors the host selection rules of csrc/conv_wgrad.hip (wgrad_nlane, wgrad_split_g8, wgrad_blocks_g8,
+wgrad_tiles, wgrad_plan, wgrad_reduce_launch) -- the arithmetic is copied, so that a change of a rule makes the
 GPU tests fail (their mirrored workspace size no longer equals the library's) instead of quietly exercising another branch."""
 import functools
 
@@ -283,7 +283,7 @@ def wgrad_plan(bits16, dil, c1, c2, cout, n, d, h, w, mode, ncu):
 
 
 def wgrad_shift_plan(bits16, ksize, cin, cout, n, d, h, w):
-    """brats_conv3d_wgrad_shift (wgrad_shift_geometry): one workgroup per tap, so the 512-workgroup rule divides by ntaps."""
+    """brats_conv3d_wgrad_shift (wgrad_plan, shifted): one workgroup per tap, so the 512-workgroup rule divides by ntaps."""
     ntiles = wgrad_ntiles(n, d, h, w)
     ntaps = 27 if ksize == 3 else 1
     cof, cif = wgrad_tiles(not bits16, cin, 0, cout)
