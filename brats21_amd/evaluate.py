@@ -284,8 +284,16 @@ class Evaluator:
     background removal -> (labels) -> crop.
 
     This is the three-channel BraTS chain: the post-processing reads the channels as TC / WT / ET (labels 1 / 2 / 4, cleaning,
-    closest-label replacement), whatever the models could take.  The networks themselves run with 1 to 16 input channels and up to 16 classes; for other label sets use
+    closest-label replacement), whatever the models could take.  The networks themselves run with 1 to 16 input channels and up to 16 classes;
+    for K exclusive classes (an ordinary label map, one class per voxel) pass ``activation="softmax"``; for other label sets use
     inferers.sliding_window_inference / tta_predict on the model and post-process the probabilities yourself.
+
+    ``activation="softmax"`` (2 <= K <= 16 classes): ``probability_sum`` sums softmax probabilities over models x TTA passes
+    (ops.softmax_planes), the result is ``out["labels"]`` -- uint8 [N, 1, D, H, W], the arg-max of the sum, ties to the lowest
+    class, 0 on voxels where every image channel is 0 (ops.argmax_labels) -- and ``out["seg"]`` is its one-hot as float
+    [N, K, ...], so that ``dice`` and ``metrics`` are per-class values (the target is then the one-hot of the label map).
+    ``thresh``, cleaning, replacement and STAPLE are operations on the BraTS regions: with "softmax" they raise
+    NotImplementedError here.
 
     ``use_graph`` (default: only with a sliding window, whose patch shape is fixed): the patch step of each model is
     captured into a hipGraph once and replayed; the graphs follow the models' weights (GraphedPredictor re-captures when
@@ -315,7 +323,14 @@ class Evaluator:
     def __init__(self, models, tta_transforms=None, sliding_window_size=None, sw_batch_size=1, overlap=0.25,
                  k_divisible=8, thresh=0.5, amp=True, use_graph=None, max_graphs=4, amp_dtype=torch.bfloat16,
                  cleaning_areas_threshold=None, replace_value_threshold=None, metrics=None, perform_staple=False,
-                 staple_threshold=0.5):
+                 staple_threshold=0.5, activation="sigmoid"):
+        if activation not in ("sigmoid", "softmax"):
+            raise ValueError(f"activation must be 'sigmoid' or 'softmax', got {activation!r}")
+        if activation == "softmax" and (thresh != 0.5 or cleaning_areas_threshold is not None or replace_value_threshold is not None
+                                        or perform_staple):
+            raise NotImplementedError("Evaluator(activation='softmax'): thresh, cleaning, replacement and STAPLE are operations on the "
+                                      "BraTS regions; the exclusive-class result is the arg-max")
+        self.activation = activation
         _check_int(cleaning_areas_threshold, "cleaning_areas_threshold", allow_none=True)
         _check_int(replace_value_threshold, "replace_value_threshold", allow_none=True)
         if metrics is not None:
@@ -351,20 +366,22 @@ class Evaluator:
 
     @torch.no_grad()
     def probability_sum(self, image):
-        """Sum over models x TTA passes of sigmoid(logits) on the (padded) image -> (sum, passes)."""
+        """Sum over models x TTA passes of sigmoid(logits) -- softmax(logits) with activation="softmax" -- on the (padded)
+        image -> (sum, passes)."""
+        act = torch.sigmoid if self.activation == "sigmoid" else ops.softmax_planes
         acc, passes = None, 0
         for model, predictor in zip(self.models, self.predictors):
             model.eval()
             if self.tta is None:
                 logits = self._logits(predictor, image)
-                acc = torch.sigmoid(logits) if acc is None else acc.add_(torch.sigmoid(logits))
+                acc = act(logits) if acc is None else acc.add_(act(logits))
                 passes += 1
                 continue
             for t in self.tta:
                 logits = self._logits(predictor, t.augment_image(image))
                 if acc is None:
                     acc = torch.zeros(t.deaug_perm.out_shape(logits.shape), dtype=torch.float32, device=image.device)
-                t.accumulate_probability(logits, acc)
+                t.accumulate_probability(logits, acc, self.activation)
                 passes += 1
         return acc, passes
 
@@ -399,7 +416,12 @@ class Evaluator:
         _need_cuda(image, "Evaluator")
         padded, p_b, p_a = shape_to_divisible(image, k=self.k)
         out = {}
-        if self.perform_staple:
+        if self.activation == "softmax":  # the arg-max of the probability sum needs no division by the passes
+            acc = self.probability_sum(padded)[0]
+            labels = ops.argmax_labels(acc, padded)
+            classes = torch.arange(acc.shape[1], device=labels.device, dtype=torch.uint8).view(1, -1, 1, 1, 1)
+            res, want_labels = ((labels == classes).float(), labels), True
+        elif self.perform_staple:
             seg, out["staple"] = self.staple_segmentation(padded)
             res = finalize_segmentation(seg, 1, padded, 0.5, want_labels)
         else:

@@ -3,7 +3,8 @@ reference configures at src/definer.py:184-203 (monai.losses.DiceLoss(include_ba
 sigmoid=True, squared_pred=True, batch=True, reduction='mean', smooth 1e-5)) and the
 deep-supervision averaging of learning/engine.py:312-333; and the distance-map criteria of learning/losses.py:59-467
 (HausdorffLoss, DiceHDLoss, SurfaceLoss = BoundaryLoss, DiceBoundaryLoss) as src/definer.py:246-282 configures them, on
-csrc/edt.hip + csrc/dist_loss.hip: no host round trip, so a step with them captures into a hipGraph like the Dice step."""
+csrc/edt.hip + csrc/dist_loss.hip: no host round trip, so a step with them captures into a hipGraph like the Dice step; and, for
+K exclusive classes, SoftmaxDiceCELoss = learning/losses.py DiceCELoss(softmax=True, to_onehot_y=True) on csrc/softmax_loss.hip."""
 from collections.abc import Sequence
 
 import torch
@@ -393,6 +394,134 @@ class DiceBoundaryLoss(_PreparedCriterion):
 
     def _loss(self, logits, prep):
         return self.lambda_dice * self.dice(logits, prep.t) + self.lambda_boundary * self.boundary(logits, prep.boundary)
+
+
+# ------------------------------------------------------------------------------------------ exclusive classes
+MAX_CLASSES = 16
+
+
+def label_map_u8(target):
+    """The target of an exclusive-class criterion as a contiguous uint8 label map [N, D, H, W]: an integer or float label map
+    [N, 1, D, H, W] / [N, D, H, W] (values outside 0..255 become 255, which every class count ignores), or a one-hot
+    [N, K, D, H, W], arg-maxed as DiceCELoss.ce does (brats_argmax_labels, ties to the lowest class)."""
+    _need_cuda(target, "label_map_u8")
+    if target.dim() == 5 and target.shape[1] != 1:
+        from .ops import argmax_labels
+        return argmax_labels(target)[:, 0]
+    if target.dim() == 5:
+        target = target[:, 0]
+    if target.dim() != 4:
+        raise AssertionError(f"ground truth must be a label map [N, 1, D, H, W] / [N, D, H, W] or a one-hot [N, K, D, H, W], "
+                             f"got {tuple(target.shape)}")
+    if target.dtype == torch.uint8:
+        return target.contiguous()
+    return torch.where((target >= 0) & (target <= 255), target, 255).to(torch.uint8).contiguous()
+
+
+class _LabelTarget(PreparedTarget):
+    """PreparedTarget of SoftmaxDiceCELoss: the uint8 label map, and per class count K (the heads of one step all have the
+    same) the per-sample class counts G [N, K] and valid-voxel counts [N] (brats_label_stats), made on first use and kept."""
+
+    def stats(self, k):
+        if k not in self.counts:
+            from . import _lib
+            lib = _lib.lib()
+            y = self.labels
+            n = y.shape[0]
+            out = torch.empty((n, k + 1), dtype=torch.float32, device=y.device)
+            with torch.cuda.device(y.device):
+                ws = torch.empty(lib.brats_label_stats_ws_floats(n), dtype=torch.float32, device=y.device)
+                _lib.check(lib.brats_label_stats(y.data_ptr(), out.data_ptr(), ws.data_ptr(), n, k, y[0].numel(),
+                                                 torch.cuda.current_stream().cuda_stream), "label_stats")
+            self.counts[k] = (out[:, :k], out[:, k])
+        return self.counts[k]
+
+
+class _SoftmaxDiceCEFn(torch.autograd.Function):
+    """lambda_dice * monai DiceLoss(softmax, to_onehot_y) + lambda_ce * CrossEntropyLoss(mean, ignore_index): one statistics
+    pass and one gradient pass over the logits (brats_softmax_stats / brats_softmax_grad), the [N][K] algebra in torch, the
+    valid-voxel count a device scalar: no host sync."""
+
+    @staticmethod
+    def forward(ctx, logits, y, g, valid, opt):
+        from . import _lib
+        lib = _lib.lib()
+        x = logits.contiguous().float()
+        n, k = x.shape[:2]
+        vox = x[0, 0].numel()
+        sums = torch.empty((n, 3 * k + 1), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            ws = torch.empty(lib.brats_softmax_ws_floats(n, k), dtype=torch.float32, device=x.device)
+            _lib.check(lib.brats_softmax_stats(x.data_ptr(), y.data_ptr(), sums.data_ptr(), ws.data_ptr(), n, k, vox,
+                                               torch.cuda.current_stream().cuda_stream), "softmax_stats")
+        s = sums[:, :3 * k].reshape(n, k, 3)
+        if opt.batch:  # the batch dimension is reduced too: one Dice value per class
+            s, g = s.sum(0, keepdim=True), g.sum(0, keepdim=True)
+        inter, pred = s[..., 0], s[..., 1 if opt.squared_pred else 2]
+        num = 2.0 * inter + opt.smooth_nr
+        if opt.jaccard:
+            den = 2.0 * (g + pred - inter) + opt.smooth_dr
+            a, b = -2.0 / den - 2.0 * num / den ** 2, 2.0 * num / den ** 2
+        else:
+            den = g + pred + opt.smooth_dr
+            a, b = -2.0 / den, num / den ** 2
+        k0 = 0 if opt.include_background else 1
+        f = (1.0 - num / den)[:, k0:]
+        scale = opt.lambda_dice / f.numel()
+        ab = torch.stack([a, b], -1) * scale
+        ab[:, :k0] = 0.0
+        count = valid.sum()
+        coef = torch.cat([ab.expand(n, k, 2).reshape(n, 2 * k), (opt.lambda_ce / count).expand(n, 1)], 1)
+        ctx.save_for_backward(x, y, coef.contiguous())
+        ctx.squared_pred = opt.squared_pred
+        return opt.lambda_dice * f.mean() + opt.lambda_ce * (sums[:, 3 * k].sum() / count)
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import _lib
+        x, y, coef = ctx.saved_tensors
+        n, k = x.shape[:2]
+        coef = (coef * grad).contiguous()
+        dx = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().brats_softmax_grad(x.data_ptr(), y.data_ptr(), coef.data_ptr(), dx.data_ptr(), n, k, x[0, 0].numel(),
+                                                     int(ctx.squared_pred), torch.cuda.current_stream().cuda_stream), "softmax_grad")
+        return dx, None, None, None, None
+
+
+class SoftmaxDiceCELoss(_PreparedCriterion):
+    """learning/losses.py DiceCELoss(softmax=True, to_onehot_y=True, reduction="mean") for K exclusive classes (2 <= K <= 16):
+    lambda_dice * monai DiceLoss(softmax, to_onehot_y, include_background, squared_pred, jaccard, batch, smooth_nr, smooth_dr)
+    + lambda_ce * torch.nn.CrossEntropyLoss(reduction="mean", ignore_index).  The target is an integer label map [N, 1, D, H, W]
+    or [N, D, H, W] of any integer or float dtype, or a one-hot [N, K, D, H, W].  A voxel whose label is not one of 0 .. K-1
+    (255 = unlabelled) is ignored by BOTH parts: it enters no sum, no count and no gradient."""
+
+    def __init__(self, include_background=True, squared_pred=True, jaccard=False, batch=True, smooth_nr=1e-5, smooth_dr=1e-5,
+                 lambda_dice=1.0, lambda_ce=1.0):
+        super().__init__()
+        if lambda_dice < 0.0:
+            raise ValueError("lambda_dice should be no less than 0.0.")
+        if lambda_ce < 0.0:
+            raise ValueError("lambda_ce should be no less than 0.0.")
+        self.include_background, self.squared_pred, self.jaccard, self.batch = bool(include_background), bool(squared_pred), bool(jaccard), bool(batch)
+        self.smooth_nr, self.smooth_dr, self.lambda_dice, self.lambda_ce = float(smooth_nr), float(smooth_dr), float(lambda_dice), float(lambda_ce)
+
+    def prepare(self, target):
+        return _LabelTarget(self, target, labels=label_map_u8(target), counts={})
+
+    def forward(self, logits, target):
+        raw = target.target if isinstance(target, PreparedTarget) else target
+        k = logits.shape[1] if logits.dim() == 5 else 0
+        if not 2 <= k <= MAX_CLASSES:
+            raise NotImplementedError(f"SoftmaxDiceCELoss: logits {tuple(logits.shape)}: [N, K, D, H, W] with 2 <= K <= {MAX_CLASSES} is built")
+        label_shape = (raw.shape[0],) + tuple(raw.shape[2 if raw.dim() == 5 else 1:])
+        if raw.dim() not in (4, 5) or label_shape != (logits.shape[0],) + tuple(logits.shape[2:]) or (raw.dim() == 5 and raw.shape[1] not in (1, k)):
+            raise AssertionError(f"ground truth has different shape ({tuple(raw.shape)}) from input ({tuple(logits.shape)})")
+        return super().forward(logits, target)
+
+    def _loss(self, logits, prep):
+        g, valid = prep.stats(logits.shape[1])
+        return _SoftmaxDiceCEFn.apply(logits, prep.labels, g, valid, self)
 
 
 def deep_supervision_prepared_loss(criterion, outputs, target):

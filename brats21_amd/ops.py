@@ -1336,6 +1336,43 @@ def distance_transform_edt(mask, mode=0):
     return out
 
 
+# ------------------------------------------------------------------------------------------ exclusive classes
+def softmax_planes(logits, inplace=False):
+    """torch.softmax(logits, 1) of f32 NCDHW logits [N, K, D, H, W], 2 <= K <= 16 (csrc/softmax_loss.hip); inplace overwrites a
+    contiguous f32 input."""
+    if not logits.is_cuda:
+        raise _lib.BratsHipError("brats21_amd.ops.softmax_planes runs on the GPU only (no CPU fallback)")
+    x = logits.contiguous().float()
+    n, k = x.shape[:2]
+    if x.dim() != 5 or not 2 <= k <= 16:
+        raise NotImplementedError(f"softmax_planes: logits {tuple(x.shape)}: [N, K, D, H, W] with 2 <= K <= 16 is built")
+    out = x if inplace else torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().brats_softmax_planes(x.data_ptr(), out.data_ptr(), n, k, x[0, 0].numel(), _stream()), "softmax_planes")
+    return out
+
+
+def argmax_labels(prob_sum, img=None):
+    """uint8 label map [N, 1, D, H, W] = arg-max over the classes of prob_sum [N, K, D, H, W] (ties to the lowest class); with
+    img [N, C, D, H, W] a voxel where every image channel is 0 gets label 0 (remove_background_voxels)."""
+    if not prob_sum.is_cuda:
+        raise _lib.BratsHipError("brats21_amd.ops.argmax_labels runs on the GPU only (no CPU fallback)")
+    p = prob_sum.contiguous().float()
+    if p.dim() != 5 or not 1 <= p.shape[1] <= 255:
+        raise ValueError(f"argmax_labels: expected [N, K, D, H, W] with K <= 255, got {tuple(p.shape)}")
+    n, k = p.shape[:2]
+    im = None
+    if img is not None:
+        im = img.contiguous().float()
+        if im.dim() != 5 or im.shape[0] != n or tuple(im.shape[2:]) != tuple(p.shape[2:]):
+            raise ValueError(f"image {tuple(im.shape)} does not match predictions {tuple(p.shape)}")
+    labels = torch.empty((n, 1) + tuple(p.shape[2:]), dtype=torch.uint8, device=p.device)
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().brats_argmax_labels(p.data_ptr(), im.data_ptr() if im is not None else None, labels.data_ptr(), n, k,
+                                                  im.shape[1] if im is not None else 0, p[0, 0].numel(), _stream()), "argmax_labels")
+    return labels
+
+
 # ------------------------------------------------------------------------------------------ STAPLE fusion
 STAPLE_MAX_RATERS = 256
 STAPLE_CHUNK = 16  # iterations enqueued between two reads of the done flags (scripts/time_staple.py records the time with it)

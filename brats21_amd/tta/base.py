@@ -81,8 +81,14 @@ class Transformer:
     def deaugment_label(self, label):
         return label
 
-    def accumulate_probability(self, logits, acc):
-        """acc += sigmoid(deaugment_mask(logits)), one fused pass (learning/engine.py:239-249 on the GPU)."""
+    def accumulate_probability(self, logits, acc, activation="sigmoid"):
+        """acc += sigmoid(deaugment_mask(logits)), one fused pass (learning/engine.py:239-249 on the GPU); activation="softmax"
+        (exclusive classes): the softmax over the class planes (ops.softmax_planes) first, then acc += deaugment_mask of it."""
+        if activation == "softmax":
+            from ..ops import softmax_planes
+            return self.deaug_perm.apply(softmax_planes(logits), out=acc, mode=1)
+        if activation != "sigmoid":
+            raise ValueError(f"activation must be 'sigmoid' or 'softmax', got {activation!r}")
         return self.deaug_perm.apply(logits, out=acc, mode=2)
 
 

@@ -54,7 +54,8 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * only (brats_cc_filter, brats_rare_fill + their workspace queries).  Still 7 after further additions only (brats_hausdorff +
  * its workspace query; brats_edt + its workspace query, brats_sigmoid_argmax_onehot, brats_hd_loss_stats / _grad,
  * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk; brats_staple_blocks / _pack /
- * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd; brats_softmax_stats / _grad / _planes + the workspace
+ * query, brats_label_stats + its workspace query, brats_argmax_labels): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
  * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
@@ -623,6 +624,34 @@ int brats_boundary_loss_stats(const float* logits, const float* dist, float* sum
                               brats_stream_t s);
 int brats_boundary_loss_grad(const float* logits, const float* dist, const float* scale, float* dlogits, size_t total,
                              brats_stream_t s);
+
+/* ---- exclusive-class segmentation (csrc/softmax_loss.hip): the reference's DiceCELoss(softmax=True, to_onehot_y=True)
+ * (learning/losses.py) and the arg-max inference that goes with it.  NCDHW f32 logits [N][K][voxels], 2 <= K <= 16, and a
+ * uint8 label map [N][voxels]; p = softmax over the K planes of a voxel, t_k = [y == k], m = [y < K]: a voxel whose label is
+ * >= K (255 = unlabelled) enters no sum, no count and no gradient (torch's ignore_index).  Labels are compared, never used
+ * as an index.  16-byte accesses where the planes are 16-byte aligned and voxels % 4 == 0, a scalar path otherwise.
+ * softmax_stats: sums[n][3k .. 3k+2] = {sum m t_k p_k, sum m p_k^2, sum m p_k} over the voxels of sample n, sums[n][3K] =
+ *   sum m (logsumexp(x) - x_y).  ws: f32 workspace of brats_softmax_ws_floats(N, K) elements (per-workgroup partials, added
+ *   in block order: no float atomics, bit-reproducible).
+ * softmax_grad: dx_k = m [ p_k (g_k - sum_j g_j p_j) + c (p_k - t_k) ] with g_j = a_j t_j + b_j 2 p_j (squared_pred) or
+ *   a_j t_j + b_j; coef[n][2k] = a_k = dL/dI_k, coef[n][2k+1] = b_k = dL/dP_k, coef[n][2K] = c = lambda_ce / count: device
+ *   memory, one row per sample.
+ * label_stats: counts[n][k] = voxels of sample n with label k (k < K), counts[n][K] = voxels with a label < K; exact in f32.
+ *   ws: brats_label_stats_ws_floats(N) f32 elements.
+ * softmax_planes: out[n][:][v] = softmax(logits[n][:][v]); out may be logits.
+ * argmax_labels: labels[n][v] = arg-max over k of sum[n][k][v], ties to the lowest class; img ([N][C][voxels] f32, may be
+ *   NULL): a voxel where every image channel is 0 gets label 0 (remove_background_voxels, utils/transforms.py:536-550). */
+size_t brats_softmax_ws_floats(int N, int K);
+int brats_softmax_stats(const float* logits, const uint8_t* labels, float* sums /*[N][3K+1]*/, float* ws, int N, int K,
+                        size_t voxels, brats_stream_t s);
+int brats_softmax_grad(const float* logits, const uint8_t* labels, const float* coef /*[N][2K+1]*/, float* dlogits, int N,
+                       int K, size_t voxels, int squared_pred, brats_stream_t s);
+size_t brats_label_stats_ws_floats(int N);
+int brats_label_stats(const uint8_t* labels, float* counts /*[N][K+1]*/, float* ws, int N, int K, size_t voxels,
+                      brats_stream_t s);
+int brats_softmax_planes(const float* logits, float* out, int N, int K, size_t voxels, brats_stream_t s);
+int brats_argmax_labels(const float* sum, const float* img, uint8_t* labels, int N, int K, int C, size_t voxels,
+                        brats_stream_t s);
 
 /* ---- multi-tensor Ranger2020 step (learning/optimizer.py:136-255: RAdam with the
  * N_sma threshold, gradient centralisation :11-20, lookahead :233-240).  All tensors f32, contiguous.

@@ -7,7 +7,12 @@ training-sized batch [2, 3, 128, 128, 128]: median of `--calls` warm calls of
   * the EquiUnet-48 training step (bf16, Ranger2020, eager and as one hipGraph) with --criterion hd beside the fused-Dice
     step of the same run -- the comparison that matters.
 
-    python scripts/time_losses.py [--calls 20] [--patch 128] [--json out.json] [--host] [--no-step]
+  * the exclusive-class criterion losses.SoftmaxDiceCELoss (csrc/softmax_loss.hip) at [2, K, 128, 128, 128], K = 4 and 16:
+    forward + backward over the main head + 4 deep heads beside the torch-eager composition of the same loss (softmax, one-hot,
+    the Dice algebra, F.cross_entropy) on the same box, and the statistics and gradient kernels alone against their byte
+    bounds (4K + 1 and 8K + 1 bytes per voxel).
+
+    python scripts/time_losses.py [--calls 20] [--patch 128] [--json out.json] [--host] [--no-step] [--no-dist] [--no-softmax]
 
 --host, where scipy is importable, also times what the reference does instead on every head (learning/losses.py:153-162):
 device -> host copy, scipy.ndimage.distance_transform_edt per (sample, class), host -> device copy."""
@@ -94,17 +99,56 @@ def step_times(dev, patch, calls, res):
             torch.cuda.empty_cache()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--patch", type=int, default=128)
-    ap.add_argument("--json", default=None)
-    ap.add_argument("--host", action="store_true")
-    ap.add_argument("--no-step", action="store_true")
-    a = ap.parse_args()
-    dev = torch.device("cuda", 0)
-    size = (a.patch,) * 3
-    res = {"shape": [2, 3] + list(size), "calls": a.calls}
+def eager_softmax_dice_ce(x, y, smooth=1e-5):
+    """what a user composes in torch without the criterion: DiceLoss(softmax, to_onehot_y, squared_pred, batch) + cross-entropy"""
+    k = x.shape[1]
+    valid = y != 255
+    m = valid.unsqueeze(1).float()
+    p = torch.softmax(x.float(), 1) * m
+    t = torch.nn.functional.one_hot(torch.where(valid, y, 0), k).movedim(-1, 1).float() * m
+    inter, den = (p * t).sum((0, 2, 3, 4)), t.sum((0, 2, 3, 4)) + (p * p).sum((0, 2, 3, 4))
+    return (1.0 - (2.0 * inter + smooth) / (den + smooth)).mean() + torch.nn.functional.cross_entropy(x.float(), y, ignore_index=255)
+
+
+def softmax_times(dev, patch, calls, res):
+    from brats21_amd import _lib
+    lib = _lib.lib()
+    size = (patch,) * 3
+    n, vox = 2, patch ** 3
+    crit = losses.SoftmaxDiceCELoss()
+    st = torch.cuda.current_stream().cuda_stream
+    for k in (4, 16):
+        g = torch.Generator(device=dev).manual_seed(k)
+        y = torch.randint(0, k, (n,) + size, device=dev, generator=g)
+        y[torch.rand((n,) + size, device=dev, generator=g) < 0.02] = 255
+        heads = [(torch.randn((n, k) + size, device=dev, generator=g) * 3).requires_grad_(True) for _ in range(5)]
+
+        def fwd_bwd(loss_fn):
+            for h in heads:
+                h.grad = None
+            loss_fn().backward()
+        res[f"softmax_dice_ce_k{k}_fwd_bwd_5head_ms"] = time_calls(
+            lambda: fwd_bwd(lambda: losses.deep_supervision_prepared_loss(crit, (heads[0], heads[1:]), y)[0]), calls)
+        res[f"softmax_dice_ce_k{k}_torch_eager_fwd_bwd_5head_ms"] = time_calls(
+            lambda: fwd_bwd(lambda: torch.stack([eager_softmax_dice_ce(h, y) for h in heads]).mean()), calls)
+        # the two streaming kernels alone on one head, against 4K + 1 and 8K + 1 bytes per voxel
+        x, y8 = heads[0].detach(), y.to(torch.uint8)
+        sums = torch.empty((n, 3 * k + 1), device=dev)
+        ws = torch.empty(lib.brats_softmax_ws_floats(n, k), device=dev)
+        coef = torch.full((n, 2 * k + 1), 1e-3, device=dev)
+        dx = torch.empty_like(x)
+        for name, per_voxel, fn in (
+                ("stats", 4 * k + 1, lambda: lib.brats_softmax_stats(x.data_ptr(), y8.data_ptr(), sums.data_ptr(), ws.data_ptr(), n, k, vox, st)),
+                ("grad", 8 * k + 1, lambda: lib.brats_softmax_grad(x.data_ptr(), y8.data_ptr(), coef.data_ptr(), dx.data_ptr(), n, k, vox, 1, st))):
+            t = time_calls(fn, calls)
+            t["bytes"] = per_voxel * n * vox
+            t["tb_per_s"] = round(t["bytes"] / (t["median"] * 1e-3) / 1e12, 3)
+            res[f"softmax_{name}_k{k}_1head_ms"] = t
+        del heads, x, dx
+        torch.cuda.empty_cache()
+
+
+def dist_times(dev, size, a, res):
     t = tumour(2, size, dev)
     heads = [torch.randn((2, 3) + size, device=dev).requires_grad_(True) for _ in range(5)]
     oh = losses.sigmoid_one_hot(heads[0])
@@ -132,6 +176,25 @@ def main():
             res["host_scipy_round_trip_1head_target_s"] = None
     del heads
     torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--patch", type=int, default=128)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--no-dist", action="store_true", help="skip the distance-transform and distance-map criterion legs")
+    ap.add_argument("--no-softmax", action="store_true", help="skip the exclusive-class criterion leg")
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    size = (a.patch,) * 3
+    res = {"shape": [2, 3] + list(size), "calls": a.calls}
+    if not a.no_dist:
+        dist_times(dev, size, a, res)
+    if not a.no_softmax:
+        softmax_times(dev, a.patch, a.calls, res)
     if not a.no_step:
         step_times(dev, a.patch, a.calls, res)
     print(json.dumps(res))
