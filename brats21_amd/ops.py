@@ -1516,6 +1516,124 @@ def staple(raters_or_packer, threshold=0.5, max_iterations=10000, return_probabi
     return seg, info
 
 
+# ------------------------------------------------------------------------------------------ CBAM attention block
+CBAM_EPS = 1e-5  # nn.InstanceNorm3d's default
+
+
+class CbamSaved:
+    """What cbam_fwd keeps for cbam_bwd: only small tensors ([N, C] vectors and f32 / uint16 planes of V voxels)."""
+    __slots__ = ("scale", "pooled", "hidden", "argvox", "comp", "cidx", "z", "stats")
+
+
+def _cbam_params(w1, b1, w2, b2, wc, gamma, beta):
+    ps = [p.detach().contiguous() for p in (w1, b1, w2, b2, wc, gamma, beta)]
+    ch, c = ps[0].shape
+    if tuple(ps[2].shape) != (c, ch) or ps[1].numel() != ch or ps[3].numel() != c or ps[4].numel() != 686 or ps[5].numel() != 1 \
+            or ps[6].numel() != 1:
+        raise _lib.BratsHipError("cbam: parameter shapes do not belong to one CBAM block")
+    for p in ps:
+        _f32(p)
+    return ps, c, ch
+
+
+def _cbam_storage(x, what):
+    if x.dtype == torch.float16:
+        raise _lib.BratsHipError(f"{what}: fp16 storage is not built for the CBAM block (float32 or bfloat16)")
+    return _code(x.dtype)
+
+
+def cbam_fwd(x, w1, b1, w2, b2, wc, gamma, beta, out=None, save=True):
+    """CBAM (channel gate, then spatial gate with InstanceNorm3d(1)) on an NDHWC tensor of float32 or bfloat16 storage:
+    -> (out, saved).  Three reads of x and one write of out; x * s and the spatial gate are never stored at x size.
+    save=False (inference): nothing is kept, saved is None.  w1 [C/r, C], w2 [C, C/r], wc [1, 2, 7, 7, 7]."""
+    l = _lib.lib()
+    xp, c, xpitch = _desc(x)
+    code = _cbam_storage(x, "cbam_fwd")
+    (w1, b1, w2, b2, wc, gamma, beta), cw, ch = _cbam_params(w1, b1, w2, b2, wc, gamma, beta)
+    if cw != c:
+        raise _lib.BratsHipError(f"cbam_fwd: the block is built for {cw} channels, the tensor has {c}")
+    n, d, h, w, _ = x.shape
+    v, dev, st = d * h * w, x.device, _stream()
+    nb, tiles = l.brats_cbam_blocks(code, c, d, h, w), l.brats_cbam_tiles(d, h, w)
+    if nb <= 0:
+        _lib.check(-2, "cbam_fwd")
+    f32 = dict(dtype=torch.float32, device=dev)
+    if out is None:
+        out = new_act(n, d, h, w, c, x.dtype, dev)
+    optr, oc, opitch = _desc(out)
+    if oc != c or out.shape != x.shape or out.dtype != x.dtype:
+        raise _lib.BratsHipError("cbam_fwd: bad output tensor")
+    sv = CbamSaved()
+    sv.pooled, sv.scale = torch.empty((n, 2, c), **f32), torch.empty((n, c), **f32)
+    sv.hidden, sv.argvox = torch.empty((n, 2, ch), **f32), torch.empty((n, c), dtype=torch.int32, device=dev)
+    sv.comp, sv.z, sv.stats = torch.empty((n, 2, v), **f32), torch.empty((n, v), **f32), torch.empty((n, 2), **f32)
+    sv.cidx = torch.empty((n, v), dtype=torch.int16, device=dev) if save else None
+    part = torch.empty(max(3 * nb * n * c, 3 * n * tiles), **f32)
+    with _span("cbam_pool", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_pool(xp, xpitch, part.data_ptr(), sv.pooled.data_ptr(), sv.argvox.data_ptr(), code, n, c, d, h, w, st), "cbam_pool")
+    with _span("cbam_gate", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_gate(sv.pooled.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), sv.hidden.data_ptr(),
+                                     sv.scale.data_ptr(), n, c, ch, st), "cbam_gate")
+    with _span("cbam_compress", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_compress(xp, xpitch, sv.scale.data_ptr(), sv.comp.data_ptr(), sv.cidx.data_ptr() if save else None, code, n, c,
+                                         d, h, w, st), "cbam_compress")
+    with _span("cbam_spatial", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_spatial(sv.comp.data_ptr(), wc.data_ptr(), sv.z.data_ptr(), part.data_ptr(), sv.stats.data_ptr(), CBAM_EPS, n,
+                                        d, h, w, st), "cbam_spatial")
+    with _span("cbam_apply", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_apply(xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                      optr, opitch, code, n, c, d, h, w, st), "cbam_apply")
+    return out, (sv if save else None)
+
+
+def cbam_bwd(dout, x, saved, w1, b1, w2, b2, wc, gamma, beta):
+    """Backward of cbam_fwd: -> (dx, dW1, db1, dW2, db2, dWc, dgamma, dbeta).  Five x-sized transfers: dout and x are read for the
+    gradient of the spatial gate and the sum_v dout * x * g partials, x once more for the rest of ds, and dout is read and dx
+    written by the last pass (which also adds davg / V and the one-hot of the voxel arg-max; it does not need x)."""
+    l = _lib.lib()
+    xp, c, xpitch = _desc(x)
+    dp, _, dpitch = _desc(dout)
+    code = _cbam_storage(x, "cbam_bwd")
+    if dout.shape != x.shape or dout.dtype != x.dtype or not isinstance(saved, CbamSaved) or saved.cidx is None:
+        raise _lib.BratsHipError("cbam_bwd: dout must have x's shape and dtype, saved must come from cbam_fwd(save=True)")
+    (w1, b1, w2, b2, wc, gamma, beta), cw, ch = _cbam_params(w1, b1, w2, b2, wc, gamma, beta)
+    n, d, h, w, _ = x.shape
+    if cw != c or tuple(saved.scale.shape) != (n, c) or tuple(saved.z.shape) != (n, d * h * w):
+        raise _lib.BratsHipError("cbam_bwd: saved tensors / parameters do not belong to this input")
+    v, dev, st, sv = d * h * w, x.device, _stream(), saved
+    nb, tiles = l.brats_cbam_blocks(code, c, d, h, w), l.brats_cbam_tiles(d, h, w)
+    f32 = dict(dtype=torch.float32, device=dev)
+    dzn, dcomp = torch.empty((n, v), **f32), torch.empty((n, 2, v), **f32)
+    asum, rsum, s12 = torch.empty((n, c), **f32), torch.empty((n, c), **f32), torch.empty((n, 2), **f32)
+    dpool, tmp = torch.empty((n, 2, c), **f32), torch.empty(n * c + 2 * n * ch, **f32)
+    part = torch.empty(max(nb * n * (c + 2), n * tiles * 686), **f32)
+    dw1, db1_, dw2, db2_ = torch.empty((ch, c), **f32), torch.empty((ch,), **f32), torch.empty((c, ch), **f32), torch.empty((c,), **f32)
+    dwc, dgamma, dbeta = torch.empty((1, 2, 7, 7, 7), **f32), torch.empty((1,), **f32), torch.empty((1,), **f32)
+    dx = new_act(n, d, h, w, c, x.dtype, dev)
+    dxp, _, dxpitch = _desc(dx)
+    with _span("cbam_bwd_reduce", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_bwd_reduce(dp, dpitch, xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(),
+                                           beta.data_ptr(), dzn.data_ptr(), part.data_ptr(), asum.data_ptr(), s12.data_ptr(), code, n, c, d, h,
+                                           w, st), "cbam_bwd_reduce")
+    with _span("cbam_bwd_spatial", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_bwd_spatial(dzn.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), s12.data_ptr(), gamma.data_ptr(),
+                                            sv.comp.data_ptr(), wc.data_ptr(), dcomp.data_ptr(), part.data_ptr(), dwc.data_ptr(), n, d, h, w, st),
+                   "cbam_bwd_spatial")
+    with _span("cbam_bwd_chan", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_bwd_chan(xp, xpitch, dcomp.data_ptr(), sv.cidx.data_ptr(), part.data_ptr(), rsum.data_ptr(), code, n, c, d, h, w,
+                                         st), "cbam_bwd_chan")
+    with _span("cbam_bwd_gate", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_bwd_gate(asum.data_ptr(), rsum.data_ptr(), sv.pooled.data_ptr(), sv.hidden.data_ptr(), w1.data_ptr(),
+                                         b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), s12.data_ptr(), tmp.data_ptr(), dpool.data_ptr(), dw1.data_ptr(),
+                                         db1_.data_ptr(), dw2.data_ptr(), db2_.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), n, c, ch, st),
+                   "cbam_bwd_gate")
+    with _span("cbam_bwd_apply", code, n, c, d, h, w):
+        _lib.check(l.brats_cbam_bwd_apply(dp, dpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                          dcomp.data_ptr(), sv.cidx.data_ptr(), dpool.data_ptr(), sv.argvox.data_ptr(), dxp, dxpitch, code, n, c,
+                                          d, h, w, st), "cbam_bwd_apply")
+    return dx, dw1, db1_, dw2, db2_, dwc, dgamma, dbeta
+
+
 # ------------------------------------------------------------------------------------------ box calibration
 def probe_box(device=None, mfma_ms=50.0, stream_bytes=403 << 20, modes=(0, 1)):
     """What THIS box delivers right now on the two resources the rooflines are quoted against (csrc/probe.hip): 16-bit

@@ -55,7 +55,7 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * its workspace query; brats_edt + its workspace query, brats_sigmoid_argmax_onehot, brats_hd_loss_stats / _grad,
  * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk; brats_staple_blocks / _pack /
  * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd; brats_softmax_stats / _grad / _planes + the workspace
- * query, brats_label_stats + its workspace query, brats_argmax_labels): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * query, brats_label_stats + its workspace query, brats_argmax_labels; the brats_cbam_* passes): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
  * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
@@ -652,6 +652,57 @@ int brats_label_stats(const uint8_t* labels, float* counts /*[N][K+1]*/, float* 
 int brats_softmax_planes(const float* logits, float* out, int N, int K, size_t voxels, brats_stream_t s);
 int brats_argmax_labels(const float* sum, const float* img, uint8_t* labels, int N, int K, int C, size_t voxels,
                         brats_stream_t s);
+
+/* ---- CBAM attention block (csrc/cbam.hip): CBAM of the reference's AttEquiUnet (networks/equiunet2020.py:147-235: ChannelGate
+ * with the avg + max pools and a shared MLP, SpatialGate = 7x7x7 convolution over [max_c | mean_c] + InstanceNorm3d(1, affine) +
+ * ReLU + sigmoid) on NDHWC activations of dtype BRATS_F32 or BRATS_BF16 (BRATS_F16: BRATS_E_UNSUPPORTED), C a multiple of 8 and
+ * at most 512, at most 2^30 voxels per sample, 16-byte aligned activation pointers.  V = D * H * W.  Element arithmetic is f32; the
+ * [N][C]-sized MLP kernels, the forward stencil and the backward sums that feed cancelling combinations accumulate in f64; every small
+ * tensor is contiguous f32 (indices int32 / uint16).  One entry point per pass; no float atomics, bit-reproducible.
+ *   blocks / tiles: workgroups per sample of the streaming passes / of the stencil passes -- the workspace sizes below use them.
+ *   pool    : pooled[n][0][c] = mean_v x, pooled[n][1][c] = max_v x, argvox[n][c] = the LOWEST voxel index holding the maximum.
+ *             part: 3 * blocks * N * C floats.
+ *   gate    : hidden[n][k][j] = relu(W1 pooled[n][k] + b1) (k = avg, max), scale[n][c] = sigmoid(mlp(avg) + mlp(max));
+ *             w1 [Ch][C], w2 [C][Ch] (nn.Linear layout).
+ *   compress: comp[n][0][v] = max_c x s, comp[n][1][v] = mean_c x s; cidx[n][v] (may be NULL) = the LOWEST channel holding the maximum.
+ *   spatial : z[n][v] = conv3d(comp, wc [1][2][7][7][7], padding 3); stats[n] = {mean, 1 / sqrt(biased var + eps)} of z over the
+ *             sample, from per-tile (count, mean, M2) merged in order.  part: 3 * N * tiles floats.
+ *   apply   : out = x s sigmoid(relu(gamma (z - mean) rstd + beta)).
+ *   bwd_reduce : reads dout and x: dzn[n][v] = the gradient at the norm's output, asum[n][c] = sum_v dout x g, s12[n] = {sum_v dzn,
+ *             sum_v dzn zhat}.  part: blocks * N * (C + 2) floats.
+ *   bwd_spatial: norm backward on load, dcomp[n][2][v] = the input gradient of the convolution, dwc[2 * 343] its weight gradient.
+ *             part: N * tiles * 686 floats.
+ *   bwd_chan: reads x: rsum[n][c] = sum_v x (dcomp0 [c == cidx] + dcomp1 / C).  part: blocks * N * C floats.
+ *   bwd_gate: ds = asum + rsum through sigmoid and MLP (s is recomputed from pooled in f64: its rounding would be multiplied by
+ *             |ds|): dpool[n][k][c] = d loss / d pooled, the four MLP gradients (samples added in order), dgamma, dbeta (from s12).
+ *             tmp: N * C + 2 * N * Ch floats.
+ *   bwd_apply: reads dout, writes dx = (dout g + dcomp0 [c == cidx] + dcomp1 / C) s + dpool[n][0][c] / V + dpool[n][1][c] [v == argvox]. */
+int brats_cbam_blocks(int dtype, int C, int D, int H, int W);
+int brats_cbam_tiles(int D, int H, int W);
+int brats_cbam_pool(const void* x, int xpitch, float* part, float* pooled, int* argvox, int dtype, int N, int C, int D, int H, int W,
+                    brats_stream_t s);
+int brats_cbam_gate(const float* pooled, const float* w1, const float* b1, const float* w2, const float* b2, float* hidden, float* scale,
+                    int N, int C, int Ch, brats_stream_t s);
+int brats_cbam_compress(const void* x, int xpitch, const float* scale, float* comp, uint16_t* cidx, int dtype, int N, int C, int D, int H,
+                        int W, brats_stream_t s);
+int brats_cbam_spatial(const float* comp, const float* wc, float* z, float* part, float* stats, float eps, int N, int D, int H, int W,
+                       brats_stream_t s);
+int brats_cbam_apply(const void* x, int xpitch, const float* scale, const float* z, const float* stats, const float* gamma,
+                     const float* beta, void* out, int opitch, int dtype, int N, int C, int D, int H, int W, brats_stream_t s);
+int brats_cbam_bwd_reduce(const void* dout, int dopitch, const void* x, int xpitch, const float* scale, const float* z,
+                          const float* stats, const float* gamma, const float* beta, float* dzn, float* part, float* asum,
+                          float* s12, int dtype, int N, int C, int D, int H, int W, brats_stream_t s);
+int brats_cbam_bwd_spatial(const float* dzn, const float* z, const float* stats, const float* s12, const float* gamma,
+                           const float* comp, const float* wc, float* dcomp, float* part, float* dwc, int N, int D, int H, int W,
+                           brats_stream_t s);
+int brats_cbam_bwd_chan(const void* x, int xpitch, const float* dcomp, const uint16_t* cidx, float* part, float* rsum, int dtype, int N,
+                        int C, int D, int H, int W, brats_stream_t s);
+int brats_cbam_bwd_gate(const float* asum, const float* rsum, const float* pooled, const float* hidden, const float* w1,
+                        const float* b1, const float* w2, const float* b2, const float* s12, float* tmp, float* dpool, float* dw1,
+                        float* db1, float* dw2, float* db2, float* dgamma, float* dbeta, int N, int C, int Ch, brats_stream_t s);
+int brats_cbam_bwd_apply(const void* dout, int dopitch, const float* scale, const float* z, const float* stats, const float* gamma,
+                         const float* beta, const float* dcomp, const uint16_t* cidx, const float* dpool, const int* argvox, void* dx,
+                         int dxpitch, int dtype, int N, int C, int D, int H, int W, brats_stream_t s);
 
 /* ---- multi-tensor Ranger2020 step (learning/optimizer.py:136-255: RAdam with the
  * N_sma threshold, gradient centralisation :11-20, lookahead :233-240).  All tensors f32, contiguous.
