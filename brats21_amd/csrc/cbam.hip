@@ -8,6 +8,9 @@
 //   out      = x s g
 // Passes over the x-sized tensors: forward pool (read x), compress (read x), apply (read x, write out); backward reduce (read
 // dout, x), chan (read x), apply (read dout, write dx).  x s and g are never stored at x size.
+// In front of a 2x2x2 max pool (the pooled encoder levels of AttEquiUnet) three passes take the pooling in: apply_pool also writes
+// maxpool2(out) and its window-index bytes; bwd_reduce_pool / bwd_apply_pool compose dout = d_skip + maxpool2_bwd(d_pooled) on load
+// and never store it -- bit-identical to the composition with brats_maxpool2_fwd / brats_maxpool2_bwd_idx (pool_up.hip).
 // Every reduction that crosses a workgroup goes through per-workgroup partials that are added in a fixed order (or, for the
 // arg-max, combined under a total order): no floating-point atomics, the same bits at every run.  Ties: the gradient of the
 // per-channel maximum over voxels goes to the lowest voxel index, that of the per-voxel maximum over channels to the lowest
@@ -411,11 +414,133 @@ __global__ void __launch_bounds__(256) cbam_apply_kernel(const T* __restrict__ x
   }
 }
 
+// ---- the gate in front of a 2x2x2 max pool (the encoder levels of AttEquiUnet) ------------------------------------------------------
+// a value as the storage type holds it
+template <typename T, int VW> DEVI void round_to_storage(float (&f)[VW]) {
+  if constexpr (std::is_same<T, bf16_t>::value) {
+#pragma unroll
+    for (int j = 0; j < VW; j += 2) unpack2(pack2(f[j], f[j + 1]), f[j], f[j + 1]);
+  }
+}
+
+// forward: the apply pass that also writes maxpool2(out).  A thread owns one x position of one channel vector and the 2 x 2 (z, y)
+// voxels above it, as in maxpool2_bwd_idx_kernel (pool_up.hip): its four loads and four stores are contiguous runs of a row across
+// the lanes.  It gates and stores them and keeps the maximum of the STORED values with its window index; the two threads of an x
+// pair then merge through LDS, and the even one writes the pooled vector and the index bytes.  The result is the sequential scan
+// of maxpool2_fwd_kernel over the window in (d, h, w) order with `a > max || a != a`: the first of equal maxima, the last NaN.
+// Work item q = xb consecutive positions of the flattened (z pair, y pair, x) index, xb even
+DEVI void pool_merge(float& m, int& k, float m2, int k2) {
+  const bool n1 = m != m, n2 = m2 != m2;
+  const bool take = (n1 || n2) ? (n2 && (!n1 || k2 > k)) : (m2 > m || (m2 == m && k2 < k));
+  if (take) { m = m2; k = k2; }
+}
+template <typename T>
+__global__ void __launch_bounds__(256) cbam_apply_pool_kernel(const T* __restrict__ x, int pitch, const float* __restrict__ scale, const float* __restrict__ z,
+                                                              const float* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              T* __restrict__ out, int opitch, T* __restrict__ pooled, int ppitch, uint8_t* __restrict__ idx,
+                                                              int D, int H, int W, int C, int cv, int xb) {
+  constexpr int VW = 16 / sizeof(T);
+  __shared__ float lmx[VW][256];
+  __shared__ int lam[VW][256];
+  const int n = blockIdx.y, tid = threadIdx.x, cvi = tid % cv, xl = tid / cv;
+  const bool lane_on = xl < xb;
+  const int Ho = H / 2, Wo = W / 2, V = D * H * W, Vp = V / 8, Q = (D / 2) * Ho * W, items = (Q + xb - 1) / xb;
+  const Norm1 nm = load_norm(stats, gamma, beta, n);
+  float sc[VW];
+#pragma unroll
+  for (int j = 0; j < VW; ++j) sc[j] = lane_on ? scale[(size_t)n * C + cvi * VW + j] : 0.f;
+  const T* xn = x + (size_t)n * V * pitch + cvi * VW;
+  T* on = out + (size_t)n * V * opitch + cvi * VW;
+  T* pn = pooled + (size_t)n * Vp * ppitch + cvi * VW;
+  uint8_t* in = idx ? idx + (size_t)n * Vp * C + cvi * VW : nullptr;
+  const float* zn_ = z + (size_t)n * V;
+  for (int item = blockIdx.x; item < items; item += gridDim.x) {
+    const int q = item * xb + xl;
+    const bool ok = lane_on && q < Q;
+    const int xx = q % W, r = q / W, yo = r % Ho, zo = r / Ho;
+    float mx[VW];
+    int am[VW];
+#pragma unroll
+    for (int j = 0; j < VW; ++j) { mx[j] = -INFINITY; am[j] = xx & 1; }
+    if (ok) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int v = ((2 * zo + (k >> 1)) * H + 2 * yo + (k & 1)) * W + xx, kk = 2 * k + (xx & 1);  // kk: the voxel's index in its window
+        float f[VW], zhat, zn;
+        Vec<T, VW>::load(xn + (size_t)v * pitch, f);
+        const float g = spatial_gate(zn_[v], nm, zhat, zn);
+#pragma unroll
+        for (int j = 0; j < VW; ++j) f[j] = f[j] * sc[j] * g;
+        Vec<T, VW>::store(on + (size_t)v * opitch, f);
+        round_to_storage<T, VW>(f);
+#pragma unroll
+        for (int j = 0; j < VW; ++j)
+          if (f[j] > mx[j] || f[j] != f[j]) { mx[j] = f[j]; am[j] = kk; }
+      }
+      if (xx & 1) {
+#pragma unroll
+        for (int j = 0; j < VW; ++j) { lmx[j][tid] = mx[j]; lam[j][tid] = am[j]; }
+      }
+    }
+    __syncthreads();
+    if (ok && !(xx & 1)) {  // (W and xb even: the odd neighbour is thread tid + cv of this item)
+#pragma unroll
+      for (int j = 0; j < VW; ++j) pool_merge(mx[j], am[j], lmx[j][tid + cv], lam[j][tid + cv]);
+      const size_t pv = ((size_t)zo * Ho + yo) * Wo + (xx >> 1);
+      Vec<T, VW>::store(pn + pv * ppitch, mx);
+      if (in) {
+        uint32_t* ap = (uint32_t*)(in + pv * C);
+#pragma unroll
+        for (int qq = 0; qq < VW / 4; ++qq) ap[qq] = am[4 * qq] | (am[4 * qq + 1] << 8) | (am[4 * qq + 2] << 16) | (am[4 * qq + 3] << 24);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// backward: the gradient that arrives at the gate's output when a max pool reads it beside the skip connection, composed on load
+// and never stored: dout[v][c] = round_to_storage(d_skip[v][c] + (idx[parent(v)][c] == pos(v) ? d_pooled[parent(v)][c] : 0)) in
+// the arithmetic of maxpool2_bwd_idx_kernel (pool_up.hip), so the two passes below see the bits its output tensor would hold.
+// Pointers are the sample's, at the thread's channel vector (dskip may be null: no skip term)
+template <typename T> struct PoolGrad {
+  const T* dskip;
+  const T* dpool;      // [D/2][H/2][W/2], pitch ppitch
+  const uint8_t* idx;  // [D/2][H/2][W/2][C] window-index bytes (d, h, w order)
+  int spitch, ppitch, C, H, W;
+  DEVI PoolGrad at(int n, int D, int c0) const {
+    PoolGrad p = *this;
+    const size_t V = (size_t)D * H * W;
+    p.dskip = dskip ? dskip + n * V * spitch + c0 : nullptr;
+    p.dpool = dpool + n * (V / 8) * ppitch + c0;
+    p.idx = idx + n * (V / 8) * C + c0;
+    return p;
+  }
+  template <int VW> DEVI void load(int v, float (&d)[VW]) const {
+    const int xx = v % W, r = v / W, yy = r % H, zz = r / H;
+    const size_t pv = ((size_t)(zz >> 1) * (H >> 1) + (yy >> 1)) * (W >> 1) + (xx >> 1);
+    const int kk = ((zz & 1) << 2) | ((yy & 1) << 1) | (xx & 1);
+    uint32_t aw[VW / 4];
+#pragma unroll
+    for (int q = 0; q < VW / 4; ++q) aw[q] = ((const uint32_t*)(idx + pv * C))[q];
+    float g[VW];
+    Vec<T, VW>::load(dpool + pv * ppitch, g);
+#pragma unroll
+    for (int j = 0; j < VW; ++j) d[j] = 0.f + ((int)((aw[j >> 2] >> (8 * (j & 3))) & 0xff) == kk ? g[j] : 0.f);
+    if (dskip) {
+      float sk[VW];
+      Vec<T, VW>::load(dskip + (size_t)v * spitch, sk);
+#pragma unroll
+      for (int j = 0; j < VW; ++j) d[j] += sk[j];
+    }
+    round_to_storage<T, VW>(d);
+  }
+};
+
 // ---- backward pass 1: reads dout and x ----------------------------------------------------------------------------------------
 // dg[v] = sum_c dout x s  ->  dzn[v] = dg g (1 - g) [zn > 0]  (the gradient at the instance norm's output, written);
-// partials of A[n][c] = sum_v dout x g and of S1 = sum_v dzn, S2 = sum_v dzn zhat
-template <typename T>
-__global__ void __launch_bounds__(256) cbam_bwd_reduce_kernel(const T* __restrict__ dout, int dpitch, const T* __restrict__ x, int pitch,
+// partials of A[n][c] = sum_v dout x g and of S1 = sum_v dzn, S2 = sum_v dzn zhat.  POOL: dout is composed on load (PoolGrad)
+template <typename T, bool POOL>
+__global__ void __launch_bounds__(256) cbam_bwd_reduce_kernel(const T* __restrict__ dout, int dpitch, PoolGrad<T> pool, int D, const T* __restrict__ x, int pitch,
                                                               const float* __restrict__ scale, const float* __restrict__ z, const float* __restrict__ stats,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ dzn,
                                                               float* __restrict__ parta /*[nb][N*C]*/, float* __restrict__ parts /*[nb][N*2]*/, int V,
@@ -427,7 +552,8 @@ __global__ void __launch_bounds__(256) cbam_bwd_reduce_kernel(const T* __restric
   const int v0 = min(V, (int)blockIdx.x * chunk), v1 = min(V, v0 + chunk), iters = (v1 - v0 + vl - 1) / vl;
   const Norm1 nm = load_norm(stats, gamma, beta, n);
   const T* xn = x + (size_t)n * V * pitch + cvi * VW;
-  const T* dn = dout + (size_t)n * V * dpitch + cvi * VW;
+  const T* dn = POOL ? nullptr : dout + (size_t)n * V * dpitch + cvi * VW;
+  const PoolGrad<T> pg = POOL ? pool.at(n, D, cvi * VW) : pool;
   float sc[VW];
   double a[VW];
 #pragma unroll
@@ -443,7 +569,8 @@ __global__ void __launch_bounds__(256) cbam_bwd_reduce_kernel(const T* __restric
     if (ok) {
       float f[VW], d[VW], zhat, zn;
       Vec<T, VW>::load(xn + (size_t)v * pitch, f);
-      Vec<T, VW>::load(dn + (size_t)v * dpitch, d);
+      if constexpr (POOL) pg.load(v, d);
+      else Vec<T, VW>::load(dn + (size_t)v * dpitch, d);
       zv = z[(size_t)n * V + v];
       const double g = (double)spatial_gate(zv, nm, zhat, zn);  // (the gate the forward pass applied)
 #pragma unroll
@@ -643,9 +770,10 @@ __global__ void __launch_bounds__(256) cbam_bwd_params_kernel(const float* __res
 }
 
 // ---- backward pass 3: reads dout, writes dx (x itself is not needed) ------------------------------------------------------------------------------
-// dx = (dout g + dcomp0 [c == arg-max channel] + dcomp1 / C) s + davg / V + dmax [v == arg-max voxel of c]
-template <typename T>
-__global__ void __launch_bounds__(256) cbam_bwd_apply_kernel(const T* __restrict__ dout, int dpitch, const float* __restrict__ scale,
+// dx = (dout g + dcomp0 [c == arg-max channel] + dcomp1 / C) s + davg / V + dmax [v == arg-max voxel of c].  POOL: dout is
+// composed on load (PoolGrad)
+template <typename T, bool POOL>
+__global__ void __launch_bounds__(256) cbam_bwd_apply_kernel(const T* __restrict__ dout, int dpitch, PoolGrad<T> pool, int D, const float* __restrict__ scale,
                                                              const float* __restrict__ z, const float* __restrict__ stats, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, const float* __restrict__ dcomp, const uint16_t* __restrict__ cidx,
                                                              const float* __restrict__ dpool, const int* __restrict__ argvox, T* __restrict__ dx, int xdpitch,
@@ -665,7 +793,8 @@ __global__ void __launch_bounds__(256) cbam_bwd_apply_kernel(const T* __restrict
     dmx[j] = dpool[((size_t)n * 2 + 1) * C + c];
     av[j] = argvox[(size_t)n * C + c];
   }
-  const T* dn = dout + (size_t)n * V * dpitch + cvi * VW;
+  const T* dn = POOL ? nullptr : dout + (size_t)n * V * dpitch + cvi * VW;
+  const PoolGrad<T> pg = POOL ? pool.at(n, D, cvi * VW) : pool;
   T* on = dx + (size_t)n * V * xdpitch + cvi * VW;
   const float* zp = z + (size_t)n * V;
   const float* d0 = dcomp + (size_t)n * 2 * V;
@@ -674,7 +803,8 @@ __global__ void __launch_bounds__(256) cbam_bwd_apply_kernel(const T* __restrict
 #pragma unroll 4
   for (int v = v0 + vlane; v < v1; v += vl) {
     float d[VW], zhat, zn;
-    Vec<T, VW>::load(dn + (size_t)v * dpitch, d);
+    if constexpr (POOL) pg.load(v, d);
+    else Vec<T, VW>::load(dn + (size_t)v * dpitch, d);
     const float g = spatial_gate(zp[v], nm, zhat, zn);
     const float gm = d0[v], ga = d1[v] / (float)C;
     const int cm = (int)cn[v] - cvi * VW;
@@ -788,13 +918,37 @@ extern "C" int brats_cbam_apply(const void* x, int xpitch, const float* scale, c
   return 0;
 }
 
-extern "C" int brats_cbam_bwd_reduce(const void* dout, int dopitch, const void* x, int xpitch, const float* scale, const float* z,
-                                     const float* stats, const float* gamma, const float* beta, float* dzn, float* part, float* asum,
-                                     float* s12, int dtype, int N, int C, int D, int H, int W, brats_stream_t s) {
-  CBAM_CHECKED(cbam_check("cbam_bwd_reduce", dtype, N, C, D, H, W));
-  CBAM_CHECKED(cbam_check_act("cbam_bwd_reduce", x, xpitch, dtype, C));
-  CBAM_CHECKED(cbam_check_act("cbam_bwd_reduce", dout, dopitch, dtype, C));
-  if (!scale || !z || !stats || !gamma || !beta || !dzn || !part || !asum || !s12) BRATS_FAIL(BRATS_E_ARG, "cbam_bwd_reduce: null pointer");
+namespace {
+
+// Where the output gradient of the two dout-reading backward passes comes from: one stored tensor, or (pooled: the _pool entry
+// points) the skip gradient, the pooled gradient and the window-index bytes it is composed from on load
+struct DoutSrc {
+  const void* dout;  // the stored gradient; pooled: the skip gradient, may be NULL
+  int dopitch;
+  const void* dpooled;
+  int dppitch;
+  const unsigned char* idx;
+  bool pooled;
+};
+int cbam_check_dout(const char* what, const DoutSrc& g, int dtype, int C, int D, int H, int W) {
+  if (!g.pooled) return cbam_check_act(what, g.dout, g.dopitch, dtype, C);
+  if ((D | H | W) & 1) BRATS_FAIL(BRATS_E_ARG, "%s: D, H, W = %d, %d, %d must be even (2x2x2 pooling)", what, D, H, W);
+  if (g.dout) CBAM_CHECKED(cbam_check_act(what, g.dout, g.dopitch, dtype, C));
+  CBAM_CHECKED(cbam_check_act(what, g.dpooled, g.dppitch, dtype, C));
+  if (!g.idx || ((size_t)g.idx & 3)) BRATS_FAIL(BRATS_E_ARG, "%s: window-index pointer NULL or not 4-byte aligned", what);
+  return 0;
+}
+template <typename T> PoolGrad<T> pool_grad(const DoutSrc& g, int C, int H, int W) {
+  return PoolGrad<T>{(const T*)g.dout, (const T*)g.dpooled, g.idx, g.dopitch, g.dppitch, C, H, W};
+}
+
+int cbam_bwd_reduce_run(const char* what, const DoutSrc& g, const void* x, int xpitch, const float* scale, const float* z, const float* stats,
+                        const float* gamma, const float* beta, float* dzn, float* part, float* asum, float* s12, int dtype, int N, int C,
+                        int D, int H, int W, brats_stream_t s) {
+  CBAM_CHECKED(cbam_check(what, dtype, N, C, D, H, W));
+  CBAM_CHECKED(cbam_check_act(what, x, xpitch, dtype, C));
+  CBAM_CHECKED(cbam_check_dout(what, g, dtype, C, D, H, W));
+  if (!scale || !z || !stats || !gamma || !beta || !dzn || !part || !asum || !s12) BRATS_FAIL(BRATS_E_ARG, "%s: null pointer", what);
   const int V = D * H * W;
   const Split sp = cbam_split(dtype, C, V);
   float* parta = part;
@@ -802,13 +956,75 @@ extern "C" int brats_cbam_bwd_reduce(const void* dout, int dopitch, const void* 
   hipStream_t st = (hipStream_t)s;
   with_storage(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(cbam_bwd_reduce_kernel<T>, dim3(sp.nb, N), dim3(256), 0, st, (const T*)dout, dopitch, (const T*)x, xpitch, scale, z, stats, gamma,
-                       beta, dzn, parta, parts, V, C, sp.cv, sp.vl, sp.chunk);
+    with_flag(g.pooled, [&](auto p) {
+      hipLaunchKernelGGL((cbam_bwd_reduce_kernel<T, decltype(p)::value>), dim3(sp.nb, N), dim3(256), 0, st, (const T*)g.dout, g.dopitch,
+                         pool_grad<T>(g, C, H, W), D, (const T*)x, xpitch, scale, z, stats, gamma, beta, dzn, parta, parts, V, C, sp.cv, sp.vl, sp.chunk);
+    });
   });
   cbam_sum_partials(parta, asum, sp.nb, N * C, st);
   cbam_sum_partials(parts, s12, sp.nb, N * 2, st);
   BRATS_CHECK_LAUNCH();
   return 0;
+}
+
+int cbam_bwd_apply_run(const char* what, const DoutSrc& g, const float* scale, const float* z, const float* stats, const float* gamma,
+                       const float* beta, const float* dcomp, const uint16_t* cidx, const float* dpool, const int* argvox, void* dx, int dxpitch,
+                       int dtype, int N, int C, int D, int H, int W, brats_stream_t s) {
+  CBAM_CHECKED(cbam_check(what, dtype, N, C, D, H, W));
+  CBAM_CHECKED(cbam_check_dout(what, g, dtype, C, D, H, W));
+  CBAM_CHECKED(cbam_check_act(what, dx, dxpitch, dtype, C));
+  if (!scale || !z || !stats || !gamma || !beta || !dcomp || !cidx || !dpool || !argvox) BRATS_FAIL(BRATS_E_ARG, "%s: null pointer", what);
+  const int V = D * H * W;
+  const Split sp = cbam_split(dtype, C, V);
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    with_flag(g.pooled, [&](auto p) {
+      hipLaunchKernelGGL((cbam_bwd_apply_kernel<T, decltype(p)::value>), dim3(sp.nb, N), dim3(256), 0, (hipStream_t)s, (const T*)g.dout, g.dopitch,
+                         pool_grad<T>(g, C, H, W), D, scale, z, stats, gamma, beta, dcomp, cidx, dpool, argvox, (T*)dx, dxpitch, V, C, sp.cv, sp.vl,
+                         sp.chunk);
+    });
+  });
+  BRATS_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int brats_cbam_apply_pool(const void* x, int xpitch, const float* scale, const float* z, const float* stats, const float* gamma,
+                                     const float* beta, void* out, int opitch, void* pooled, int ppitch, unsigned char* idx, int dtype, int N,
+                                     int C, int D, int H, int W, brats_stream_t s) {
+  CBAM_CHECKED(cbam_check("cbam_apply_pool", dtype, N, C, D, H, W));
+  if ((D | H | W) & 1) BRATS_FAIL(BRATS_E_ARG, "cbam_apply_pool: D, H, W = %d, %d, %d must be even (2x2x2 pooling)", D, H, W);
+  CBAM_CHECKED(cbam_check_act("cbam_apply_pool", x, xpitch, dtype, C));
+  CBAM_CHECKED(cbam_check_act("cbam_apply_pool", out, opitch, dtype, C));
+  CBAM_CHECKED(cbam_check_act("cbam_apply_pool", pooled, ppitch, dtype, C));
+  if (!scale || !z || !stats || !gamma || !beta) BRATS_FAIL(BRATS_E_ARG, "cbam_apply_pool: null pointer");
+  if ((size_t)idx & 3) BRATS_FAIL(BRATS_E_ARG, "cbam_apply_pool: window-index pointer not 4-byte aligned");
+  const int cv = C / vec_width(dtype);
+  int xb = (256 / cv) & ~1;  // x positions per work item: even, so that both voxels of an x pair are in one workgroup
+  if (xb > W) xb = W;
+  const size_t items = ((size_t)(D / 2) * (H / 2) * W + xb - 1) / xb;
+  with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(cbam_apply_pool_kernel<T>, dim3(stream_grid(items, 1, 8 * CBAM_MAX_BLOCKS), N), dim3(256), 0, (hipStream_t)s, (const T*)x, xpitch,
+                       scale, z, stats, gamma, beta, (T*)out, opitch, (T*)pooled, ppitch, idx, D, H, W, C, cv, xb);
+  });
+  BRATS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int brats_cbam_bwd_reduce(const void* dout, int dopitch, const void* x, int xpitch, const float* scale, const float* z,
+                                     const float* stats, const float* gamma, const float* beta, float* dzn, float* part, float* asum,
+                                     float* s12, int dtype, int N, int C, int D, int H, int W, brats_stream_t s) {
+  return cbam_bwd_reduce_run("cbam_bwd_reduce", DoutSrc{dout, dopitch, nullptr, 0, nullptr, false}, x, xpitch, scale, z, stats, gamma, beta, dzn, part,
+                             asum, s12, dtype, N, C, D, H, W, s);
+}
+extern "C" int brats_cbam_bwd_reduce_pool(const void* dskip, int dspitch, const void* dpooled, int dppitch, const unsigned char* idx, const void* x,
+                                          int xpitch, const float* scale, const float* z, const float* stats, const float* gamma,
+                                          const float* beta, float* dzn, float* part, float* asum, float* s12, int dtype, int N, int C, int D,
+                                          int H, int W, brats_stream_t s) {
+  return cbam_bwd_reduce_run("cbam_bwd_reduce_pool", DoutSrc{dskip, dspitch, dpooled, dppitch, idx, true}, x, xpitch, scale, z, stats, gamma, beta, dzn,
+                             part, asum, s12, dtype, N, C, D, H, W, s);
 }
 
 extern "C" int brats_cbam_bwd_spatial(const float* dzn, const float* z, const float* stats, const float* s12, const float* gamma,
@@ -862,17 +1078,13 @@ extern "C" int brats_cbam_bwd_apply(const void* dout, int dopitch, const float* 
                                     const float* stats, const float* gamma, const float* beta, const float* dcomp, const uint16_t* cidx,
                                     const float* dpool, const int* argvox, void* dx, int dxpitch, int dtype, int N, int C, int D, int H, int W,
                                     brats_stream_t s) {
-  CBAM_CHECKED(cbam_check("cbam_bwd_apply", dtype, N, C, D, H, W));
-  CBAM_CHECKED(cbam_check_act("cbam_bwd_apply", dout, dopitch, dtype, C));
-  CBAM_CHECKED(cbam_check_act("cbam_bwd_apply", dx, dxpitch, dtype, C));
-  if (!scale || !z || !stats || !gamma || !beta || !dcomp || !cidx || !dpool || !argvox) BRATS_FAIL(BRATS_E_ARG, "cbam_bwd_apply: null pointer");
-  const int V = D * H * W;
-  const Split sp = cbam_split(dtype, C, V);
-  with_storage(dtype, [&](auto t) {
-    using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(cbam_bwd_apply_kernel<T>, dim3(sp.nb, N), dim3(256), 0, (hipStream_t)s, (const T*)dout, dopitch, scale, z, stats,
-                       gamma, beta, dcomp, cidx, dpool, argvox, (T*)dx, dxpitch, V, C, sp.cv, sp.vl, sp.chunk);
-  });
-  BRATS_CHECK_LAUNCH();
-  return 0;
+  return cbam_bwd_apply_run("cbam_bwd_apply", DoutSrc{dout, dopitch, nullptr, 0, nullptr, false}, scale, z, stats, gamma, beta, dcomp, cidx, dpool, argvox,
+                            dx, dxpitch, dtype, N, C, D, H, W, s);
+}
+extern "C" int brats_cbam_bwd_apply_pool(const void* dskip, int dspitch, const void* dpooled, int dppitch, const unsigned char* idx,
+                                         const float* scale, const float* z, const float* stats, const float* gamma, const float* beta,
+                                         const float* dcomp, const uint16_t* cidx, const float* dpool, const int* argvox, void* dx, int dxpitch,
+                                         int dtype, int N, int C, int D, int H, int W, brats_stream_t s) {
+  return cbam_bwd_apply_run("cbam_bwd_apply_pool", DoutSrc{dskip, dspitch, dpooled, dppitch, idx, true}, scale, z, stats, gamma, beta, dcomp, cidx, dpool,
+                            argvox, dx, dxpitch, dtype, N, C, D, H, W, s);
 }

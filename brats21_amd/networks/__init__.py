@@ -1,2 +1,3 @@
+from .att_equiunet import AttEquiUnet  # noqa: F401
 from .cbam import CBAM  # noqa: F401
 from .equiunet import EquiUnet  # noqa: F401

@@ -505,6 +505,78 @@ def _ref_bwd(ctx, cx, d_ref, d_out):
     return ops.conv3d_narrow(g, ops.pack_weights_narrow(r.conv0.weight, PACK_DGRAD), k, add=rest)
 
 
+def _deep_heads_on(m):
+    return m.deep_supervision and not (m.skip_deep_heads_in_eval and not m.training)
+
+
+def _plus(a, b):
+    return a if b is None else a + b
+
+
+def _decoder_fwd(ctx, cx, down1, down2, down3, down4, bottom, bottom_2):
+    """The decoder and the heads behind bottom_2 (networks/equiunet2020.py:481-498; AttEquiUnet's program hands in its gated
+    tensors) -> [logits, deep heads...]; ctx.bufs / ctx.heads / ctx.top_fused are what _decoder_bwd reads."""
+    m = cx.m
+    cgr = functools.partial(_cgr_fwd, cx)
+
+    def up(t):
+        return _inherit_amax(ops.upsample(t, 2), t)
+
+    up3 = cgr(m.decoder3.ConvBnRelu2, cgr(m.decoder3.ConvBnRelu1, down3, x2=up(bottom_2), lazy=True))
+    up2 = cgr(m.decoder2.ConvBnRelu2, cgr(m.decoder2.ConvBnRelu1, down2, x2=up(up3), lazy=True))
+    u1 = cgr(m.decoder1.ConvBnRelu1, down1, x2=up(up2), lazy=True)
+    # the last layer's activation up1 feeds only the output head: where the kernels for it are built, the head reads
+    # the raw convolution output and applies GroupNorm + act on load (ops.gn_head), the backward recomputes what it
+    # needs (ops.gn_act_bwd_head) -- up1 (2 x 403 MB written + read at 2 x 48 x 128^3) is never stored
+    last = m.decoder1.ConvBnRelu2
+    kact, slope_t = _unit_act(last, cx.act)
+    nk = m.outconv.weight.shape[0]
+    fuse_top = (m.fold_head_fwd and cx.drop is None and not last.batch_norm and slope_t is None and kact in ("relu", "leakyrelu")
+                and nk <= 4 and (not cx.will_bwd or (m.fold_head_bwd and ops.head_fold_ok(m.outconv.weight, kact, slope_t))))
+    if fuse_top:
+        y1 = cgr(last, u1, no_act=True)
+        up1 = None
+        outs = [ops.gn_head(y1, cx.recs[last][5], m.outconv.weight, m.outconv.bias, kact)]
+    else:
+        up1 = cgr(last, u1)
+        outs = [ops.head(up1, m.outconv.weight, m.outconv.bias, 1)]
+    ctx.top_fused = fuse_top
+    ctx.out_shape = tuple(outs[0].shape)
+    ctx.heads = [(m.outconv, up1, 1)]
+    if _deep_heads_on(m):
+        for hd, src, sc in ((m.deep_bottom[0], bottom, 8), (m.deep_bottom2[0], bottom_2, 8), (m.deep3[0], up3, 4),
+                            (m.deep2[0], up2, 2)):
+            outs.append(ops.head(src, hd.weight, hd.bias, sc))
+            ctx.heads.append((hd, src, sc))
+    ctx.bufs = (down1, down2, down3, down4, bottom, bottom_2, up3, up2, up1)
+    return outs
+
+
+def _decoder_bwd(ctx, cx, douts):
+    """Backward of _decoder_fwd -> (d_skip1, d_skip2, d_skip3, the whole gradient of bottom_2, the deep head's gradient of bottom or
+    None)."""
+    m = cx.m
+    _, _, _, _, bottom, bottom_2, up3, up2, up1 = ctx.bufs
+    cbw = functools.partial(_cgr_bwd, cx)
+    c1, c2 = _blk(m.decoder1)
+    # the output head on up1: folded into the GroupNorm backward of the last layer where that is built
+    top, dsrc = _heads_bwd(ctx, cx, douts, m.fold_head_bwd and cx.drop is None and not c2.batch_norm
+                           and ops.head_fold_ok(m.outconv.weight, *_unit_act(c2, cx.act)))
+
+    def extra(t):
+        return dsrc.get(t.data_ptr())
+
+    d_c1 = cbw(c2, None, head=top, bst=c1) if top is not None else cbw(c2, extra(up1) if extra(up1) is not None else torch.zeros_like(up1), bst=c1)
+    d_skip1, d_u1 = cbw(c1, d_c1)
+    d_up2 = _plus(ops.upsample_bwd(d_u1, 2), extra(up2))
+    c1, c2 = _blk(m.decoder2)
+    d_skip2, d_u2 = cbw(c1, cbw(c2, d_up2, bst=c1))
+    d_up3 = _plus(ops.upsample_bwd(d_u2, 2), extra(up3))
+    c1, c2 = _blk(m.decoder3)
+    d_skip3, d_u3 = cbw(c1, cbw(c2, d_up3, bst=c1))
+    return d_skip1, d_skip2, d_skip3, _plus(ops.upsample_bwd(d_u3, 2), extra(bottom_2)), extra(bottom)
+
+
 class _EquiUnetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, dtype, *params):
@@ -518,10 +590,6 @@ class _EquiUnetFn(torch.autograd.Function):
     def _forward(ctx, cx, x0):
         m = cx.m
         cgr = functools.partial(_cgr_fwd, cx)
-
-        def up(t):
-            return _inherit_amax(ops.upsample(t, 2), t)
-
         # encoder (networks/equiunet2020.py:469-475); every tensor is dense NDHWC, the decoder convolutions
         # read the virtual concat [skip | up-sampled] from two pointers (no torch.cat, no strided slices)
         # (the last layer of a level writes its activation -- the skip connection -- and the max-pooled tensor in one pass;
@@ -531,37 +599,10 @@ class _EquiUnetFn(torch.autograd.Function):
         down3, p3 = cgr(m.encoder3.ConvBnRelu2, cgr(m.encoder3.ConvBnRelu1, p2, lazy=True), pool=True)
         down4 = cgr(m.encoder4.ConvBnRelu2, cgr(m.encoder4.ConvBnRelu1, p3, lazy=True))
         # bottom (:477-478): dilated block, then conv over cat[down4, bottom]
-        deep_heads = m.deep_supervision and not (m.skip_deep_heads_in_eval and not m.training)
-        bottom = cgr(m.bottom.ConvBnRelu2, cgr(m.bottom.ConvBnRelu1, down4, lazy=True), lazy=not deep_heads)
+        bottom = cgr(m.bottom.ConvBnRelu2, cgr(m.bottom.ConvBnRelu1, down4, lazy=True), lazy=not _deep_heads_on(m))
         bottom_2 = cgr(m.bottom_2, down4, x2=bottom)
         # decoder (:481-486)
-        up3 = cgr(m.decoder3.ConvBnRelu2, cgr(m.decoder3.ConvBnRelu1, down3, x2=up(bottom_2), lazy=True))
-        up2 = cgr(m.decoder2.ConvBnRelu2, cgr(m.decoder2.ConvBnRelu1, down2, x2=up(up3), lazy=True))
-        u1 = cgr(m.decoder1.ConvBnRelu1, down1, x2=up(up2), lazy=True)
-        # the last layer's activation up1 feeds only the output head: where the kernels for it are built, the head reads
-        # the raw convolution output and applies GroupNorm + act on load (ops.gn_head), the backward recomputes what it
-        # needs (ops.gn_act_bwd_head) -- up1 (2 x 403 MB written + read at 2 x 48 x 128^3) is never stored
-        last = m.decoder1.ConvBnRelu2
-        kact, slope_t = _unit_act(last, cx.act)
-        nk = m.outconv.weight.shape[0]
-        fuse_top = (m.fold_head_fwd and cx.drop is None and not last.batch_norm and slope_t is None and kact in ("relu", "leakyrelu")
-                    and nk <= 4 and (not cx.will_bwd or (m.fold_head_bwd and ops.head_fold_ok(m.outconv.weight, kact, slope_t))))
-        if fuse_top:
-            y1 = cgr(last, u1, no_act=True)
-            up1 = None
-            outs = [ops.gn_head(y1, cx.recs[last][5], m.outconv.weight, m.outconv.bias, kact)]
-        else:
-            up1 = cgr(last, u1)
-            outs = [ops.head(up1, m.outconv.weight, m.outconv.bias, 1)]
-        ctx.top_fused = fuse_top
-        ctx.out_shape = tuple(outs[0].shape)
-        ctx.heads = [(m.outconv, up1, 1)]
-        if deep_heads:
-            for hd, src, sc in ((m.deep_bottom[0], bottom, 8), (m.deep_bottom2[0], bottom_2, 8), (m.deep3[0], up3, 4),
-                                (m.deep2[0], up2, 2)):
-                outs.append(ops.head(src, hd.weight, hd.bias, sc))
-                ctx.heads.append((hd, src, sc))
-        ctx.bufs = (down1, down2, down3, down4, bottom, bottom_2, up3, up2, up1)
+        outs = _decoder_fwd(ctx, cx, down1, down2, down3, down4, bottom, bottom_2)
         if m.refinement:  # (networks/equiunet2020.py:490-491: out = [refunet(out), out])
             outs.insert(0, _ref_fwd(ctx, cx, outs[0]))
         return tuple(outs)
@@ -569,35 +610,16 @@ class _EquiUnetFn(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, cx, *douts):
         m = cx.m
-        down1, down2, down3, down4, bottom, bottom_2, up3, up2, up1 = ctx.bufs
+        down1, down2, down3 = ctx.bufs[:3]
         cbw = functools.partial(_cgr_bwd, cx)
 
         level_bwd = functools.partial(_level_bwd, cx)
         if m.refinement:  # the stage runs first: (d_refined, d_out, deep...) -> (the whole gradient of out, deep...)
             douts = (_ref_bwd(ctx, cx, douts[0], douts[1]),) + tuple(douts[2:])
 
-        c1, c2 = _blk(m.decoder1)
-        # the output head on up1: folded into the GroupNorm backward of the last layer where that is built
-        top, dsrc = _heads_bwd(ctx, cx, douts, m.fold_head_bwd and cx.drop is None and not c2.batch_norm
-                               and ops.head_fold_ok(m.outconv.weight, *_unit_act(c2, cx.act)))
-
-        def extra(t):
-            return dsrc.get(t.data_ptr())
-
-        def plus(a, b):
-            return a if b is None else a + b
-
-        d_c1 = cbw(c2, None, head=top, bst=c1) if top is not None else cbw(c2, extra(up1) if extra(up1) is not None else torch.zeros_like(up1), bst=c1)
-        d_skip1, d_u1 = cbw(c1, d_c1)
-        d_up2 = plus(ops.upsample_bwd(d_u1, 2), extra(up2))
-        c1, c2 = _blk(m.decoder2)
-        d_skip2, d_u2 = cbw(c1, cbw(c2, d_up2, bst=c1))
-        d_up3 = plus(ops.upsample_bwd(d_u2, 2), extra(up3))
-        c1, c2 = _blk(m.decoder3)
-        d_skip3, d_u3 = cbw(c1, cbw(c2, d_up3, bst=c1))
-        d_b2 = plus(ops.upsample_bwd(d_u3, 2), extra(bottom_2))
+        d_skip1, d_skip2, d_skip3, d_b2, d_deep_bottom = _decoder_bwd(ctx, cx, douts)
         d_skip4, d_bot = cbw(m.bottom_2, d_b2)
-        d_bottom = plus(d_bot, extra(bottom))
+        d_bottom = _plus(d_bot, d_deep_bottom)
         c1, c2 = _blk(m.bottom)
         d_down4 = d_skip4 + cbw(c1, cbw(c2, d_bottom, bst=c1))
         c1, c2 = _blk(m.encoder4)

@@ -1522,7 +1522,7 @@ CBAM_EPS = 1e-5  # nn.InstanceNorm3d's default
 
 class CbamSaved:
     """What cbam_fwd keeps for cbam_bwd: only small tensors ([N, C] vectors and f32 / uint16 planes of V voxels)."""
-    __slots__ = ("scale", "pooled", "hidden", "argvox", "comp", "cidx", "z", "stats")
+    __slots__ = ("scale", "pooled", "hidden", "argvox", "comp", "cidx", "z", "stats", "pidx")
 
 
 def _cbam_params(w1, b1, w2, b2, wc, gamma, beta):
@@ -1542,10 +1542,12 @@ def _cbam_storage(x, what):
     return _code(x.dtype)
 
 
-def cbam_fwd(x, w1, b1, w2, b2, wc, gamma, beta, out=None, save=True):
+def cbam_fwd(x, w1, b1, w2, b2, wc, gamma, beta, out=None, save=True, pool=False):
     """CBAM (channel gate, then spatial gate with InstanceNorm3d(1)) on an NDHWC tensor of float32 or bfloat16 storage:
     -> (out, saved).  Three reads of x and one write of out; x * s and the spatial gate are never stored at x size.
-    save=False (inference): nothing is kept, saved is None.  w1 [C/r, C], w2 [C, C/r], wc [1, 2, 7, 7, 7]."""
+    save=False (inference): nothing is kept, saved is None.  w1 [C/r, C], w2 [C, C/r], wc [1, 2, 7, 7, 7].
+    pool=True (D, H, W even): -> (out, maxpool2(out), saved), the pooled tensor written by the last pass (brats_cbam_apply_pool);
+    with save, saved.pidx holds the pooling's window-index bytes for cbam_bwd(..., d_pooled=)."""
     l = _lib.lib()
     xp, c, xpitch = _desc(x)
     code = _cbam_storage(x, "cbam_fwd")
@@ -1568,6 +1570,14 @@ def cbam_fwd(x, w1, b1, w2, b2, wc, gamma, beta, out=None, save=True):
     sv.hidden, sv.argvox = torch.empty((n, 2, ch), **f32), torch.empty((n, c), dtype=torch.int32, device=dev)
     sv.comp, sv.z, sv.stats = torch.empty((n, 2, v), **f32), torch.empty((n, v), **f32), torch.empty((n, 2), **f32)
     sv.cidx = torch.empty((n, v), dtype=torch.int16, device=dev) if save else None
+    sv.pidx = None
+    if pool:
+        if d % 2 or h % 2 or w % 2:
+            raise _lib.BratsHipError(f"cbam_fwd(pool=True): D, H, W = {d}, {h}, {w} must be even")
+        pooled = new_act(n, d // 2, h // 2, w // 2, c, x.dtype, dev)
+        pp, _, ppitch = _desc(pooled)
+        if save:
+            sv.pidx = torch.empty((n, d // 2, h // 2, w // 2, c), dtype=torch.uint8, device=dev)
     part = torch.empty(max(3 * nb * n * c, 3 * n * tiles), **f32)
     with _span("cbam_pool", code, n, c, d, h, w):
         _lib.check(l.brats_cbam_pool(xp, xpitch, part.data_ptr(), sv.pooled.data_ptr(), sv.argvox.data_ptr(), code, n, c, d, h, w, st), "cbam_pool")
@@ -1580,22 +1590,40 @@ def cbam_fwd(x, w1, b1, w2, b2, wc, gamma, beta, out=None, save=True):
     with _span("cbam_spatial", code, n, c, d, h, w):
         _lib.check(l.brats_cbam_spatial(sv.comp.data_ptr(), wc.data_ptr(), sv.z.data_ptr(), part.data_ptr(), sv.stats.data_ptr(), CBAM_EPS, n,
                                         d, h, w, st), "cbam_spatial")
+    if pool:
+        with _span("cbam_apply_pool", code, n, c, d, h, w):
+            _lib.check(l.brats_cbam_apply_pool(xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(),
+                                               beta.data_ptr(), optr, opitch, pp, ppitch, sv.pidx.data_ptr() if save else None, code, n, c,
+                                               d, h, w, st), "cbam_apply_pool")
+        return out, pooled, (sv if save else None)
     with _span("cbam_apply", code, n, c, d, h, w):
         _lib.check(l.brats_cbam_apply(xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                                       optr, opitch, code, n, c, d, h, w, st), "cbam_apply")
     return out, (sv if save else None)
 
 
-def cbam_bwd(dout, x, saved, w1, b1, w2, b2, wc, gamma, beta):
+def cbam_bwd(dout, x, saved, w1, b1, w2, b2, wc, gamma, beta, d_pooled=None):
     """Backward of cbam_fwd: -> (dx, dW1, db1, dW2, db2, dWc, dgamma, dbeta).  Five x-sized transfers: dout and x are read for the
     gradient of the spatial gate and the sum_v dout * x * g partials, x once more for the rest of ds, and dout is read and dx
-    written by the last pass (which also adds davg / V and the one-hot of the voxel arg-max; it does not need x)."""
+    written by the last pass (which also adds davg / V and the one-hot of the voxel arg-max; it does not need x).
+    d_pooled (the block was run with pool=True, save=True): the gradient of the pooled tensor; dout is then the gradient that
+    arrives at `out` directly (the skip connection) or None, and the two dout-reading passes compose dout + maxpool2_bwd(d_pooled)
+    on load (brats_cbam_bwd_reduce_pool / _bwd_apply_pool) -- bit-identical to maxpool2_bwd(out, d_pooled, dx_skip=dout) first."""
     l = _lib.lib()
     xp, c, xpitch = _desc(x)
-    dp, _, dpitch = _desc(dout)
+    dp, dpitch = (None, 0) if dout is None else _desc(dout)[::2]
     code = _cbam_storage(x, "cbam_bwd")
-    if dout.shape != x.shape or dout.dtype != x.dtype or not isinstance(saved, CbamSaved) or saved.cidx is None:
+    if dout is None and d_pooled is None:
+        raise _lib.BratsHipError("cbam_bwd: no gradient given")
+    if (dout is not None and (dout.shape != x.shape or dout.dtype != x.dtype)) or not isinstance(saved, CbamSaved) or saved.cidx is None:
         raise _lib.BratsHipError("cbam_bwd: dout must have x's shape and dtype, saved must come from cbam_fwd(save=True)")
+    if d_pooled is not None:
+        pooled_shape = (x.shape[0], x.shape[1] // 2, x.shape[2] // 2, x.shape[3] // 2, x.shape[4])
+        if saved.pidx is None or tuple(d_pooled.shape) != pooled_shape or d_pooled.dtype != x.dtype:
+            raise _lib.BratsHipError("cbam_bwd: d_pooled must have the pooled tensor's shape and x's dtype, saved must come from "
+                                     "cbam_fwd(pool=True, save=True)")
+        qp, _, qpitch = _desc(d_pooled)
+        pooled_src = (dp, dpitch, qp, qpitch, saved.pidx.data_ptr())
     (w1, b1, w2, b2, wc, gamma, beta), cw, ch = _cbam_params(w1, b1, w2, b2, wc, gamma, beta)
     n, d, h, w, _ = x.shape
     if cw != c or tuple(saved.scale.shape) != (n, c) or tuple(saved.z.shape) != (n, d * h * w):
@@ -1611,10 +1639,13 @@ def cbam_bwd(dout, x, saved, w1, b1, w2, b2, wc, gamma, beta):
     dwc, dgamma, dbeta = torch.empty((1, 2, 7, 7, 7), **f32), torch.empty((1,), **f32), torch.empty((1,), **f32)
     dx = new_act(n, d, h, w, c, x.dtype, dev)
     dxp, _, dxpitch = _desc(dx)
-    with _span("cbam_bwd_reduce", code, n, c, d, h, w):
-        _lib.check(l.brats_cbam_bwd_reduce(dp, dpitch, xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(),
-                                           beta.data_ptr(), dzn.data_ptr(), part.data_ptr(), asum.data_ptr(), s12.data_ptr(), code, n, c, d, h,
-                                           w, st), "cbam_bwd_reduce")
+    # (the pooled forms take (d_skip, pitch, d_pooled, pitch, window indices) where the plain ones take (dout, pitch))
+    reduce, apply, src = (("cbam_bwd_reduce", "cbam_bwd_apply", (dp, dpitch)) if d_pooled is None else
+                          ("cbam_bwd_reduce_pool", "cbam_bwd_apply_pool", pooled_src))
+    with _span(reduce, code, n, c, d, h, w):
+        _lib.check(getattr(l, "brats_" + reduce)(*src, xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(),
+                                                 beta.data_ptr(), dzn.data_ptr(), part.data_ptr(), asum.data_ptr(), s12.data_ptr(), code, n,
+                                                 c, d, h, w, st), reduce)
     with _span("cbam_bwd_spatial", code, n, c, d, h, w):
         _lib.check(l.brats_cbam_bwd_spatial(dzn.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), s12.data_ptr(), gamma.data_ptr(),
                                             sv.comp.data_ptr(), wc.data_ptr(), dcomp.data_ptr(), part.data_ptr(), dwc.data_ptr(), n, d, h, w, st),
@@ -1627,10 +1658,10 @@ def cbam_bwd(dout, x, saved, w1, b1, w2, b2, wc, gamma, beta):
                                          b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), s12.data_ptr(), tmp.data_ptr(), dpool.data_ptr(), dw1.data_ptr(),
                                          db1_.data_ptr(), dw2.data_ptr(), db2_.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), n, c, ch, st),
                    "cbam_bwd_gate")
-    with _span("cbam_bwd_apply", code, n, c, d, h, w):
-        _lib.check(l.brats_cbam_bwd_apply(dp, dpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                          dcomp.data_ptr(), sv.cidx.data_ptr(), dpool.data_ptr(), sv.argvox.data_ptr(), dxp, dxpitch, code, n, c,
-                                          d, h, w, st), "cbam_bwd_apply")
+    with _span(apply, code, n, c, d, h, w):
+        _lib.check(getattr(l, "brats_" + apply)(*src, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(),
+                                                beta.data_ptr(), dcomp.data_ptr(), sv.cidx.data_ptr(), dpool.data_ptr(), sv.argvox.data_ptr(),
+                                                dxp, dxpitch, code, n, c, d, h, w, st), apply)
     return dx, dw1, db1_, dw2, db2_, dwc, dgamma, dbeta
 
 

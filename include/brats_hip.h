@@ -55,7 +55,7 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * its workspace query; brats_edt + its workspace query, brats_sigmoid_argmax_onehot, brats_hd_loss_stats / _grad,
  * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk; brats_staple_blocks / _pack /
  * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd; brats_softmax_stats / _grad / _planes + the workspace
- * query, brats_label_stats + its workspace query, brats_argmax_labels; the brats_cbam_* passes): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * query, brats_label_stats + its workspace query, brats_argmax_labels; the brats_cbam_* passes; brats_cbam_apply_pool, brats_cbam_bwd_reduce_pool / _bwd_apply_pool): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
  * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
@@ -703,6 +703,26 @@ int brats_cbam_bwd_gate(const float* asum, const float* rsum, const float* poole
 int brats_cbam_bwd_apply(const void* dout, int dopitch, const float* scale, const float* z, const float* stats, const float* gamma,
                          const float* beta, const float* dcomp, const uint16_t* cidx, const float* dpool, const int* argvox, void* dx,
                          int dxpitch, int dtype, int N, int C, int D, int H, int W, brats_stream_t s);
+/* The block in front of a 2x2x2 max pool (an encoder level of AttEquiUnet: skip = CBAM(x), next level = maxpool(CBAM(x))).  D, H, W
+ * even (BRATS_E_ARG otherwise); everything else as above.
+ *   apply_pool: apply that also writes pooled [N, D/2, H/2, W/2, C] = maxpool2(out) -- the maximum of the STORED values, the first
+ *             of equal maxima in (d, h, w) window order -- and, with idx != NULL, the window-index bytes [N, D/2, H/2, W/2, C] in the
+ *             encoding of brats_maxpool2_fwd (what brats_maxpool2_bwd_idx reads).
+ *   bwd_reduce_pool / bwd_apply_pool: bwd_reduce / bwd_apply whose dout is composed on load and never stored:
+ *             dout[v][c] = round_to_storage(dskip[v][c] + (idx[parent(v)][c] == pos(v) ? dpooled[parent(v)][c] : 0)), dskip may be
+ *             NULL (no skip term).  Same voxel walk and summation order as the plain passes: bit-identical to running them on the
+ *             output of brats_maxpool2_bwd_idx(idx, dpooled, dskip). */
+int brats_cbam_apply_pool(const void* x, int xpitch, const float* scale, const float* z, const float* stats, const float* gamma,
+                          const float* beta, void* out, int opitch, void* pooled, int ppitch, unsigned char* idx, int dtype, int N,
+                          int C, int D, int H, int W, brats_stream_t s);
+int brats_cbam_bwd_reduce_pool(const void* dskip, int dspitch, const void* dpooled, int dppitch, const unsigned char* idx, const void* x,
+                               int xpitch, const float* scale, const float* z, const float* stats, const float* gamma,
+                               const float* beta, float* dzn, float* part, float* asum, float* s12, int dtype, int N, int C, int D,
+                               int H, int W, brats_stream_t s);
+int brats_cbam_bwd_apply_pool(const void* dskip, int dspitch, const void* dpooled, int dppitch, const unsigned char* idx,
+                              const float* scale, const float* z, const float* stats, const float* gamma, const float* beta,
+                              const float* dcomp, const uint16_t* cidx, const float* dpool, const int* argvox, void* dx, int dxpitch,
+                              int dtype, int N, int C, int D, int H, int W, brats_stream_t s);
 
 /* ---- multi-tensor Ranger2020 step (learning/optimizer.py:136-255: RAdam with the
  * N_sma threshold, gradient centralisation :11-20, lookahead :233-240).  All tensors f32, contiguous.
