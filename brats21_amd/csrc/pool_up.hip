@@ -428,14 +428,26 @@ extern "C" int BRATS_API(brats_upsample_fwd)(const void* x, int xpitch, void* y,
   return 0;
 }
 
+// acc[j] = the stored sum of the adjoint's value and an addend: the value rounded to the storage type first, then the f32 sum
+// of the two stored values, rounded once by the store -- what a separate elementwise add of the two tensors computes
+template <typename T, int VW>
+DEVI void add_stored(float* acc, const T* addp) {
+  float b[VW];
+  if constexpr (VW == 1) b[0] = to_f<T>(addp[0]);
+  else Vec<T, VW>::load(addp, b);
+#pragma unroll
+  for (int j = 0; j < VW; ++j) acc[j] = to_f<T>(from_f<T>(acc[j])) + b[j];
+}
+
 // 1-D adjoint of the lerp along one axis of a tensor viewed as [outer][L][inner_vox][C(+pitch)]:
 // out[o][i][v][c] = sum_{l : i0(l)==i} w0(l)*in[o][l][v][c] + sum_{l : i1(l)==i, i1!=i0} w1(l)*in[..l..].
 // Candidates l are re-derived with the *forward's own* f32 expression, so forward and adjoint are
 // exactly transposes of each other.
-template <typename TI, typename TO, int VW>
+template <typename TI, typename TO, int VW, bool ADD = false>
 __global__ void lerp_adjoint_kernel(const TI* __restrict__ in, int in_pitch, TO* __restrict__ out, int out_pitch,
                                     size_t outer, int Lout /*len of in*/, int Lin /*len of out*/, size_t inner_vox, int C,
-                                    float scale) {
+                                    float scale, const TO* __restrict__ add = nullptr /* ADD: out = stored(adjoint) + add */,
+                                    int add_pitch = 0) {
   const int cv = C / VW;
   const size_t total = outer * Lin * inner_vox * cv;
   const float inv = scale > 0.f ? 1.f / scale : 0.f;
@@ -465,6 +477,7 @@ __global__ void lerp_adjoint_kernel(const TI* __restrict__ in, int in_pitch, TO*
         for (int j = 0; j < VW; ++j) acc[j] += w * a[j];
       }
     }
+    if constexpr (ADD) add_stored<TO, VW>(acc, add + ((o * Lin + i) * inner_vox + iv) * add_pitch + c0);
     if constexpr (VW == 1) out[((o * Lin + i) * inner_vox + iv) * out_pitch + c0] = from_f<TO>(acc[0]);
     else Vec<TO, VW>::store(out + ((o * Lin + i) * inner_vox + iv) * out_pitch + c0, acc);
   }
@@ -542,9 +555,11 @@ DEVI void ubf_add(float* acc, float w, const bf16_t* p) {
   for (int j = 0; j < 8; ++j) acc[j] += w * a[j];
 }
 struct UbfStep { int l[UBF_MAXP]; float wc[UBF_MAXP], wn[UBF_MAXP]; int np; };
+// ADD: dx = stored(adjoint) + add (an addend of dx's extent, pitch addpitch; may be the gradient another consumer produced)
+template <bool ADD>
 __global__ void __launch_bounds__(UBF_THREADS, 4) upsample2_bwd_fused_kernel(const bf16_t* __restrict__ dy, int dypitch, bf16_t* __restrict__ dx,
                                                                           int dxpitch, int C, int D, int H, int W, int cd, float sd,
-                                                                          float sh, float sw) {
+                                                                          float sh, float sw, const bf16_t* __restrict__ add, int addpitch) {
   __shared__ __attribute__((aligned(16))) bf16_t slab[UBF_FH * UBF_FW * UBF_CS];  // the finished coarse plane, D-reduced: [fh][fw][48]
   __shared__ __attribute__((aligned(16))) bf16_t t2s[UBF_TH * UBF_FW * UBF_CS];   // ... H-reduced: [4][fw][48]
   __shared__ float wys[UBF_TH][UBF_FH], wxs[UBF_TW][UBF_FW];
@@ -706,6 +721,9 @@ __global__ void __launch_bounds__(UBF_THREADS, 4) upsample2_bwd_fused_kernel(con
         const float w = wxs[xc][f];
         if (w != 0.f) ubf_add(acc, w, t2s + ((size_t)(h * fw + f) * UBF_CV + cvi) * 8);
       }
+      if constexpr (ADD)
+        add_stored<bf16_t, 8>(acc, add + (size_t)n * D * H * W * addpitch + (size_t)sl * UBF_CS +
+                                       (((size_t)i * H + ya + h) * W + xa + xc) * addpitch + cvi * 8);
       Vec<bf16_t, 8>::store(dst + (((size_t)i * H + ya + h) * W + xa + xc) * dxpitch + cvi * 8, acc);
     }
   }
@@ -878,14 +896,18 @@ extern "C" size_t BRATS_API(brats_upsample_bwd_ws_bytes)(int dtype, int N, int C
 
 template <typename T>
 static int upsample_bwd_t(const T* dy, int dypitch, T* dx, int dxpitch, char* tmp, int N, int C, int D, int H, int W, int sc,
-                          hipStream_t st) {
+                          hipStream_t st, const T* add = nullptr, int addpitch = 0) {
   constexpr int VW = 16 / sizeof(T);
   const int Do = D * sc, Ho = H * sc, Wo = W * sc;
   if constexpr (sizeof(T) == 2) {
     if (const int cd = upsample_bwd_fused_cd(N, C, D, H, W, sc)) {  // one launch, nothing through tmp
       const dim3 grid((unsigned)((size_t)N * (H / UBF_TH) * (W / UBF_TW) * (C / UBF_CS) * (D / cd)));
-      hipLaunchKernelGGL(upsample2_bwd_fused_kernel, grid, dim3(UBF_THREADS), 0, st, dy, dypitch, dx, dxpitch, C, D, H, W, cd,
-                         ac_scale(D, Do), ac_scale(H, Ho), ac_scale(W, Wo));
+      if (add)
+        hipLaunchKernelGGL(upsample2_bwd_fused_kernel<true>, grid, dim3(UBF_THREADS), 0, st, dy, dypitch, dx, dxpitch, C, D, H, W, cd,
+                           ac_scale(D, Do), ac_scale(H, Ho), ac_scale(W, Wo), add, addpitch);
+      else
+        hipLaunchKernelGGL(upsample2_bwd_fused_kernel<false>, grid, dim3(UBF_THREADS), 0, st, dy, dypitch, dx, dxpitch, C, D, H, W, cd,
+                           ac_scale(D, Do), ac_scale(H, Ho), ac_scale(W, Wo), (const bf16_t*)nullptr, 0);
       BRATS_CHECK_LAUNCH();
       return 0;
     }
@@ -903,8 +925,12 @@ static int upsample_bwd_t(const T* dy, int dypitch, T* dx, int dxpitch, char* tm
                      (size_t)N * D, Ho, H, (size_t)Wo, C, ac_scale(H, Ho));
   // W axis: [N*D*H][Wo][1][C] -> [N*D*H][W][1][C(pitch)]
   total = (size_t)N * D * H * W * (C / VW);
-  hipLaunchKernelGGL((lerp_adjoint_kernel<T, T, VW>), dim3(stream_grid(total, 256, POOL_MAX_BLOCKS)), dim3(256), 0, st, (const T*)t2, C, dx,
-                     dxpitch, (size_t)N * D * H, Wo, W, (size_t)1, C, ac_scale(W, Wo));
+  if (add)
+    hipLaunchKernelGGL((lerp_adjoint_kernel<T, T, VW, true>), dim3(stream_grid(total, 256, POOL_MAX_BLOCKS)), dim3(256), 0, st, (const T*)t2, C,
+                       dx, dxpitch, (size_t)N * D * H, Wo, W, (size_t)1, C, ac_scale(W, Wo), add, addpitch);
+  else
+    hipLaunchKernelGGL((lerp_adjoint_kernel<T, T, VW>), dim3(stream_grid(total, 256, POOL_MAX_BLOCKS)), dim3(256), 0, st, (const T*)t2, C, dx,
+                       dxpitch, (size_t)N * D * H, Wo, W, (size_t)1, C, ac_scale(W, Wo), (const T*)nullptr, 0);
   BRATS_CHECK_LAUNCH();
   return 0;
 }
@@ -916,6 +942,19 @@ extern "C" int BRATS_API(brats_upsample_bwd)(const void* dy, int dypitch, void* 
   return with_storage(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
     return upsample_bwd_t<T>((const T*)dy, dypitch, (T*)dx, dxpitch, (char*)tmp, N, C, D, H, W, scale, (hipStream_t)s);
+  });
+}
+// dx = stored(adjoint of dy) + add, bit-equal to brats_upsample_bwd followed by an elementwise add of the two tensors (the f32
+// sum of the two stored values, rounded once); add has dx's extent and must not overlap dx
+extern "C" int BRATS_API(brats_upsample_bwd_add)(const void* dy, int dypitch, const void* add, int addpitch, void* dx, int dxpitch,
+                                                 void* tmp, int dtype, int N, int C, int D, int H, int W, int scale, brats_stream_t s) {
+  const int vw = vec_width(dtype);
+  if (!dy || !add || !dx || !tmp || C % vw || dypitch % vw || dxpitch % vw || addpitch % vw)
+    BRATS_FAIL(BRATS_E_ARG, "upsample_bwd_add: bad argument");
+  return with_storage(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return upsample_bwd_t<T>((const T*)dy, dypitch, (T*)dx, dxpitch, (char*)tmp, N, C, D, H, W, scale, (hipStream_t)s, (const T*)add,
+                             addpitch);
   });
 }
 #include "twin_end.hpp"

@@ -33,6 +33,7 @@ class TrainStep:
         self.amp_dtype = amp_dtype
         self.scaler = scaler
         self._params = None
+        self._one = None
         if amp and amp_dtype == torch.float16 and scaler is None:
             self.scaler = torch.amp.GradScaler("cuda")  # src/main_train.py:110
 
@@ -67,7 +68,11 @@ class TrainStep:
             self.scaler.step(self.optimizer)
             self.scaler.update()
             return loss
-        loss.backward()
+        # the root gradient: one constant 1 kept across steps instead of the ones_like fill autograd launches per backward()
+        one = self._one
+        if one is None or one.device != loss.device or one.dtype != loss.dtype or one.shape != loss.shape:
+            one = self._one = torch.ones_like(loss, requires_grad=False)
+        loss.backward(one)
         if self.buckets is not None:
             self.buckets.finish()
         if self.max_grad_norm is not None:  # Engine._unscale_and_clip (learning/engine.py:442-452)

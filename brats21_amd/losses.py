@@ -5,6 +5,7 @@ deep-supervision averaging of learning/engine.py:312-333; and the distance-map c
 (HausdorffLoss, DiceHDLoss, SurfaceLoss = BoundaryLoss, DiceBoundaryLoss) as src/definer.py:246-282 configures them, on
 csrc/edt.hip + csrc/dist_loss.hip: no host round trip, so a step with them captures into a hipGraph like the Dice step; and, for
 K exclusive classes, SoftmaxDiceCELoss = learning/losses.py DiceCELoss(softmax=True, to_onehot_y=True) on csrc/softmax_loss.hip."""
+import ctypes
 from collections.abc import Sequence
 
 import torch
@@ -44,9 +45,20 @@ def deep_supervision_loss(criterion, outputs, target):
     return criterion(outputs, target), outputs
 
 
+MAX_FUSED_HEADS, MAX_FUSED_CLASSES = 8, 16  # brats_dice_stats_multi / brats_dice_finish
+
+
+def _pointer_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[x.data_ptr() for x in tensors])
+
+
 class _FusedDiceFn(torch.autograd.Function):
-    """loss = mean over heads and classes of (1 - (2I+eps)/(D+eps)); two HBM passes per head in HIP
-    (brats_dice_stats / brats_dice_grad), the [heads, classes] algebra in torch, no host sync."""
+    """loss = mean over heads and classes of (1 - (2I+eps)/(D+eps)), no host sync.  Heads of the target's shape (the training
+    step: every deep head is up-sampled to full size): three launches for all of them -- brats_dice_stats_multi,
+    brats_dice_finish (the ordered sums, the [heads, classes] algebra, the loss) and brats_dice_grad_multi -- with the target
+    read once per pass.  Heads in any other form (a strided view, another dtype, more than 8 of them): two HBM passes per head
+    (brats_dice_stats / brats_dice_grad), the algebra in torch.  Both paths give the same bits; the loss value could differ in
+    its last place where the kernel's order of the final mean is not torch's (csrc/dice.hip, dice_mean)."""
 
     @staticmethod
     def forward(ctx, target, jaccard, eps, *heads):
@@ -56,6 +68,20 @@ class _FusedDiceFn(torch.autograd.Function):
         t = target.contiguous().float()
         n, k = t.shape[:2]
         vox = t[0, 0].numel()
+        ctx.multi = (len(heads) <= MAX_FUSED_HEADS and k <= MAX_FUSED_CLASSES and n * k <= 65535 and t.is_cuda
+                     and all(h.shape == t.shape and h.dtype == torch.float32 and h.is_contiguous() and h.device == t.device for h in heads))
+        if ctx.multi:
+            nh = len(heads)
+            with torch.cuda.device(t.device):
+                ws = torch.empty(lib.brats_dice_multi_ws_floats(nh, n, k), dtype=torch.float32, device=t.device)
+                sums = torch.empty((nh, k, 3), dtype=torch.float32, device=t.device)
+                coef = torch.empty((nh, k, 2), dtype=torch.float32, device=t.device)
+                loss = torch.empty((), dtype=torch.float32, device=t.device)
+                _lib.check(lib.brats_dice_stats_multi(_pointer_array(heads), nh, t.data_ptr(), ws.data_ptr(), n, k, vox, st), "dice_stats_multi")
+                _lib.check(lib.brats_dice_finish(ws.data_ptr(), nh, n, k, vox, eps, int(bool(jaccard)), sums.data_ptr(), coef.data_ptr(),
+                                                 loss.data_ptr(), st), "dice_finish")
+            ctx.save_for_backward(t, coef, *heads)
+            return loss
         hs = [h.contiguous().float() for h in heads]
         sums = torch.empty((len(hs), k, 3), dtype=torch.float32, device=t.device)
         ws = torch.empty(lib.brats_dice_ws_floats(n, k), dtype=torch.float32, device=t.device)  # per-block partials
@@ -83,6 +109,13 @@ class _FusedDiceFn(torch.autograd.Function):
         t, coef, *hs = ctx.saved_tensors
         n, k = t.shape[:2]
         vox = t[0, 0].numel()
+        if ctx.multi:  # coef * g is formed inside the kernel from the device scalar g
+            g = g.to(device=t.device, dtype=torch.float32)
+            with torch.cuda.device(t.device):
+                outs = [torch.empty_like(h) for h in hs]
+                _lib.check(lib.brats_dice_grad_multi(_pointer_array(hs), len(hs), t.data_ptr(), coef.data_ptr(), g.data_ptr(),
+                                                     _pointer_array(outs), n, k, vox, st), "dice_grad_multi")
+            return (None, None, None) + tuple(outs)
         coef = (coef * g).contiguous()
         outs = []
         for i, h in enumerate(hs):

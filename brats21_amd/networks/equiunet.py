@@ -568,13 +568,14 @@ def _decoder_bwd(ctx, cx, douts):
 
     d_c1 = cbw(c2, None, head=top, bst=c1) if top is not None else cbw(c2, extra(up1) if extra(up1) is not None else torch.zeros_like(up1), bst=c1)
     d_skip1, d_u1 = cbw(c1, d_c1)
-    d_up2 = _plus(ops.upsample_bwd(d_u1, 2), extra(up2))
+    # (the deep head's gradient of the same activation is added inside the adjoint's launch: the sum of the two stored tensors)
+    d_up2 = ops.upsample_bwd(d_u1, 2, add=extra(up2))
     c1, c2 = _blk(m.decoder2)
     d_skip2, d_u2 = cbw(c1, cbw(c2, d_up2, bst=c1))
-    d_up3 = _plus(ops.upsample_bwd(d_u2, 2), extra(up3))
+    d_up3 = ops.upsample_bwd(d_u2, 2, add=extra(up3))
     c1, c2 = _blk(m.decoder3)
     d_skip3, d_u3 = cbw(c1, cbw(c2, d_up3, bst=c1))
-    return d_skip1, d_skip2, d_skip3, _plus(ops.upsample_bwd(d_u3, 2), extra(bottom_2)), extra(bottom)
+    return d_skip1, d_skip2, d_skip3, ops.upsample_bwd(d_u3, 2, add=extra(bottom_2)), extra(bottom)
 
 
 class _EquiUnetFn(torch.autograd.Function):

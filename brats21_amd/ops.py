@@ -961,15 +961,27 @@ def set_upsample_bwd_fused(mode):
     return _lib.lib().brats_upsample_bwd_set_fused(mode)
 
 
-def upsample_bwd(dy, scale=2):
+def upsample_bwd(dy, scale=2, add=None, out=None):
+    """The adjoint of upsample; add (a tensor of the result's shape and dtype, e.g. the gradient another consumer of the same
+    activation produced): the result is upsample_bwd(dy) + add, bit for bit, in the same launches (brats_upsample_bwd_add).
+    out: a channel-slice view to write into instead of a new tensor."""
     dptr, c, dp = _desc(dy)
     n, do, ho, wo, _ = dy.shape
     d, h, w = do // scale, ho // scale, wo // scale
     code = _code(dy.dtype)
     ws = torch.empty(_lib.lib().brats_upsample_bwd_ws_bytes(code, n, c, d, h, w, scale), dtype=torch.uint8, device=dy.device)
-    dx = new_act(n, d, h, w, c, dy.dtype, dy.device)
-    _lib.check(_lib.lib().brats_upsample_bwd(dptr, dp, dx.data_ptr(), c, ws.data_ptr(), code, n, c, d, h, w, scale,
-                                             _stream()), "upsample_bwd")
+    dx = new_act(n, d, h, w, c, dy.dtype, dy.device) if out is None else out
+    xptr, xc, xp = _desc(dx)
+    if tuple(dx.shape) != (n, d, h, w, c) or dx.dtype != dy.dtype:
+        raise ValueError(f"upsample_bwd: out {tuple(dx.shape)} {dx.dtype} does not match {(n, d, h, w, c)} {dy.dtype}")
+    if add is None:
+        _lib.check(_lib.lib().brats_upsample_bwd(dptr, dp, xptr, xp, ws.data_ptr(), code, n, c, d, h, w, scale, _stream()), "upsample_bwd")
+        return dx
+    if tuple(add.shape) != (n, d, h, w, c) or add.dtype != dy.dtype:
+        raise ValueError(f"upsample_bwd: addend {tuple(add.shape)} {add.dtype} does not match {(n, d, h, w, c)} {dy.dtype}")
+    aptr, _, ap = _desc(add)
+    _lib.check(_lib.lib().brats_upsample_bwd_add(dptr, dp, aptr, ap, xptr, xp, ws.data_ptr(), code, n, c, d, h, w, scale, _stream()),
+               "upsample_bwd_add")
     return dx
 
 

@@ -452,6 +452,11 @@ int brats_upsample_fwd(const void* x, int xpitch, void* y, int ypitch, int dtype
 size_t brats_upsample_bwd_ws_bytes(int dtype, int N, int C, int D, int H, int W, int scale);
 int brats_upsample_bwd(const void* dy, int dypitch, void* dx, int dxpitch, void* tmp, int dtype,
                        int N, int C, int D, int H, int W, int scale, brats_stream_t s);
+/* dx = adjoint + add in the same launches: the adjoint's value is rounded to the storage type, added to the addend in f32 and
+ * stored once -- bit-equal to brats_upsample_bwd followed by an elementwise add of the two tensors.  add has dx's extent
+ * (pitch addpitch) and must not overlap dx. */
+int brats_upsample_bwd_add(const void* dy, int dypitch, const void* add, int addpitch, void* dx, int dxpitch, void* tmp,
+                           int dtype, int N, int C, int D, int H, int W, int scale, brats_stream_t s);
 /* Test knob: 1 / -1 (default) = scale 2 on 16-bit tensors runs the three axes of the adjoint in one launch (a coarse tile per
  * workgroup, the fine box read once, H and W reductions out of LDS) where it tiles: C a multiple of 48, W of 8, D and H of 4;
  * 0 = the three passes through tmp everywhere.  Bit-identical results; returns the previous setting. */
@@ -531,6 +536,23 @@ int brats_dice_stats(const float* logits, const float* target, float* sums /*[K]
                      size_t voxels, brats_stream_t s);
 int brats_dice_grad(const float* logits, const float* target, const float* coef /*[K][2]*/,
                     float* dlogits, int N, int K, size_t voxels, brats_stream_t s);
+/* The same for 1 <= H <= 8 heads [N][K][voxels] that share one target, in three launches (one statistics pass, one finisher,
+ * one gradient pass): the target is read once per pass.  heads / dlogits are HOST arrays of H device pointers, read during the
+ * call and passed to the kernels by value.  Every value is bit-equal to the per-head entries above; the 16-byte path is taken
+ * when voxels is a multiple of 4 and EVERY plane starts on a 16-byte boundary (one misaligned head sends all through the scalar
+ * loop).
+ *   stats_multi : ws (brats_dice_multi_ws_floats(H, N, K) floats) = per head the per-block partials of brats_dice_stats, head
+ *                 h at ws + h * brats_dice_ws_floats(N, K).
+ *   finish      : sums [H][K][3] = the ordered totals; coef [H][K][2] = dL/dI, dL/dP2 of L = mean over heads and classes of
+ *                 1 - (2 I + eps) / (D + eps), D = T2 + P2 (jaccard: 2 (T2 + P2 - I)); loss = L.  K <= 16.
+ *   grad_multi  : dlogits[h] = gradient of head h for the upstream gradient g (a DEVICE scalar): coef * g is formed inside. */
+size_t brats_dice_multi_ws_floats(int H, int N, int K);
+int brats_dice_stats_multi(const float* const* heads, int H, const float* target, float* ws, int N, int K, size_t voxels,
+                           brats_stream_t s);
+int brats_dice_finish(const float* ws, int H, int N, int K, size_t voxels, float eps, int jaccard, float* sums, float* coef,
+                      float* loss, brats_stream_t s);
+int brats_dice_grad_multi(const float* const* heads, int H, const float* target, const float* coef, const float* g,
+                          float* const* dlogits, int N, int K, size_t voxels, brats_stream_t s);
 
 /* ---- post-forward chain of Engine.evaluate on the GPU.  NCDHW f32.
  * pad_crop: dst[p][z][y][x] = src[p][z-oz][y-oy][x-ox] inside the source box, `fill` outside; positive
