@@ -28,7 +28,12 @@ def get_model(args: argparse.Namespace) -> torch.nn.Module:
         from .networks.equiunet_assp import EquiUnetASSPEvo
 
         return EquiUnetASSPEvo(**kwargs)
-    raise NameError("Not Supported Model")
+    if args.model == "modified_unet":  # src/definer.py:155-170 (no dropout argument there)
+        from .networks import Unet
+
+        return Unet(img_ch=4, output_ch=args.num_classes, features=kwargs["features"], norm_layer=args.norm, act=args.act,
+                    deep_supervision=True)
+    raise NameError("Not Supported Model")  # (r2unet, r2attunet, att_unet of the same family included)
 
 
 _MONAI_ONLY_CRITERIA = ("generalized_dice", "focal", "tversky", "dice_ce", "dice_focal")

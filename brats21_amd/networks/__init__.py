@@ -1,3 +1,4 @@
 from .att_equiunet import AttEquiUnet  # noqa: F401
 from .cbam import CBAM  # noqa: F401
 from .equiunet import EquiUnet  # noqa: F401
+from .unet import Unet  # noqa: F401

@@ -257,6 +257,10 @@ def _cgr_fwd(cx, unit, x, x2=None, *, no_act=False, pool=False, lazy=False):
                 hit = unit._bcn_fold = (key, (w.detach() * a_c.view(-1, 1, 1, 1, 1), cbias, gamma_c, beta_c))
             w, cbias, gamma_c, beta_c = hit[1]
         fp8, lazy = None, False
+    elif unit.conv.bias is not None:
+        # a learnable convolution bias (the units of networks/unet_family.py): it rides in the convolution like bcn's folded
+        # shift; the e4m3 form is not built with one, so such a unit takes the 16-bit convolution
+        cbias, fp8 = unit.conv.bias.detach(), None
     cout = w.shape[0]
     cin_pad = x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)
     c1 = x.shape[-1] if x2 is not None else None
@@ -328,6 +332,8 @@ def _cgr_bwd(cx, unit, dz, *, need_dx=True, head=None, pool=None, bst=None):
         a_c, _, gamma_c, _ = unit.bn.tables()
         w_bwd = unit.conv.weight.detach() * a_c.view(-1, 1, 1, 1, 1)  # the weights the forward convolved with
         fp8 = None
+    elif unit.conv.bias is not None:
+        fp8 = None
     tiles = None
     if isinstance(dz, tuple):
         dz, tiles = dz
@@ -385,6 +391,10 @@ def _cgr_bwd(cx, unit, dz, *, need_dx=True, head=None, pool=None, bst=None):
         pg = _bcn_param_grads(unit, dw, db, dgamma, dbeta)  # dw / db are the gradients of a_c * W and b_c
     else:
         pg = {unit.conv.weight: dw, unit.bn.weight: dgamma, unit.bn.bias: dbeta}
+        if unit.conv.bias is not None:
+            # the channel sum of dy: ops.channel_dot streams the tensor once (the weight-gradient entry's own dbias pass is one
+            # workgroup per channel, see _ref_bwd)
+            pg[unit.conv.bias] = ops.channel_dot(dy).sum(0)
     for prm, g in pg.items():
         cx.put(prm, g)
     if not need_dx:

@@ -985,6 +985,70 @@ def upsample_bwd(dy, scale=2, add=None, out=None):
     return dx
 
 
+def upsample_nearest(x, scale=2, out=None):
+    """nn.Upsample(scale_factor=2) in its default mode on an NDHWC tensor: out[n][z][y][x] = x[n][z // 2][y // 2][x // 2], a copy.
+    out: a channel-slice view to write into instead of a new tensor."""
+    ptr, c, p = _desc(x)
+    n, d, h, w, _ = x.shape
+    if out is None:
+        out = new_act(n, d * scale, h * scale, w * scale, c, x.dtype, x.device)
+    optr, oc, op = _desc(out)
+    if tuple(out.shape) != (n, d * scale, h * scale, w * scale, c) or out.dtype != x.dtype:
+        raise ValueError(f"upsample_nearest: out {tuple(out.shape)} {out.dtype} does not match {(n, d * scale, h * scale, w * scale, c)} {x.dtype}")
+    _lib.check(_lib.lib().brats_upsample_nearest_fwd(ptr, p, optr, op, _code(x.dtype), n, c, d, h, w, scale, _stream()),
+               "upsample_nearest_fwd")
+    return out
+
+
+def upsample_nearest_bwd(dy, scale=2, add=None, out=None):
+    """The adjoint of upsample_nearest: every coarse voxel = the f32 sum of its 8 children, in one launch without a workspace.
+    add / out: as in upsample_bwd (the result is upsample_nearest_bwd(dy) + add, bit for bit)."""
+    dptr, c, dp = _desc(dy)
+    n, do, ho, wo, _ = dy.shape
+    if do % scale or ho % scale or wo % scale:
+        raise ValueError(f"upsample_nearest_bwd: the extent {(do, ho, wo)} is no multiple of the scale {scale}")
+    d, h, w = do // scale, ho // scale, wo // scale
+    dx = new_act(n, d, h, w, c, dy.dtype, dy.device) if out is None else out
+    xptr, xc, xp = _desc(dx)
+    if tuple(dx.shape) != (n, d, h, w, c) or dx.dtype != dy.dtype:
+        raise ValueError(f"upsample_nearest_bwd: out {tuple(dx.shape)} {dx.dtype} does not match {(n, d, h, w, c)} {dy.dtype}")
+    aptr, ap = None, 0
+    if add is not None:
+        if tuple(add.shape) != (n, d, h, w, c) or add.dtype != dy.dtype:
+            raise ValueError(f"upsample_nearest_bwd: addend {tuple(add.shape)} {add.dtype} does not match {(n, d, h, w, c)} {dy.dtype}")
+        aptr, _, ap = _desc(add)
+    _lib.check(_lib.lib().brats_upsample_nearest_bwd(dptr, dp, aptr, ap, xptr, xp, _code(dy.dtype), n, c, d, h, w, scale, _stream()),
+               "upsample_nearest_bwd")
+    return dx
+
+
+def _planes(t, what):
+    if t.dim() != 5 or not t.is_cuda:
+        raise _lib.BratsHipError(f"{what}: expected a CUDA tensor of shape [N, K, D, H, W]")
+    return t.contiguous().float()
+
+
+def planes_nearest(low, scale):
+    """nn.Upsample(scale_factor=scale) in its default mode on f32 NCDHW planes (the deep-head logits), scale 2, 4 or 8."""
+    low = _planes(low, "planes_nearest")
+    n, k, d, h, w = low.shape
+    out = torch.empty((n, k, d * scale, h * scale, w * scale), dtype=torch.float32, device=low.device)
+    _lib.check(_lib.lib().brats_planes_nearest_fwd(low.data_ptr(), out.data_ptr(), n * k, d, h, w, scale, _stream()), "planes_nearest_fwd")
+    return out
+
+
+def planes_nearest_bwd(dout, scale):
+    """The adjoint of planes_nearest: every coarse element = the f32 sum of its scale^3 block, in one fixed order."""
+    dout = _planes(dout, "planes_nearest_bwd")
+    n, k, do, ho, wo = dout.shape
+    if do % scale or ho % scale or wo % scale:
+        raise ValueError(f"planes_nearest_bwd: the extent {(do, ho, wo)} is no multiple of the scale {scale}")
+    dlow = torch.empty((n, k, do // scale, ho // scale, wo // scale), dtype=torch.float32, device=dout.device)
+    _lib.check(_lib.lib().brats_planes_nearest_bwd(dout.data_ptr(), dlow.data_ptr(), n * k, do // scale, ho // scale, wo // scale, scale,
+                                                   _stream()), "planes_nearest_bwd")
+    return dlow
+
+
 # ------------------------------------------------------------------------------------------ heads
 def head(x, weight, bias, scale=1):
     """NCDHW f32 logits [N, K, D*s, H*s, W*s] = upsample_s(conv1x1(x)); weight [K, C, 1,1,1]."""

@@ -55,7 +55,8 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * its workspace query; brats_edt + its workspace query, brats_sigmoid_argmax_onehot, brats_hd_loss_stats / _grad,
  * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk; brats_staple_blocks / _pack /
  * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd; brats_softmax_stats / _grad / _planes + the workspace
- * query, brats_label_stats + its workspace query, brats_argmax_labels; the brats_cbam_* passes; brats_cbam_apply_pool, brats_cbam_bwd_reduce_pool / _bwd_apply_pool): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * query, brats_label_stats + its workspace query, brats_argmax_labels; the brats_cbam_* passes; brats_cbam_apply_pool, brats_cbam_bwd_reduce_pool / _bwd_apply_pool;
+ * brats_upsample_nearest_fwd / _bwd, brats_planes_nearest_fwd / _bwd): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
  * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
@@ -461,6 +462,24 @@ int brats_upsample_bwd_add(const void* dy, int dypitch, const void* add, int add
  * workgroup, the fine box read once, H and W reductions out of LDS) where it tiles: C a multiple of 48, W of 8, D and H of 4;
  * 0 = the three passes through tmp everywhere.  Bit-identical results; returns the previous setting. */
 int brats_upsample_bwd_set_fused(int mode);
+
+/* ---- nearest-neighbour up-sampling (csrc/nearest.hip; nn.Upsample(scale_factor=s) in its default mode, networks/unet_family.py:
+ * 43,170-172).  Arguments as brats_upsample_fwd / brats_upsample_bwd_add: N, C, D, H, W are the COARSE tensor's.
+ * NDHWC pair: dtype BRATS_F32 | BRATS_BF16 | BRATS_F16, scale 2, C and the pitches multiples of a 16-byte vector (4 / 8 elements);
+ * BRATS_E_UNSUPPORTED otherwise.
+ *   fwd: y[n][z][y][x][:] = x[n][z/2][y/2][x/2][:] -- a copy, bit-identical to the source in every dtype.
+ *   bwd: dx[n][z][y][x][:] = the sum of its 8 children of dy, accumulated in f32 in one fixed order (z, y, x offset; x fastest) and
+ *   rounded once to the storage type; no atomics, no workspace.  add (optional, dx's extent, pitch addpitch, must not overlap dx):
+ *   the contract of brats_upsample_bwd_add -- the adjoint rounded to storage, added to add in f32, stored once.  dx may be a channel
+ *   slice (dxpitch > C). */
+int brats_upsample_nearest_fwd(const void* x, int xpitch, void* y, int ypitch, int dtype, int N, int C,
+                               int D, int H, int W, int scale, brats_stream_t s);
+int brats_upsample_nearest_bwd(const void* dy, int dypitch, const void* add /*optional*/, int addpitch, void* dx, int dxpitch,
+                               int dtype, int N, int C, int D, int H, int W, int scale, brats_stream_t s);
+/* The same pair on f32 NCDHW planes (the deep-supervision logits): low [planes][D][H][W] <-> out [planes][D*s][H*s][W*s], scale 2, 4
+ * or 8 (BRATS_E_UNSUPPORTED otherwise).  bwd: dlow = the sum of the s^3 block of dout in f32 in the fixed order (z, y, x offset). */
+int brats_planes_nearest_fwd(const float* low, float* out, int planes, int D, int H, int W, int scale, brats_stream_t s);
+int brats_planes_nearest_bwd(const float* dout, float* dlow, int planes, int D, int H, int W, int scale, brats_stream_t s);
 
 /* ---- narrow-output 3x3x3 convolution (csrc/conv_narrow.hip): C input channels (a multiple of 8) -> 1 <= K <= 16 planes, zero
  * padding, dilation 1:  out[n][k][z][y][x] (f32, NCDHW) = add[n][k][z][y][x] + bias[k] + sum_taps sum_c w[k][c][tap] * x[n][z+dz][y+dy][x+dx][c]
