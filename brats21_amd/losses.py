@@ -4,7 +4,9 @@ sigmoid=True, squared_pred=True, batch=True, reduction='mean', smooth 1e-5)) and
 deep-supervision averaging of learning/engine.py:312-333; and the distance-map criteria of learning/losses.py:59-467
 (HausdorffLoss, DiceHDLoss, SurfaceLoss = BoundaryLoss, DiceBoundaryLoss) as src/definer.py:246-282 configures them, on
 csrc/edt.hip + csrc/dist_loss.hip: no host round trip, so a step with them captures into a hipGraph like the Dice step; and, for
-K exclusive classes, SoftmaxDiceCELoss = learning/losses.py DiceCELoss(softmax=True, to_onehot_y=True) on csrc/softmax_loss.hip."""
+K exclusive classes, SoftmaxDiceCELoss = learning/losses.py DiceCELoss(softmax=True, to_onehot_y=True) on csrc/softmax_loss.hip;
+and the multi-label criteria src/definer.py:204-245 configures as dice_ce, dice_focal, focal and tversky (DiceCELoss, DiceFocalLoss,
+FocalLoss, TverskyLoss) on csrc/sigmoid_loss.hip."""
 import ctypes
 from collections.abc import Sequence
 
@@ -555,6 +557,204 @@ class SoftmaxDiceCELoss(_PreparedCriterion):
     def _loss(self, logits, prep):
         g, valid = prep.stats(logits.shape[1])
         return _SoftmaxDiceCEFn.apply(logits, prep.labels, g, valid, self)
+
+
+# ------------------------------------------------------------------------------------------ multi-label criteria: dice_ce, dice_focal, focal, tversky
+SIG_FOCAL, SIG_CE = 1, 2  # BRATS_SIG_FOCAL, BRATS_SIG_CE of include/brats_hip.h
+
+
+def _dice_algebra(inter, p2, t2, d):
+    """monai DiceLoss(sigmoid, squared_pred, reduction mean) from the per-(sample, class) sums [N, K], `d` a _SigmoidDice:
+    (value, d value / d I, d value / d P2), the derivatives [N, K]."""
+    n = inter.shape[0]
+    if d.batch:  # the batch dimension is reduced too: one Dice value per class
+        inter, p2, t2 = inter.sum(0, keepdim=True), p2.sum(0, keepdim=True), t2.sum(0, keepdim=True)
+    num = 2.0 * inter + d.smooth_nr
+    if d.jaccard:
+        den = 2.0 * (t2 + p2 - inter) + d.smooth_dr
+        a, b = -2.0 / den - 2.0 * num / den ** 2, 2.0 * num / den ** 2
+    else:
+        den = t2 + p2 + d.smooth_dr
+        a, b = -2.0 / den, num / den ** 2
+    f = 1.0 - num / den
+    return f.mean(), (a / f.numel()).expand(n, -1), (b / f.numel()).expand(n, -1)
+
+
+class _SigmoidLossFn(torch.autograd.Function):
+    """One of the four multi-label criteria: one statistics pass and one gradient pass over the logits (brats_sigmoid_loss_stats /
+    brats_sigmoid_loss_grad, csrc/sigmoid_loss.hip); the criterion's `_algebra` turns the [N, K] sums into the value and the
+    coefficient table in torch on the device, and the upstream gradient is multiplied into the table there: no host sync."""
+
+    @staticmethod
+    def forward(ctx, logits, prep, crit):
+        from . import _lib
+        lib = _lib.lib()
+        x = logits.contiguous().float()
+        n, k = x.shape[:2]
+        vox = x[0, 0].numel()
+        classmap = prep.classmap if crit.terms & SIG_CE else None
+        sums = torch.empty((n, 4 * k + 1), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            ws = torch.empty(lib.brats_sigmoid_loss_ws_floats(n, k), dtype=torch.float32, device=x.device)
+            _lib.check(lib.brats_sigmoid_loss_stats(x.data_ptr(), prep.t.data_ptr(), classmap.data_ptr() if classmap is not None else None,
+                                                    sums.data_ptr(), ws.data_ptr(), n, k, vox, crit.terms, crit.gamma,
+                                                    torch.cuda.current_stream().cuda_stream), "sigmoid_loss_stats")
+        inter, p2, p1, focal = sums[:, :4 * k].reshape(n, k, 4).unbind(-1)
+        value, (a, b, c, fc), cce = crit._algebra(inter, p2, p1, focal, sums[:, 4 * k], prep.tsums[..., 0], prep.tsums[..., 1], vox)
+        zero = torch.zeros((n, k), dtype=torch.float32, device=x.device)
+        table = torch.stack([zero if v is None else v.expand(n, k) for v in (a, b, c, fc)], -1).reshape(n, 4 * k)
+        coef = torch.cat([table, torch.full((n, 1), cce, dtype=torch.float32, device=x.device)], 1)
+        ctx.save_for_backward(x, prep.t, classmap, coef)
+        ctx.terms, ctx.gamma = crit.terms, crit.gamma
+        return value
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import _lib
+        x, t, classmap, coef = ctx.saved_tensors
+        n, k = x.shape[:2]
+        coef = (coef * grad).contiguous()
+        dx = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().brats_sigmoid_loss_grad(x.data_ptr(), t.data_ptr(), classmap.data_ptr() if classmap is not None else None,
+                                                          coef.data_ptr(), dx.data_ptr(), n, k, x[0, 0].numel(), ctx.terms, ctx.gamma,
+                                                          torch.cuda.current_stream().cuda_stream), "sigmoid_loss_grad")
+        return dx, None, None
+
+
+class _SigmoidCriterion(_PreparedCriterion):
+    """Base of the four: `terms` (SIG_FOCAL | SIG_CE) says what the passes compute beside the Dice sums, `gamma` is the focal
+    exponent.  prepare(target) is the one pass over the target of a step (brats_sigmoid_target_prepare): the upcast target, its
+    per-(sample, class) sums T1 and T2 and, for the CE term, the class map -- shared by every deep-supervision head."""
+    terms, gamma = 0, 0.0
+
+    def prepare(self, target):
+        from . import _lib
+        lib = _lib.lib()
+        _need_cuda(target, type(self).__name__)
+        if target.dim() < 3 or target.shape[1] > MAX_CLASSES:
+            raise NotImplementedError(f"{type(self).__name__}: target {tuple(target.shape)}: [N, K, ...] with K <= {MAX_CLASSES} is built")
+        t = target.contiguous().float()
+        n, k = t.shape[:2]
+        tsums = torch.empty((n, k, 2), dtype=torch.float32, device=t.device)
+        classmap = torch.empty((n,) + tuple(t.shape[2:]), dtype=torch.uint8, device=t.device) if self.terms & SIG_CE else None
+        with torch.cuda.device(t.device):
+            ws = torch.empty(lib.brats_sigmoid_loss_ws_floats(n, k), dtype=torch.float32, device=t.device)
+            _lib.check(lib.brats_sigmoid_target_prepare(t.data_ptr(), tsums.data_ptr(), classmap.data_ptr() if classmap is not None else None,
+                                                        ws.data_ptr(), n, k, t[0, 0].numel(),
+                                                        torch.cuda.current_stream().cuda_stream), "sigmoid_target_prepare")
+        return PreparedTarget(self, target, t=t, tsums=tsums, classmap=classmap)
+
+    def forward(self, logits, target):
+        raw = target.target if isinstance(target, PreparedTarget) else target
+        if logits.dim() != raw.dim():
+            raise ValueError("the number of dimensions for input and target should be the same.")
+        if logits.shape != raw.shape:
+            raise AssertionError(f"ground truth has different shape ({tuple(raw.shape)}) from input ({tuple(logits.shape)})")
+        if logits.dim() < 3 or logits.shape[1] > MAX_CLASSES:
+            raise NotImplementedError(f"{type(self).__name__}: logits {tuple(logits.shape)}: [N, K, ...] with K <= {MAX_CLASSES} is built")
+        return super().forward(logits, target)
+
+    def _loss(self, logits, prep):
+        return _SigmoidLossFn.apply(logits, prep, self)
+
+
+def _nonnegative(**lambdas):
+    for name, v in lambdas.items():
+        if v < 0.0:
+            raise ValueError(f"{name} should be no less than 0.0.")
+    return [float(v) for v in lambdas.values()]
+
+
+class DiceCELoss(_SigmoidCriterion):
+    """learning/losses.py:470-595 as src/definer.py:204-212 configures it (sigmoid=True, squared_pred=True, batch=True):
+    lambda_dice * monai DiceLoss(sigmoid) + lambda_ce * torch.nn.CrossEntropyLoss(mean) on the raw logits against
+    y = argmax_k target (DiceCELoss.ce: ties to the lowest channel, so a background voxel and an all-ones voxel are class 0 --
+    the reference's behaviour, kept).  For one class out of K per voxel see SoftmaxDiceCELoss."""
+    terms = SIG_CE
+
+    def __init__(self, include_background=True, to_onehot_y=False, sigmoid=False, softmax=False, other_act=None, squared_pred=False,
+                 jaccard=False, reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5, batch=False, ce_weight=None, lambda_dice=1.0,
+                 lambda_ce=1.0):
+        super().__init__()
+        if softmax and to_onehot_y:
+            raise NotImplementedError("DiceCELoss(softmax=True, to_onehot_y=True) is losses.SoftmaxDiceCELoss")
+        _check_reference_options("DiceCELoss", sigmoid, softmax, to_onehot_y, other_act, reduction)
+        if ce_weight is not None:
+            raise NotImplementedError("DiceCELoss: ce_weight is not built (the reference factory never sets it)")
+        self.dice = _SigmoidDice("DiceCELoss", include_background, squared_pred, jaccard, smooth_nr, smooth_dr, batch)
+        self.lambda_dice, self.lambda_ce = _nonnegative(lambda_dice=lambda_dice, lambda_ce=lambda_ce)
+
+    def _algebra(self, inter, p2, p1, focal, ce, t1, t2, vox):
+        dice, a, b = _dice_algebra(inter, p2, t2, self.dice)
+        voxels = float(inter.shape[0] * vox)
+        value = self.lambda_dice * dice + self.lambda_ce * (ce.sum() / voxels)
+        return value, (self.lambda_dice * a, self.lambda_dice * b, None, None), self.lambda_ce / voxels
+
+
+class DiceFocalLoss(_SigmoidCriterion):
+    """monai 0.6.0 DiceFocalLoss as src/definer.py:213-221 configures it (sigmoid=True, squared_pred=True, batch=False):
+    lambda_dice * DiceLoss(sigmoid) + lambda_focal * FocalLoss(gamma) on the raw logits."""
+    terms = SIG_FOCAL
+
+    def __init__(self, include_background=True, to_onehot_y=False, sigmoid=False, softmax=False, other_act=None, squared_pred=False,
+                 jaccard=False, reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5, batch=False, gamma=2.0, focal_weight=None,
+                 lambda_dice=1.0, lambda_focal=1.0):
+        super().__init__()
+        _check_reference_options("DiceFocalLoss", sigmoid, softmax, to_onehot_y, other_act, reduction)
+        if focal_weight is not None:
+            raise NotImplementedError("DiceFocalLoss: focal_weight is not built (the reference factory never sets it)")
+        self.dice = _SigmoidDice("DiceFocalLoss", include_background, squared_pred, jaccard, smooth_nr, smooth_dr, batch)
+        self.gamma = float(gamma)
+        self.lambda_dice, self.lambda_focal = _nonnegative(lambda_dice=lambda_dice, lambda_focal=lambda_focal)
+
+    def _algebra(self, inter, p2, p1, focal, ce, t1, t2, vox):
+        dice, a, b = _dice_algebra(inter, p2, t2, self.dice)
+        elements = float(focal.numel() * vox)
+        value = self.lambda_dice * dice + self.lambda_focal * (focal.sum() / elements)
+        return value, (self.lambda_dice * a, self.lambda_dice * b, None, torch.full_like(focal, self.lambda_focal / elements)), 0.0
+
+
+class FocalLoss(_SigmoidCriterion):
+    """monai 0.6.0 FocalLoss(gamma, reduction mean) (src/definer.py:232-236): the mean over N x K x voxels of
+    exp(gamma logsigmoid(-x (2t - 1))) bce(x, t) on the raw logits -- (1 - p_t)^gamma BCE for a binary target."""
+    terms = SIG_FOCAL
+
+    def __init__(self, include_background=True, to_onehot_y=False, gamma=2.0, weight=None, reduction="mean"):
+        super().__init__()
+        _check_reference_options("FocalLoss", True, False, to_onehot_y, None, reduction)
+        if not include_background or weight is not None:
+            raise NotImplementedError("FocalLoss: include_background=False and class weights are not built (src/definer.py:232-236)")
+        self.gamma = float(gamma)
+
+    def _algebra(self, inter, p2, p1, focal, ce, t1, t2, vox):
+        elements = float(focal.numel() * vox)
+        return focal.sum() / elements, (None, None, None, torch.full_like(focal, 1.0 / elements)), 0.0
+
+
+class TverskyLoss(_SigmoidCriterion):
+    """monai TverskyLoss(sigmoid, alpha, beta, reduction mean) (src/definer.py:237-245): per (sample, class) -- per class with
+    batch=True -- 1 - (tp + smooth_nr) / (tp + alpha fp + beta fn + smooth_dr), tp = sum p t, fp = sum p (1 - t),
+    fn = sum (1 - p) t."""
+
+    def __init__(self, include_background=True, to_onehot_y=False, sigmoid=False, softmax=False, other_act=None, alpha=0.5, beta=0.5,
+                 reduction="mean", smooth_nr=1e-5, smooth_dr=1e-5, batch=False):
+        super().__init__()
+        _check_reference_options("TverskyLoss", sigmoid, softmax, to_onehot_y, other_act, reduction)
+        if not include_background:
+            raise NotImplementedError("TverskyLoss: include_background=False is not built (src/definer.py:237-245)")
+        self.alpha, self.beta, self.smooth_nr, self.smooth_dr, self.batch = float(alpha), float(beta), float(smooth_nr), float(smooth_dr), bool(batch)
+
+    def _algebra(self, inter, p2, p1, focal, ce, t1, t2, vox):
+        n = inter.shape[0]
+        if self.batch:
+            inter, p1, t1 = inter.sum(0, keepdim=True), p1.sum(0, keepdim=True), t1.sum(0, keepdim=True)
+        num = inter + self.smooth_nr
+        den = inter + self.alpha * (p1 - inter) + self.beta * (t1 - inter) + self.smooth_dr
+        f = 1.0 - num / den
+        a = (-1.0 / den + num / den ** 2 * (1.0 - self.alpha - self.beta)) / f.numel()
+        c = num / den ** 2 * self.alpha / f.numel()
+        return f.mean(), (a.expand(n, -1), None, c.expand(n, -1), None), 0.0
 
 
 def deep_supervision_prepared_loss(criterion, outputs, target):

@@ -694,6 +694,33 @@ int brats_softmax_planes(const float* logits, float* out, int N, int K, size_t v
 int brats_argmax_labels(const float* sum, const float* img, uint8_t* labels, int N, int K, int C, size_t voxels,
                         brats_stream_t s);
 
+/* ---- multi-label criteria over sigmoid probabilities (csrc/sigmoid_loss.hip): the per-(sample, class) sums and the gradient
+ * of dice_ce, dice_focal, focal and tversky (src/definer.py:204-245: the reference's DiceCELoss(sigmoid=True) and monai's
+ * DiceFocalLoss, FocalLoss, TverskyLoss).  NCDHW f32 logits and target [N][K][voxels], 1 <= K <= 16; p = sigmoid(x).  `terms`
+ * is 0, BRATS_SIG_FOCAL or BRATS_SIG_CE (both together: BRATS_E_UNSUPPORTED, no criterion of the reference has both): what is
+ * not asked for is neither read nor computed (no class map and no softmax without BRATS_SIG_CE, no logarithm without
+ * BRATS_SIG_FOCAL) and its sums are written as 0; the grad pass does not read its coefficients.  16-byte accesses where
+ * every plane is 16-byte aligned and voxels % 4 == 0, a scalar path otherwise.  ws: f32 workspace of
+ * brats_sigmoid_loss_ws_floats(N, K) elements (per-workgroup partials, added in block order: no float atomics, bit-reproducible).
+ * sigmoid_target_prepare: tsums[n][2k .. 2k+1] = {sum t, sum t^2} over the voxels of plane (n, k); classmap (may be NULL):
+ *   classmap[n][v] = arg-max over k of target[n][k][v], ties to the lowest channel (torch.argmax of DiceCELoss.ce,
+ *   learning/losses.py:571: an all-zero and an all-one voxel are both class 0).
+ * sigmoid_loss_stats: sums[n][4k .. 4k+3] = {sum p t, sum p^2, sum p, F} with F = sum exp(gamma logsigmoid(-x (2t - 1))) bce(x, t)
+ *   (monai 0.6.0 FocalLoss; bce = x - x t + softplus(-x)), sums[n][4K] = CE = sum (logsumexp_k x - x_y), y = classmap.  Every
+ *   exponential has a non-positive argument: logits of +-100 stay finite.  classmap is only ever compared, never an index.
+ * sigmoid_loss_grad: dx = p (1 - p) (A t + 2 B p + C) + Fc dF/dx + c (softmax_k x - [k == y]),
+ *   dF/dx = exp(gamma q) [p - t - gamma bce (2t - 1) sigmoid(x (2t - 1))], q = logsigmoid(-x (2t - 1));
+ *   coef[n][4k .. 4k+3] = {A, B, C, Fc} = dL/d{sum p t, sum p^2, sum p, F}, coef[n][4K] = c = dL/dCE: device memory. */
+#define BRATS_SIG_FOCAL 1
+#define BRATS_SIG_CE 2
+size_t brats_sigmoid_loss_ws_floats(int N, int K);
+int brats_sigmoid_target_prepare(const float* target, float* tsums /*[N][2K]*/, uint8_t* classmap, float* ws, int N, int K,
+                                 size_t voxels, brats_stream_t s);
+int brats_sigmoid_loss_stats(const float* logits, const float* target, const uint8_t* classmap, float* sums /*[N][4K+1]*/,
+                             float* ws, int N, int K, size_t voxels, int terms, float gamma, brats_stream_t s);
+int brats_sigmoid_loss_grad(const float* logits, const float* target, const uint8_t* classmap, const float* coef /*[N][4K+1]*/,
+                            float* dlogits, int N, int K, size_t voxels, int terms, float gamma, brats_stream_t s);
+
 /* ---- CBAM attention block (csrc/cbam.hip): CBAM of the reference's AttEquiUnet (networks/equiunet2020.py:147-235: ChannelGate
  * with the avg + max pools and a shared MLP, SpatialGate = 7x7x7 convolution over [max_c | mean_c] + InstanceNorm3d(1, affine) +
  * ReLU + sigmoid) on NDHWC activations of dtype BRATS_F32 or BRATS_BF16 (BRATS_F16: BRATS_E_UNSUPPORTED), C a multiple of 8 and

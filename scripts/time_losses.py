@@ -12,7 +12,13 @@ training-sized batch [2, 3, 128, 128, 128]: median of `--calls` warm calls of
     the Dice algebra, F.cross_entropy) on the same box, and the statistics and gradient kernels alone against their byte
     bounds (4K + 1 and 8K + 1 bytes per voxel).
 
+  * the multi-label criteria losses.DiceCELoss, DiceFocalLoss, FocalLoss, TverskyLoss (csrc/sigmoid_loss.hip) at
+    [2, K, 128, 128, 128], K = 3 and 16: the target pass, the statistics and gradient passes per term mask against their byte
+    bounds (8K (+ 1) and 12K (+ 1) bytes per voxel), forward + backward of each criterion on one head beside the torch-eager
+    composition of the same loss (tests/_sigmoid_losses_ref.py) on the same box.
+
     python scripts/time_losses.py [--calls 20] [--patch 128] [--json out.json] [--host] [--no-step] [--no-dist] [--no-softmax]
+                                  [--no-sigmoid]
 
 --host, where scipy is importable, also times what the reference does instead on every head (learning/losses.py:153-162):
 device -> host copy, scipy.ndimage.distance_transform_edt per (sample, class), host -> device copy."""
@@ -148,6 +154,58 @@ def softmax_times(dev, patch, calls, res):
         torch.cuda.empty_cache()
 
 
+def sigmoid_times(dev, patch, calls, res):
+    """the four multi-label criteria (csrc/sigmoid_loss.hip) at [2, K, patch^3], K = 3 and 16: the statistics and the gradient pass
+    alone per term mask against 8K (+ 1) and 12K (+ 1) bytes per voxel, the target pass, forward + backward of each criterion on
+    one head, and the plain-torch composition of the same loss (tests/_sigmoid_losses_ref.py) on the same box"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import _sigmoid_losses_ref as ref
+    from brats21_amd import _lib
+    lib = _lib.lib()
+    size = (patch,) * 3
+    n, vox = 2, patch ** 3
+    st = torch.cuda.current_stream().cuda_stream
+    kwargs = dict(include_background=True, sigmoid=True, softmax=False, squared_pred=True, reduction="mean")
+    criteria = {"dice_ce": lambda: losses.DiceCELoss(batch=True, **kwargs), "dice_focal": lambda: losses.DiceFocalLoss(batch=False, **kwargs),
+                "focal": lambda: losses.FocalLoss(gamma=2.0, reduction="mean"),
+                "tversky": lambda: losses.TverskyLoss(include_background=True, sigmoid=True, softmax=False, alpha=0.5, beta=0.5, reduction="mean")}
+    for k in (3, 16):
+        g = torch.Generator(device=dev).manual_seed(k)
+        r = torch.rand((n, 1) + size, device=dev, generator=g)
+        t = (r < torch.arange(1, k + 1, device=dev).view(1, k, 1, 1, 1) / (k + 1.0)).float()  # nested binary channels
+        x = (torch.randn((n, k) + size, device=dev, generator=g) * 3).requires_grad_(True)
+        xd = x.detach()
+        sums, tsums = torch.empty((n, 4 * k + 1), device=dev), torch.empty((n, k, 2), device=dev)
+        ws = torch.empty(lib.brats_sigmoid_loss_ws_floats(n, k), device=dev)
+        ymap = torch.empty((n,) + size, dtype=torch.uint8, device=dev)
+        coef = torch.full((n, 4 * k + 1), 1e-3, device=dev)
+        dx = torch.empty_like(xd)
+        passes = [("target_prepare", 4 * k, lambda: lib.brats_sigmoid_target_prepare(t.data_ptr(), tsums.data_ptr(), None, ws.data_ptr(), n, k, vox, st)),
+                  ("target_prepare_classmap", 4 * k + 1,
+                   lambda: lib.brats_sigmoid_target_prepare(t.data_ptr(), tsums.data_ptr(), ymap.data_ptr(), ws.data_ptr(), n, k, vox, st))]
+        for label, terms in (("dice", 0), ("focal", losses.SIG_FOCAL), ("ce", losses.SIG_CE)):
+            ce = 1 if terms & losses.SIG_CE else 0
+            passes.append((f"stats_{label}", 8 * k + ce, lambda terms=terms: lib.brats_sigmoid_loss_stats(
+                xd.data_ptr(), t.data_ptr(), ymap.data_ptr(), sums.data_ptr(), ws.data_ptr(), n, k, vox, terms, 2.0, st)))
+            passes.append((f"grad_{label}", 12 * k + ce, lambda terms=terms: lib.brats_sigmoid_loss_grad(
+                xd.data_ptr(), t.data_ptr(), ymap.data_ptr(), coef.data_ptr(), dx.data_ptr(), n, k, vox, terms, 2.0, st)))
+        for name, per_voxel, fn in passes:
+            tm = time_calls(fn, calls)
+            tm["bytes"] = per_voxel * n * vox
+            tm["tb_per_s"] = round(tm["bytes"] / (tm["median"] * 1e-3) / 1e12, 3)
+            res[f"sigmoid_{name}_k{k}_ms"] = tm
+
+        def fwd_bwd(loss_fn):
+            x.grad = None
+            loss_fn().backward()
+        for name, make in criteria.items():
+            crit = make()
+            res[f"{name}_k{k}_fwd_bwd_1head_ms"] = time_calls(lambda: fwd_bwd(lambda: crit(x, t)), calls)
+            res[f"{name}_k{k}_torch_eager_fwd_bwd_1head_ms"] = time_calls(lambda: fwd_bwd(lambda: ref.CRITERIA[name](x, t)), calls)
+        del x, xd, dx, t, r
+        torch.cuda.empty_cache()
+
+
 def dist_times(dev, size, a, res):
     t = tumour(2, size, dev)
     heads = [torch.randn((2, 3) + size, device=dev).requires_grad_(True) for _ in range(5)]
@@ -187,6 +245,7 @@ def main():
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--no-dist", action="store_true", help="skip the distance-transform and distance-map criterion legs")
     ap.add_argument("--no-softmax", action="store_true", help="skip the exclusive-class criterion leg")
+    ap.add_argument("--no-sigmoid", action="store_true", help="skip the dice_ce / dice_focal / focal / tversky leg")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     size = (a.patch,) * 3
@@ -195,6 +254,8 @@ def main():
         dist_times(dev, size, a, res)
     if not a.no_softmax:
         softmax_times(dev, a.patch, a.calls, res)
+    if not a.no_sigmoid:
+        sigmoid_times(dev, a.patch, a.calls, res)
     if not a.no_step:
         step_times(dev, a.patch, a.calls, res)
     print(json.dumps(res))
