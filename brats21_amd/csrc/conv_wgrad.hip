@@ -10,6 +10,7 @@
 // and a dY tile are staged once per tile and reused by 27 taps x COF x CIF MFMAs per k-step.
 // Split-K over workgroups writes f32 slabs ws[split][tap][co][ci]; a second kernel reduces them in a
 // fixed order (bitwise reproducible, no float atomics) into torch's [co][ci][tap] layout.
+// The deep levels (many weights, few voxels) have a form without slabs: conv_wgrad_noslab_kernel, below.
 #include <stdlib.h>
 #include "twin_begin.hpp"
 #include "common.hpp"
@@ -718,6 +719,261 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_alltaps2_kernel(const Wgrad
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// No-slab form (deep levels: many weights, few voxels).  The all-taps kernels above give every workgroup its own split-K slab
+// of 27 x 48 x 48 floats (249 KB): at 2 x 16^3 a workgroup walks 4-8 tiles, and a launch writes -- and the reduction reads back --
+// 64 MB of slabs for 6 MB of operands.  Here a workgroup owns a DISJOINT part of dW, 48 co x 16 ci x 27 taps, over the WHOLE
+// reduction: it walks every tile of the batch (grid.x = 1, grid.y = cout / 48, grid.z = cin / 16) and writes its part once,
+// straight into the caller's dw in torch's [co][ci][tap] layout.  No workspace, no second kernel.  All workgroups walk the
+// tiles in the same order: X and dY of the batch (a few MB) are served by L2.
+// Geometry = alltaps2<3, 1> at any layer: 27 (tap, ci-fragment) pairs over 8 MFMA waves (waves 0-2 four, waves 3-7 three), 3 co
+// fragments per pair -- the X fragment is reused 3x as in <3, 3>.  16-channel X rows make the halo tile small enough for
+// DILATION 2 as well (8 x 8 x 20 voxels x 32 B = 41 KB), which the 48-channel rows never were.
+// Loader waves.  A workgroup this small has 69 bytes to load per MFMA (all-taps <3, 3>: 44), and issuing LDS-DMA stalls the
+// issuing wave at the rate of the CU's load path: with the MFMA waves issuing the next tile's loads themselves (the all-taps
+// scheme) a tile took 5.8 k cycles, 3.1 k of MFMA plus 1.8 k of load issue plus barriers.  The accumulators need 48 registers
+// here, not 132, so a THIRD wave per SIMD fits (12 waves, <= 168 registers): waves 8-11 do nothing but fetch tile t + 1 -- X
+// and dY, both by LDS-DMA, into the other of two (X | dY) buffers -- while waves 0-7 run tile t's MFMAs; one barrier per tile.
+// Summation: THE SLAB FORM'S, bit for bit.  The slab plan of the same problem (p.nlane tile ranges x g8 = p.nsplit / p.nlane
+// interleaved sub-groups, see "spatial groups") says which tiles each of its slabs would hold; a workgroup walks the tiles slab
+// after slab (WgNoslabWalk), each slab's tiles in the slab kernels' order and k-step layout into `acc`, and at the end of a slab
+// adds `acc` to `tot` -- what wgrad_reduce_taps_kernel does with the slabs, in slab order.  So dw has the very bits the slab
+// form and its reduction give (a training run does not change when the rule takes this form), and the f32 chains stay as
+// short as a slab's: one chain over all 8192 voxels measured 2.8x the slab forms' error.  Fixed order, no atomics.
+// Epilogue: after the last tile the whole LDS is dead; the 48 x 16 x 27 sums (83 KB) are laid out in it as [co][ci][tap] and
+// every co row -- one contiguous run of 1728 bytes in dw -- goes out with 16-byte stores (4-byte stores when dw, e.g. a
+// slice of a gradient bucket, is not 16-byte aligned).  p.ws = the caller's dw.
+template <int DIL> struct Wg3n {
+  static constexpr int HZ = WG_TZ + 2 * DIL, HY = WG_TY + 2 * DIL, HX = WG_TX + 2 * DIL, HVOX = HZ * HY * HX;  // 6 x 6 x 18 | 8 x 8 x 20
+  static constexpr int COF = 3, CO = 48, CI = 16;
+  static constexpr int SX = 2 * CI, SY = 2 * CO, XPPV = CI / 8, YPPV = CO / 8;
+  static constexpr int MMA_WAVES = 8, LOAD_WAVES = 4, THREADS = 64 * (MMA_WAVES + LOAD_WAVES), LT = 64 * LOAD_WAVES;
+  static constexpr int XPIECES = HVOX * XPPV, YPIECES = WG_VOX * YPPV;   // 1296 | 2560, 1536
+  static constexpr int XI = (XPIECES + LT - 1) / LT, YI = YPIECES / LT;  // 6 | 10, 6 per loader thread
+  static constexpr int XB = XI * LT * 16, YB = YI * LT * 16;             // 24576 | 40960, 24576: whole 1-KB DMA rows per wave
+  static constexpr int BUF = XB + YB;
+  static constexpr int PAIRS = 27, PPW = 4;                              // pair = tap t -> wave t % 8
+  static constexpr int OUT_ROW = CI * 27, OUT_B = CO * OUT_ROW * 4;      // 432 floats per co row, 82944 bytes
+  static constexpr int LDS = 2 * BUF > OUT_B ? 2 * BUF : OUT_B;          // 98304 | 131072
+  static_assert(HZ <= 8 && HY <= 8 && HX <= 32, "packed halo coordinates: 3 + 3 + 5 bits");
+  static_assert(YPIECES % LT == 0, "");
+};
+
+// the tiles in the order of the slab plan: slab `split` = (range split % nlane, sub-group split / nlane) holds the tiles
+// range * tpx + sub-group, + g8, ... of its range, as in the slab kernels.  All scalar.
+struct WgNoslabWalk {
+  int nlane, nsplit, g8, tpx, ntiles;
+  int split, tile, end;
+  DEVI void enter() {  // the first slab from `split` on that has a tile; tile >= end: none is left
+    for (;; ++split) {
+      const int lane8 = split % nlane;
+      tile = lane8 * tpx + split / nlane;
+      end = min(ntiles, (lane8 + 1) * tpx);
+      if (tile < end || split + 1 >= nsplit) return;
+    }
+  }
+  DEVI WgNoslabWalk(const WgradParams& p) : nlane(p.nlane), nsplit(p.nsplit), g8(p.nsplit / p.nlane),
+                                            tpx((p.ntiles + p.nlane - 1) / p.nlane), ntiles(p.ntiles), split(0) { enter(); }
+  DEVI bool done() const { return tile >= end; }
+  DEVI bool next() {  // true: the tile just left was the last of its slab
+    tile += g8;
+    if (tile < end) return false;
+    if (split + 1 < nsplit) { ++split; enter(); }
+    return true;
+  }
+};
+
+template <int DIL>
+__global__ __launch_bounds__(768, 1) void conv_wgrad_noslab_kernel(const WgradParams p) {
+  typedef bf16_t T;
+  using G = Wg3n<DIL>;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int co0 = blockIdx.y * G::CO, ci0 = blockIdx.z * G::CI;
+  f32x4 tot[G::PPW][G::COF];
+#pragma unroll
+  for (int jj = 0; jj < G::PPW; ++jj)
+#pragma unroll
+    for (int m = 0; m < G::COF; ++m) tot[jj][m] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // Both roles walk the same tile sequence and pass the same barriers: one after the first tile has landed, then one per tile.
+  // After the barrier of the t-th tile the buffer (t + 1) & 1 holds the next one (its loader waited for its own pieces first)
+  // and nobody reads buffer t & 1 any more.
+  WgNoslabWalk walk(p);
+  if (wave >= G::MMA_WAVES) {
+    // ---- loader waves: tile t + 1 -> buffer (t + 1) & 1 while the MFMA waves read buffer t & 1 ----
+    const int lt = tid - 64 * G::MMA_WAVES, lw = wave - G::MMA_WAVES;
+    const T* xsrc;
+    int xpitch;
+    if (ci0 < p.c1) { xsrc = (const T*)p.x1 + ci0; xpitch = p.p1; }  // (c1 % 16 == 0: a block never straddles the sources)
+    else { xsrc = (const T*)p.x2 + (ci0 - p.c1); xpitch = p.p2; }
+    const int xpb = xpitch * 2, ypb = p.dyp * 2;
+    // static per-lane piece data, as in the all-taps kernel: byte offset from the halo corner (X) / the tile corner (dY) and
+    // the packed halo coordinates hz | hy << 3 | hx << 6 for the range tests of boundary tiles (flat piece P = lt + 256 i:
+    // the lane-linear image LDS-DMA writes)
+    int xoffs[G::XI], xcode[G::XI], yoffs[G::YI], ycode[G::YI];
+#pragma unroll
+    for (int i = 0; i < G::XI; ++i) {
+      const int P = lt + G::LT * i;
+      const int vox = P / G::XPPV, part = P % G::XPPV;
+      const int hx = vox % G::HX, hy = (vox / G::HX) % G::HY, hz = vox / (G::HX * G::HY);
+      const bool ok = P < G::XPIECES;
+      xoffs[i] = ok ? ((hz * p.H + hy) * p.W + hx) * xpb + part * 16 : (int)0x80000000;
+      xcode[i] = ok ? (hz | hy << 3 | hx << 6 | 1 << 14) : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < G::YI; ++i) {
+      const int P = lt + G::LT * i;
+      const int vox = P / G::YPPV, part = P % G::YPPV;
+      const int z = vox >> 6, y = (vox >> 4) & 3, x = vox & 15;
+      yoffs[i] = ((z * p.H + y) * p.W + x) * ypb + part * 16;
+      ycode[i] = (z + DIL) | (y + DIL) << 3 | (x + DIL) << 6;  // the dY tile = the halo box without its rim
+    }
+    const unsigned xsample_bytes = (unsigned)p.D * p.H * p.W * xpitch * 2;
+    const unsigned ysample_bytes = (unsigned)p.D * p.H * p.W * p.dyp * 2;
+    auto issue_tile = [&](int tile, int buf) {
+      int bt = tile;
+      const int x0 = (bt % p.tx) * WG_TX; bt /= p.tx;
+      const int y0 = (bt % p.ty) * WG_TY; bt /= p.ty;
+      const int z0 = (bt % p.tz) * WG_TZ;
+      const int n = bt / p.tz;
+      const size_t sample_vox = (size_t)n * p.D * p.H * p.W;
+      const rsrc4_t xrs = make_rsrc4(xsrc + sample_vox * xpitch, xsample_bytes);
+      const rsrc4_t yrs = make_rsrc4((const T*)p.dy + sample_vox * p.dyp + co0, ysample_bytes);
+      const int xorg = (((z0 - DIL) * p.H + (y0 - DIL)) * p.W + (x0 - DIL)) * xpb;  // byte offset of the halo corner (negative at the low faces)
+      const int yorg = ((z0 * p.H + y0) * p.W + x0) * ypb;
+      char* const dst = lds + buf * G::BUF + lw * 1024;  // wave-uniform: the DMA adds lane * 16
+      // bit h set <=> 0 <= o - DIL + h < size  <=>  max(0, DIL - o) <= h < min(HN, size - o + DIL)
+      auto inside = [](int o, int size, int hn) {
+        const int lo = o >= DIL ? 0 : DIL - o, hi = size - o + DIL < hn ? size - o + DIL : hn;
+        return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+      };
+      const unsigned zm = inside(z0, p.D, G::HZ), ym = inside(y0, p.H, G::HY), xm = inside(x0, p.W, G::HX);
+      // pieces outside the volume get an out-of-range offset: the DMA writes zeros
+      static_for<0, G::XI>([&](auto i_) {
+        constexpr int i = i_;
+        const int c = xcode[i];
+        const unsigned ok = (unsigned)(c >> 14) & (zm >> (c & 7)) & (ym >> ((c >> 3) & 7)) & (xm >> ((c >> 6) & 31)) & 1u;
+        lds_dma16_async(xrs, dst + i * (G::LT * 16), (xorg + xoffs[i]) | ((int)ok - 1));
+      });
+      static_for<0, G::YI>([&](auto i_) {
+        constexpr int i = i_;
+        const int c = ycode[i];
+        const unsigned ok = (zm >> (c & 7)) & (ym >> ((c >> 3) & 7)) & (xm >> ((c >> 6) & 31)) & 1u;
+        lds_dma16_async(yrs, dst + G::XB + i * (G::LT * 16), (yorg + yoffs[i]) | ((int)ok - 1));
+      });
+    };
+    issue_tile(walk.tile, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int buf = 1; !walk.done(); buf ^= 1) {
+      walk.next();
+      if (!walk.done()) issue_tile(walk.tile, buf);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+  } else {
+    // ---- MFMA waves ----
+    const int q = lane >> 4, v = lane & 15;
+    const bool four = wave + 24 < G::PAIRS;  // scalar: this wave owns a fourth tap
+    int poff[G::PPW];
+#pragma unroll
+    for (int jj = 0; jj < G::PPW; ++jj) {
+      const int t = wave + 8 * jj;
+      poff[jj] = t < G::PAIRS ? ((((t / 9) * G::HY + (t / 3) % 3) * G::HX + t % 3) * DIL) * G::SX : 0;
+    }
+    f32x4 acc[G::PPW][G::COF];
+#pragma unroll
+    for (int jj = 0; jj < G::PPW; ++jj)
+#pragma unroll
+      for (int m = 0; m < G::COF; ++m) acc[jj][m] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int qq = v >> 2, pp = v & 3;
+    const int ybase = (4 * q + qq) * G::SY + pp * 8;
+    const int xbase = (4 * q + qq) * G::SX + pp * 8;
+    __syncthreads();  // tile 0 has landed
+    for (int buf = 0; !walk.done(); buf ^= 1) {
+      const char* ldx = lds + buf * G::BUF;
+      const char* ldy = ldx + G::XB;
+      // k-step s = x-rows 2s, 2s+1 of the tile (row = z*4 + y); see the tap-plane kernel for the fragment layout
+      constexpr int PD = 3;
+      bf16x8 a[2][G::COF], b[PD + 1];
+      auto read_a = [&](auto s_) {
+        constexpr int s = s_;
+        const int yoff = ybase + (32 * s) * G::SY;
+#pragma unroll
+        for (int m = 0; m < G::COF; ++m) a[s & 1][m] = tr_pair(ldy + yoff + m * 32, ldy + yoff + 16 * G::SY + m * 32);
+      };
+      // (waves 3-7 have no fourth tap: they skip that step's B read and MFMAs -- the LDS reads, 1.2 per MFMA here against
+      //  0.85 in the all-taps <3, 3> form, are what a tile's time is made of: 8 waves x 112 reads x 512 B = 3.6 k cycles of the
+      //  CU's LDS against 3.1 k of MFMA)
+      auto read_b = [&](auto u_) {
+        constexpr int u = u_;
+        constexpr int s = u / G::PPW, jj = u % G::PPW;
+        if (jj + 1 < G::PPW || four) {
+          const int xoff = xbase + (((s >> 1) * G::HY + 2 * (s & 1)) * G::HX) * G::SX + poff[jj];
+          b[u % (PD + 1)] = tr_pair(ldx + xoff, ldx + xoff + G::HX * G::SX);
+        }
+      };
+      constexpr int NU = 8 * G::PPW;
+      read_a(std::integral_constant<int, 0>{});
+      static_for<0, PD>([&](auto u_) { read_b(u_); });
+      static_for<0, NU>([&](auto u_) {
+        constexpr int u = u_;
+        constexpr int s = u / G::PPW, jj = u % G::PPW;
+        if constexpr (u + PD < NU) read_b(std::integral_constant<int, u + PD>{});
+        if constexpr (jj == 0 && s + 1 < 8) read_a(std::integral_constant<int, s + 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        if (jj + 1 < G::PPW || four) {
+#pragma unroll
+          for (int m = 0; m < G::COF; ++m)
+            acc[jj][m] = MFMA16_16x16x32(a[s & 1][m], b[u % (PD + 1)], acc[jj][m]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      if (walk.next()) {  // scalar: the end of a slab's tiles
+#pragma unroll
+        for (int jj = 0; jj < G::PPW; ++jj)
+#pragma unroll
+          for (int m = 0; m < G::COF; ++m) { tot[jj][m] += acc[jj][m]; acc[jj][m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      }
+      __syncthreads();  // done reading this buffer; the other one is full
+    }
+  }
+
+  // ---- dw[co][ci][tap]: through LDS, so that every co row leaves as one contiguous run.  Every DMA has landed and every
+  //      operand read is done (the last tile's barrier) ----
+  float* outl = (float*)lds;
+  if (wave < G::MMA_WAVES) {
+    const int q = lane >> 4, v = lane & 15;
+#pragma unroll
+    for (int jj = 0; jj < G::PPW; ++jj) {
+      const int t = wave + 8 * jj;
+      if (t < G::PAIRS) {
+        // C/D layout: lane (q, v) holds rows (co) 4q..4q+3 of column (ci) v
+#pragma unroll
+        for (int m = 0; m < G::COF; ++m)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) outl[(m * 16 + 4 * q + r) * G::OUT_ROW + v * 27 + t] = tot[jj][m][r];
+      }
+    }
+  }
+  __syncthreads();
+  const size_t row_pitch = (size_t)p.cin * 27;
+  float* dst = p.ws + (size_t)co0 * row_pitch + (size_t)ci0 * 27;
+  if (((size_t)p.ws & 15) == 0) {  // (rows start at multiples of 16 * 27 floats from dw)
+    for (int i = tid; i < G::CO * (G::OUT_ROW / 4); i += G::THREADS) {
+      const int row = i / (G::OUT_ROW / 4), c = i % (G::OUT_ROW / 4);
+      *(f32x4*)(dst + row * row_pitch + c * 4) = *(const f32x4*)(outl + row * G::OUT_ROW + c * 4);
+    }
+  } else {
+    for (int i = tid; i < G::CO * G::OUT_ROW; i += G::THREADS) {
+      const int row = i / G::OUT_ROW, c = i % G::OUT_ROW;
+      dst[row * row_pitch + c] = outl[i];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // e4m3 all-taps kernel (BASELINE.json configs[4], model.conv_fp8 = "all"): the weight gradient of the 48 x 48 channel
 // blocks on v_mfma_scale_f32_16x16x128_f8f6f4 (twice the bf16 MFMA rate).  X and dY stay bf16 in HBM; the X halo tile and
 // the dY tile arrive by LDS-DMA in bf16 staging buffers (as X does in the kernel above), and every thread quantises the pieces IT
@@ -1145,11 +1401,44 @@ static int wgrad_alltaps_mode() {
   return g_wgrad_alltaps_mode >= 0 ? g_wgrad_alltaps_mode : env_mode;
 }
 
+int g_wgrad_noslab_mode = -1;  // brats_conv3d_set_wgrad_noslab(): -1 = environment / default (the rule), 0 = never, 1 = wherever it is built
+extern "C" int BRATS_API(brats_conv3d_set_wgrad_noslab)(int mode) {
+  const int old = g_wgrad_noslab_mode;
+  g_wgrad_noslab_mode = mode < 0 ? -1 : (mode ? 1 : 0);
+  return old;
+}
+static int wgrad_noslab_mode() {
+  static int env_mode = -2;
+  if (env_mode < -1) {
+    const char* e = getenv("BRATS_WGRAD_NOSLAB");
+    const int m = e ? atoi(e) : -1;
+    env_mode = m < 0 ? -1 : (m ? 1 : 0);
+  }
+  return g_wgrad_noslab_mode >= 0 ? g_wgrad_noslab_mode : env_mode;
+}
+// The no-slab form is built for 16-bit 3x3x3 problems at dilation 1 | 2 whose channels fill its 48 co x 16 ci blocks.
+static bool wgrad_noslab_built(int dtype, bool shifted, int ksize, int dil, const WgradArgs& a) {
+  return !shifted && ksize == 3 && dtype == BRATS_BF16 && (dil == 1 || dil == 2) && a.cout > 0 && a.cout % 48 == 0 && a.c1 > 0 &&
+         a.c1 % 16 == 0 && a.c2 % 16 == 0 && a.N > 0 && a.D > 0 && a.H > 0 && a.W > 0;
+}
+// The rule (mode -1).  A no-slab workgroup walks ALL tiles of the batch -- about 2 us each, however many workgroups there
+// are -- while a slab workgroup's share shrinks with the split; in exchange it writes 83 KB once where a slab launch writes
+// and reads back nsplit x 27 x cout x cin floats.  It pays for many weights over few voxels (measured on the deep layers at
+// 2 x 16^3 ... 2 x 32^3: DESIGN.md, "No-slab weight gradient"; profiles/wgrad_noslab_layers.txt):
+//  * its blocks of dW fill at least three quarters of the CUs (384 -> 384 and 768 -> 192: 192 blocks, won; 192 -> 384: 96, lost);
+//  * at most 32 tiles at dilation 1 (64: a tie, 128: lost) and 64 at dilation 2, where the slab form is the slower tap-plane
+//    kernel (64: won).
+static bool wgrad_noslab_rule(const WgradArgs& a, int dil, int ntiles) {
+  const int wgs = (a.cout / 48) * (a.cin() / 16);
+  return 4 * wgs >= 3 * device_cus() && ntiles <= (dil == 2 ? 64 : 32);
+}
+
 // every kernel form the host launches, and everything it decides for one problem.  wgrad_plan() and wgrad_f8_plan() are the
 // only places where a form is chosen: the workspace-size functions and the launchers both read the plan.
 enum WgradForm {
   WG_TAP_PLANE, WG_SHIFTED_TAP,                             // conv_wgrad_kernel<T, DIL, cof, cif, KS = 3 | 1>, 16-bit and f32
   WG_ALLTAPS2_33, WG_ALLTAPS2_42, WG_ALLTAPS2_31,           // conv_wgrad_alltaps2_kernel<cof, cif>, 16-bit
+  WG_NOSLAB,                                                // conv_wgrad_noslab_kernel<DIL>, 16-bit: writes dw itself
   WG_ALLTAPS_1, WG_ALLTAPS_1_4,                             // conv_wgrad_alltaps_kernel<1>, <1, 4> (the first layer of a width-64 network: 64 co x 16 ci), 16-bit
   WG_F8_33, WG_F8_42                                        // conv_wgrad_alltaps_f8_kernel<cof, cif>
 };
@@ -1157,7 +1446,8 @@ struct WgradPlan {
   WgradForm form;
   int cof, cif;            // 16-channel fragments per co / ci block
   int cot, cit;            // co / ci blocks = grid.y, grid.z
-  int nlane, g8, nsplit;   // nsplit = nlane * g8 slabs
+  int nlane, g8, nsplit;   // nsplit = nlane * g8 slabs (WG_NOSLAB: nlane, g8 of the slab plan, whose tile order it walks, and
+                           // nsplit = 0 -- no workspace is written and no reduction follows)
   int ntaps, groups;       // grid.x = groups * nsplit (tap-plane: 3 tap planes, shifted-tap: ntaps, all-taps: 1)
   bool clear;              // slab entries of padded ci / co lanes are never written: clear the slabs first
   WgradTileGrid tiles;
@@ -1166,13 +1456,26 @@ struct WgradPlan {
 };
 
 // the plan of one 16-bit / f32 problem: 3x3x3 at dilation 1 | 2 (all-taps where it is built and pays, else tap planes), or
-// with `shifted` the shifted-tap form (1x1x1, and 3x3x3 at any dilation)
-static WgradPlan wgrad_plan(int dtype, bool shifted, int ksize, int dil, const WgradArgs& a) {
+// with `shifted` the shifted-tap form (1x1x1, and 3x3x3 at any dilation).  noslab: the caller can take the no-slab form (a plain
+// 16-bit problem; not the 16-bit passes of a split-precision problem, whose three products meet in the slab reduction, and not
+// the workspace-size functions: they keep reporting the slab plan's bytes, an upper bound of what the no-slab form needs -- none)
+static WgradPlan wgrad_plan(int dtype, bool shifted, int ksize, int dil, const WgradArgs& a, bool noslab = false) {
   WgradPlan pl;
   const int c1 = a.c1, c2 = a.c2, cin = a.cin(), cout = a.cout;
   pl.tiles = wgrad_tile_grid(a);
   pl.ntaps = ksize == 3 ? 27 : 1;
   pl.per = (size_t)pl.ntaps * cout * cin;
+  // (with the all-taps switch at 0 the tap-plane kernel runs everywhere: INTEGRATION.md)
+  if (noslab && wgrad_alltaps_mode() && wgrad_noslab_mode() != 0 && wgrad_noslab_built(dtype, shifted, ksize, dil, a) &&
+      (wgrad_noslab_mode() == 1 || wgrad_noslab_rule(a, dil, pl.tiles.ntiles))) {
+    pl.form = WG_NOSLAB;
+    pl.cof = 3; pl.cif = 1;
+    pl.cot = cout / 48; pl.cit = cin / 16;
+    const WgradPlan slab = wgrad_plan(dtype, shifted, ksize, dil, a);  // whose summation order the kernel keeps
+    pl.nlane = slab.nlane; pl.g8 = slab.g8; pl.nsplit = 0; pl.groups = 1;
+    pl.clear = false;
+    return pl;
+  }
   // all-taps kernels: blocks of 48 co x 48 ci, or 64 co x 32 ci for widths that are multiples of 64 but not of 48 (LDS-DMA
   // form only); the first layer (narrow: one source of <= 16 channels) is one 16-channel ci block
   const bool narrow = c2 == 0 && c1 <= 16;
@@ -1232,17 +1535,18 @@ static int wgrad_dispatch(const WgradParams& p, int cof, int cif, dim3 grid, hip
   BRATS_FAIL(BRATS_E_UNSUPPORTED, "wgrad: unsupported tile %dx%d", cof, cif);
 }
 
-template <auto KERN, int LDS>
+template <auto KERN, int LDS, int THREADS = 512>
 static int wgrad_alltaps_launch(const WgradParams& p, dim3 grid, hipStream_t st) {
   static std::atomic<uint64_t> attr_done{0};
   BRATS_ENSURE_LDS_ATTR(KERN, LDS, attr_done);
-  hipLaunchKernelGGL(KERN, grid, dim3(512), LDS, st, p);
+  hipLaunchKernelGGL(KERN, grid, dim3(THREADS), LDS, st, p);
   BRATS_CHECK_LAUNCH();
   return 0;
 }
 
 // runs the MFMA kernel of one planned problem (16-bit or f32 operands as `dtype` says) into the pl.nsplit slabs at ws
-// ([split][ntaps][cout][cin] f32 each); `room` = the bytes the workspace-size function promises the caller for them
+// ([split][ntaps][cout][cin] f32 each); `room` = the bytes the workspace-size function promises the caller for them.
+// WG_NOSLAB: `ws` is the caller's dw ([cout][cin][27]), written completely; the caller launches no reduction
 static int wgrad_run(const WgradPlan& pl, int dtype, int dil, const WgradArgs& a, float* ws, size_t room, hipStream_t st) {
   const char* who = pl.form == WG_SHIFTED_TAP ? "wgrad_shift" : "wgrad";
   // ci tiles of x2 start at tile index ceil(c1/CI_T): only exact when c1 % CI_T == 0 or c2 == 0
@@ -1256,6 +1560,13 @@ static int wgrad_run(const WgradPlan& pl, int dtype, int dil, const WgradArgs& a
   const dim3 grid(pl.groups * pl.nsplit, pl.cot, pl.cit);  // tap-plane: x = lane + nlane*(3*gsub + tzg)
   const bool bf = dtype == BRATS_BF16;
   switch (pl.form) {
+    case WG_NOSLAB: {  // (ws = the caller's dw)
+      const dim3 g1(1, pl.cot, pl.cit);
+      WgradParams pn = p;
+      pn.nsplit = pl.nlane * pl.g8;  // (the slabs of the slab plan: the kernel's summation groups)
+      return dil == 1 ? wgrad_alltaps_launch<conv_wgrad_noslab_kernel<1>, Wg3n<1>::LDS, Wg3n<1>::THREADS>(pn, g1, st)
+                      : wgrad_alltaps_launch<conv_wgrad_noslab_kernel<2>, Wg3n<2>::LDS, Wg3n<2>::THREADS>(pn, g1, st);
+    }
     case WG_TAP_PLANE:
       if (bf) return dil == 1 ? wgrad_dispatch<bf16_t, 1>(p, pl.cof, pl.cif, grid, st) : wgrad_dispatch<bf16_t, 2>(p, pl.cof, pl.cif, grid, st);
       return dil == 1 ? wgrad_dispatch<float, 1>(p, pl.cof, pl.cif, grid, st) : wgrad_dispatch<float, 2>(p, pl.cof, pl.cif, grid, st);
@@ -1388,6 +1699,12 @@ extern "C" size_t BRATS_API(brats_conv3d_wgrad_shift_ws_bytes)(int dtype, int ks
   return ksize == 1 || ksize == 3 ? wgrad_ws_bytes(dtype, true, ksize, wgrad_shape(N, D, H, W, cin, 0, cout)) : 0;
 }
 
+// 1 = brats_conv3d_wgrad takes the no-slab form for this 3x3x3 problem under the current switches, 0 = a slab form
+extern "C" int BRATS_API(brats_conv3d_wgrad_noslab_taken)(int dtype, int dil, int N, int D, int H, int W, int c1, int c2, int cout) {
+  if (dtype != BRATS_BF16 || c1 <= 0 || cout <= 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+  return wgrad_plan(dtype, false, 3, dil, wgrad_shape(N, D, H, W, c1, c2, cout), true).form == WG_NOSLAB ? 1 : 0;
+}
+
 static int wgrad_impl(bool shifted, WgradArgs a, const float* amax_dy, float* ws, float* dw, float* dbias, int dtype, int ksize, int dil,
                       brats_stream_t s) {
   const char* who = shifted ? "wgrad_shift" : "wgrad";
@@ -1409,9 +1726,10 @@ static int wgrad_impl(bool shifted, WgradArgs a, const float* amax_dy, float* ws
   int rc = x3 && !shifted ? wgrad_x3_fused(a, amax_dy, ws, dw, dil, st) : 1;
   if (rc == 1) {  // (split precision: not a layer of the fused kernel)
     const int dt = x3 ? BRATS_BF16 : dtype;  // the operand type of the kernels
-    const WgradPlan pl = wgrad_plan(dt, shifted, ksize, dil, a);
+    const WgradPlan pl = wgrad_plan(dt, shifted, ksize, dil, a, !x3);
     const size_t room = wgrad_slab_room(dt, shifted, ksize, a);
     if (x3) rc = wgrad_x3(pl, dil, a, amax_dy, ws, dw, room, st);
+    else if (pl.form == WG_NOSLAB) rc = wgrad_run(pl, dtype, dil, a, dw, room, st);
     else if (!(rc = wgrad_run(pl, dtype, dil, a, ws, room, st))) wgrad_reduce_launch((const float*)ws, dw, pl.nsplit, a.cout, a.cin(), pl.ntaps, st);
   }
   if (rc) return rc;

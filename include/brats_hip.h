@@ -208,6 +208,16 @@ size_t brats_conv3d_wgrad_ws_bytes(int dtype, int ksize, int N, int D, int H, in
  * everywhere, -1 = default (1, or the BRATS_WGRAD_ALLTAPS environment variable).  Same values up
  * to f32 summation order; returns the previous setting. */
 int brats_conv3d_set_wgrad_alltaps(int mode);
+/* Tuning / test knob of the no-slab weight gradient (deep levels: a workgroup owns 48 co x 16 ci x 27 taps of dW over the
+ * whole batch and writes them once into dw -- no split-K slabs, no reduction launch; 16-bit 3x3x3 problems at dilation 1 | 2
+ * with cout % 48 == 0 and c1, c2 % 16 == 0): 1 = wherever it is built, 0 = never, -1 = default (the rule: enough channel
+ * blocks for a quarter of the CUs and few tiles; or the BRATS_WGRAD_NOSLAB environment variable).  With the all-taps switch
+ * at 0 it is never taken.  Where the slab form's reduction is the all-taps one (cout * cin >= 32768: every problem the rule
+ * takes) dw has the slab form's bits: the kernel keeps its summation order.  Returns the previous setting.  The workspace-size
+ * functions do not depend on it: they report the slab plan's bytes, of which this form uses none. */
+int brats_conv3d_set_wgrad_noslab(int mode);
+/* 1 = brats_conv3d_wgrad takes the no-slab form for this 3x3x3 problem under the current switches, 0 = a slab form */
+int brats_conv3d_wgrad_noslab_taken(int dtype, int dil, int N, int D, int H, int W, int c1, int c2, int cout);
 /* Tuning / test knob of the split-precision weight gradient (brats_conv3d_x3_wgrad): 1 = the fused kernel (f32 tiles staged
  * once, split into fp16 / bf16 pairs on their way into LDS, three MFMA products per staged tile: csrc/conv_wgrad_x3.hpp) for
  * dilation-1 layers with 48-channel blocks that have enough tiles, 2 = the fused kernel for ANY tile count (tests), 0 = the
