@@ -340,6 +340,159 @@ extern "C" int BRATS_API(brats_affine_act_fwd)(const void* y, int ypitch, const 
   return 0;
 }
 
+// ---- s = add + act(y*scale + shift) ------------------------------------------------------------
+// The recurrent block of R2U-Net (networks/unet_family.py:60-101) feeds `x + previous result` to its next convolution and
+// ends in a residual: the sum is written by the normalise pass itself -- three tensors move where affine_act + an
+// elementwise add move five.  The activation is rounded to T first (what affine_act would have stored), added to `add` in
+// f32 and rounded once: bit-identical to brats_affine_act_fwd followed by an add of the two stored tensors.  Same walk as
+// affine_act_kernel: a thread owns one 16-byte channel vector, two voxels (four loads) in flight.
+template <typename T, bool HEAVY, bool NT = false>
+__global__ void __launch_bounds__(256) affine_act_add_kernel(const T* __restrict__ y, int ypitch, const float* __restrict__ scale_shift,
+                                                             const T* __restrict__ add, int addpitch, T* __restrict__ s, int spitch,
+                                                             int act, SlopeArg sl, int voxels, int C) {
+  constexpr int VW = 16 / sizeof(T);
+  const float slope = sl.p ? *sl.p : sl.v;
+  const int n = blockIdx.y;
+  const int cv = C / VW;
+  const int vl_n = blockDim.x / cv;  // voxel lanes per block
+  const int mycv = threadIdx.x % cv, myvl = threadIdx.x / cv;
+  const bool live = myvl < vl_n;
+  const int c0 = mycv * VW;
+  float sc[VW], sh[VW];
+#pragma unroll
+  for (int j = 0; j < VW; ++j) {
+    sc[j] = scale_shift[((size_t)n * C + c0 + j) * 2];
+    sh[j] = scale_shift[((size_t)n * C + c0 + j) * 2 + 1];
+  }
+  const T* yb = y + (size_t)n * voxels * ypitch + c0;
+  const T* ab = add + (size_t)n * voxels * addpitch + c0;
+  T* sb = s + (size_t)n * voxels * spitch + c0;
+  const int stride = gridDim.x * vl_n;
+  auto run = [&](auto relu_) {
+    constexpr bool RELU = decltype(relu_)::value;
+    auto body = [&](float* a, const float* r) {
+#pragma unroll
+      for (int j = 0; j < VW; ++j) {
+        const float t = a[j] * sc[j] + sh[j];
+        float z;
+        if constexpr (RELU) z = __builtin_fmaxf(t, 0.f);
+        else z = act_fwd<HEAVY>(t, act, slope);
+        a[j] = to_f<T>(from_f<T>(z)) + r[j];  // the activation as affine_act stores it, then one f32 add
+      }
+    };
+    int vox = live ? blockIdx.x * vl_n + myvl : voxels;
+    for (; vox + stride < voxels; vox += 2 * stride) {
+      float a0[VW], a1[VW], r0[VW], r1[VW];
+      vload<T, VW, NT>(yb + (size_t)vox * ypitch, a0);
+      vload<T, VW, NT>(ab + (size_t)vox * addpitch, r0);
+      vload<T, VW, NT>(yb + (size_t)(vox + stride) * ypitch, a1);
+      vload<T, VW, NT>(ab + (size_t)(vox + stride) * addpitch, r1);
+      body(a0, r0);
+      body(a1, r1);
+      vstore<T, VW, NT>(sb + (size_t)vox * spitch, a0);
+      vstore<T, VW, NT>(sb + (size_t)(vox + stride) * spitch, a1);
+    }
+    if (vox < voxels) {
+      float a0[VW], r0[VW];
+      vload<T, VW, NT>(yb + (size_t)vox * ypitch, a0);
+      vload<T, VW, NT>(ab + (size_t)vox * addpitch, r0);
+      body(a0, r0);
+      vstore<T, VW, NT>(sb + (size_t)vox * spitch, a0);
+    }
+  };
+  if (!HEAVY && act == BRATS_ACT_RELU) run(std::true_type{});
+  else run(std::false_type{});
+}
+
+extern "C" int BRATS_API(brats_affine_act_add_fwd)(const void* y, int ypitch, const float* scale_shift, const void* add, int addpitch,
+                                                   void* s, int spitch, int dtype, int act, float slope_value, const float* slope_dev,
+                                                   int N, int voxels, int C, brats_stream_t st) {
+  const SlopeArg slope{slope_value, slope_dev};
+  const int vw = vec_width(dtype);
+  if (!y || !add || !s || !scale_shift) BRATS_FAIL(BRATS_E_ARG, "affine_act_add_fwd: null pointer");
+  if (N <= 0 || voxels <= 0 || C <= 0 || C % vw || ypitch % vw || addpitch % vw || spitch % vw || C / vw > 256 || ypitch < C ||
+      addpitch < C || spitch < C)
+    BRATS_FAIL(BRATS_E_ARG, "affine_act_add_fwd: C and pitches must be multiples of %d (C <= %d, pitch >= C)", vw, 256 * vw);
+  const bool big = big_tensor(dtype, (size_t)N * voxels * C);
+  dim3 grid(voxel_walk(vw, voxels, C).grid(big ? 8192 : 2048), N);
+  with_act_stream(dtype, act > BRATS_ACT_LEAKY, big, [&](auto t, auto heavy, auto nt) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((affine_act_add_kernel<T, decltype(heavy)::value, decltype(nt)::value>), grid, dim3(256), 0, (hipStream_t)st,
+                       (const T*)y, ypitch, scale_shift, (const T*)add, addpitch, (T*)s, spitch, act, slope, voxels, C);
+  });
+  BRATS_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- dst = src0 + src1 (+ src2 (+ src3)) -------------------------------------------------------
+// The gradient of a tensor with several readers (the input of a RecurrentBlock, read by each of its t + 1 applications;
+// x0 of the block, read by the first RecurrentBlock and the residual): f32 accumulation in argument order, one rounding,
+// one launch -- nsrc + 1 tensors move where chained adds move 3 (nsrc - 1).  No atomics, no workspace.
+struct GradSrcs { const void* p[4]; int pitch[4]; };
+template <typename T, int NS, bool NT = false>
+__global__ void __launch_bounds__(256) grad_sum_kernel(GradSrcs srcs, T* __restrict__ dst, int dpitch, int voxels, int C) {
+  constexpr int VW = 16 / sizeof(T);
+  const int n = blockIdx.y;
+  const int cv = C / VW;
+  const int vl_n = blockDim.x / cv;
+  const int mycv = threadIdx.x % cv, myvl = threadIdx.x / cv;
+  const bool live = myvl < vl_n;
+  const int c0 = mycv * VW;
+  const T* sb[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) sb[i] = (const T*)srcs.p[i] + (size_t)n * voxels * srcs.pitch[i] + c0;
+  T* db = dst + (size_t)n * voxels * dpitch + c0;
+  const int stride = gridDim.x * vl_n;
+  auto step = [&](int v0, auto cnt) {  // NV voxels (NV x NS loads of 16 bytes) in flight per thread
+    constexpr int NV = decltype(cnt)::value;
+    float a[NV][NS][VW];
+#pragma unroll
+    for (int q = 0; q < NV; ++q)
+#pragma unroll
+      for (int i = 0; i < NS; ++i) vload<T, VW, NT>(sb[i] + (size_t)(v0 + q * stride) * srcs.pitch[i], a[q][i]);
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+#pragma unroll
+      for (int i = 1; i < NS; ++i)
+#pragma unroll
+        for (int j = 0; j < VW; ++j) a[q][0][j] += a[q][i][j];
+      vstore<T, VW, NT>(db + (size_t)(v0 + q * stride) * dpitch, a[q][0]);
+    }
+  };
+  int vox = live ? blockIdx.x * vl_n + myvl : voxels;
+  for (; vox + stride < voxels; vox += 2 * stride) step(vox, std::integral_constant<int, 2>{});
+  if (vox < voxels) step(vox, std::integral_constant<int, 1>{});
+}
+
+extern "C" int BRATS_API(brats_grad_sum)(const void* src0, int pitch0, const void* src1, int pitch1, const void* src2, int pitch2,
+                                         const void* src3, int pitch3, int nsrc, void* dst, int dpitch, int dtype, int N, int voxels,
+                                         int C, brats_stream_t st) {
+  const int vw = vec_width(dtype);
+  if (nsrc < 2 || nsrc > 4) BRATS_FAIL(BRATS_E_ARG, "grad_sum: nsrc = %d (2 .. 4 sources)", nsrc);
+  GradSrcs g{{src0, src1, src2, src3}, {pitch0, pitch1, pitch2, pitch3}};
+  if (!dst) BRATS_FAIL(BRATS_E_ARG, "grad_sum: null pointer");
+  for (int i = 0; i < nsrc; ++i) {
+    if (!g.p[i]) BRATS_FAIL(BRATS_E_ARG, "grad_sum: null pointer (source %d of %d)", i, nsrc);
+    if (g.pitch[i] % vw || g.pitch[i] < C) BRATS_FAIL(BRATS_E_ARG, "grad_sum: pitch %d of source %d must be a multiple of %d and >= C", g.pitch[i], i, vw);
+  }
+  if (N <= 0 || voxels <= 0 || C <= 0 || C % vw || dpitch % vw || dpitch < C || C / vw > 256)
+    BRATS_FAIL(BRATS_E_ARG, "grad_sum: C and pitches must be multiples of %d (C <= %d, pitch >= C)", vw, 256 * vw);
+  const bool big = big_tensor(dtype, (size_t)N * voxels * C);
+  dim3 grid(voxel_walk(vw, voxels, C).grid(big ? 8192 : 2048), N);
+  with_stream(dtype, big, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    constexpr bool NT = decltype(nt)::value;
+    auto go = [&](auto ns) {
+      hipLaunchKernelGGL((grad_sum_kernel<T, decltype(ns)::value, NT>), grid, dim3(256), 0, (hipStream_t)st, g, (T*)dst, dpitch, voxels, C);
+    };
+    if (nsrc == 2) go(std::integral_constant<int, 2>{});
+    else if (nsrc == 3) go(std::integral_constant<int, 3>{});
+    else go(std::integral_constant<int, 4>{});
+  });
+  BRATS_CHECK_LAUNCH();
+  return 0;
+}
+
 // 16 bytes of a tensor kept as loaded (4 registers) until the arithmetic wants the 8 (4) floats: the head-fold passes hold four
 // voxels per thread in flight, unpacked up front they cost 32 registers and an occupancy step
 template <typename T> struct Raw16;

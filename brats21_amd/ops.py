@@ -747,6 +747,52 @@ def affine_act(y, scale_shift, act="relu", out=None, slope=0.01, amax=None, slop
     return out
 
 
+def affine_act_add(y, scale_shift, add, act="relu", out=None, slope=0.01, slope_t=None):
+    """out = add + act(y * scale + shift) in one pass (include/brats_hip.h: brats_affine_act_add_fwd): bit-identical to
+    affine_act(y, ...) followed by an elementwise add of the two stored tensors.  add / out may be channel-slice views; out must
+    not overlap y or add."""
+    ptr, c, p = _desc(y)
+    aptr, ac, ap = _desc(add)
+    n, d, h, w, _ = y.shape
+    if add.shape != y.shape or add.dtype != y.dtype:
+        raise _lib.BratsHipError("affine_act_add: add must have y's shape and dtype")
+    if out is None:
+        out = new_act(n, d, h, w, c, y.dtype, y.device)
+    optr, oc, op = _desc(out)
+    if out.shape != y.shape or out.dtype != y.dtype:
+        raise _lib.BratsHipError("affine_act_add: bad output tensor")
+    _lib.check(_lib.lib().brats_affine_act_add_fwd(ptr, p, scale_shift.data_ptr(), aptr, ap, optr, op, _code(y.dtype), ACTS[act], slope,
+                                                   _f32(slope_t), n, d * h * w, c, _stream()), "affine_act_add_fwd")
+    return out
+
+
+def grad_sum(*srcs, out=None):
+    """out = srcs[0] + srcs[1] (+ srcs[2] (+ srcs[3])) on NDHWC tensors (or channel-slice views) of one shape and storage type:
+    f32 accumulation in argument order, one rounding, one launch (include/brats_hip.h: brats_grad_sum) -- the gradient of a
+    tensor with several readers.  More than four sources: further launches that take the running sum as their first source.
+    Small f32 tensors (weight gradients) go through a [1, 1, 1, rows, C] view.  out must not overlap a source."""
+    if len(srcs) < 2:
+        raise _lib.BratsHipError("grad_sum: at least two sources")
+    first = srcs[0]
+    if any(s.shape != first.shape or s.dtype != first.dtype for s in srcs[1:]):
+        raise _lib.BratsHipError("grad_sum: the sources must have one shape and dtype")
+    if len(srcs) > 4:
+        return grad_sum(grad_sum(*srcs[:4]), *srcs[4:], out=out)
+    n, d, h, w, c = first.shape
+    if out is None:
+        out = new_act(n, d, h, w, c, first.dtype, first.device)
+    optr, oc, op = _desc(out)
+    if out.shape != first.shape or out.dtype != first.dtype:
+        raise _lib.BratsHipError("grad_sum: bad output tensor")
+    args = []
+    for s in srcs:
+        ptr, _, p = _desc(s)
+        args += [ptr, p]
+    args += [None, 0] * (4 - len(srcs))
+    _lib.check(_lib.lib().brats_grad_sum(*args, len(srcs), optr, op, _code(first.dtype), n, d * h * w, c, _stream()), "grad_sum")
+    return out
+
+
 def dropout(x, p, state, unit, out=None):
     """nn.Dropout(p) on an NDHWC activation (or, with the same arguments, on the gradient flowing back through it): x * keep /
     (1 - p) with keep a pure function of (state[0] = seed, state[1] = step counter, unit id, element index) -- brats_dropout.
@@ -785,23 +831,27 @@ def affine_act_pool(y, scale_shift, act="relu", slope=0.01, amax=None, slope_t=N
     return z, pooled
 
 
-def _gn_bwd_bufs(y):
+def _gn_bwd_bufs(y, dy=None):
     """(dy like y, reduction workspace, dgamma [C], dbeta [C]) of the GroupNorm + activation backward entry points."""
     n, c = y.shape[0], y.shape[-1]
     red = torch.empty(_lib.lib().brats_gn_bwd_ws_floats(n, c), dtype=torch.float32, device=y.device)
     dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
     dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
-    return torch.empty(y.shape, dtype=y.dtype, device=y.device), red, dgamma, dbeta
+    return (torch.empty(y.shape, dtype=y.dtype, device=y.device) if dy is None else dy), red, dgamma, dbeta
 
 
-def gn_act_bwd(dz, y, scale_shift, mean_rstd, gamma, groups=8, act="relu", slope=0.01, amax=None, slope_t=None):
-    """Returns (dy, dgamma, dbeta) for z = act(GroupNorm(y)); amax (optional, zero-initialised) receives max|dy|."""
+def gn_act_bwd(dz, y, scale_shift, mean_rstd, gamma, groups=8, act="relu", slope=0.01, amax=None, slope_t=None, out=None):
+    """Returns (dy, dgamma, dbeta) for z = act(GroupNorm(y)); amax (optional, zero-initialised) receives max|dy|.
+    out: the tensor dy is written to (e.g. a slice of a stacked buffer) instead of a fresh one."""
     dzp, c, dzpitch = _desc(dz)
     yp, _, ypitch = _desc(y)
     n, d, h, w, _ = y.shape
-    dy, red, dgamma, dbeta = _gn_bwd_bufs(y)
+    dy, red, dgamma, dbeta = _gn_bwd_bufs(y, out)
+    dyp, dyc, dypitch = _desc(dy)
+    if dy.shape != y.shape or dy.dtype != y.dtype:
+        raise _lib.BratsHipError("gn_act_bwd: bad output tensor")
     _lib.check(_lib.lib().brats_gn_act_bwd(dzp, dzpitch, yp, ypitch, scale_shift.data_ptr(), mean_rstd.data_ptr(),
-                                           _f32(gamma), dy.data_ptr(), c, red.data_ptr(), dgamma.data_ptr(),
+                                           _f32(gamma), dyp, dypitch, red.data_ptr(), dgamma.data_ptr(),
                                            dbeta.data_ptr(), _code(y.dtype), ACTS[act], slope, _f32(slope_t), n, d * h * w, c,
                                            groups, _f32(amax), _stream()), "gn_act_bwd")
     return dy, dgamma, dbeta
@@ -1739,6 +1789,144 @@ def cbam_bwd(dout, x, saved, w1, b1, w2, b2, wc, gamma, beta, d_pooled=None):
                                                 beta.data_ptr(), dcomp.data_ptr(), sv.cidx.data_ptr(), dpool.data_ptr(), sv.argvox.data_ptr(),
                                                 dxp, dxpitch, code, n, c, d, h, w, st), apply)
     return dx, dw1, db1_, dw2, db2_, dwc, dgamma, dbeta
+
+
+# ------------------------------------------------------------------------------------------ recurrent residual block (R2U-Net)
+class RrcnnSaved:
+    """What rrcnn_fwd keeps for rrcnn_bwd.  Of tensor size: per RecurrentBlock the stacked unit inputs S and raw convolution outputs
+    Y, [(t + 1) N, D, H, W, C] each, and the block input(s) x (x2)."""
+    __slots__ = ("x", "x2", "S", "Y", "ss", "mr", "groups", "act", "t", "n")
+
+
+def _rrcnn_params(params):
+    ps = [p.detach() for p in params]
+    if len(ps) != 10:
+        raise _lib.BratsHipError("rrcnn: ten parameters in the block's state-dict order (RCNN.0.conv.0.weight .. Conv_1x1.bias)")
+    c = ps[8].shape[0]
+    ok = (ps[8].dim() == 5 and tuple(ps[8].shape[2:]) == (1, 1, 1) and ps[9].numel() == c
+          and all(tuple(ps[i].shape) == (c, c, 3, 3, 3) for i in (0, 4)) and all(ps[i].numel() == c for i in (1, 2, 3, 5, 6, 7)))
+    if not ok:
+        raise _lib.BratsHipError("rrcnn: parameter shapes do not belong to one RRCNNblock")
+    for p in ps:
+        _f32(p.contiguous())
+    return [p.contiguous() for p in ps], c, ps[8].shape[1]
+
+
+def rrcnn_fwd(x, x2, params, groups=8, act="relu", t=2, save=True):
+    """RRCNNblock (networks/unet_family.py:60-101 of the reference) on NDHWC tensors: x0 = conv1x1([x | x2]) + bias, two
+    RecurrentBlocks -- ONE conv3x3x3 (bias) -> norm -> act unit applied t + 1 times, to xb and then to xb + previous result --,
+    out = x0 + result.  -> (out, saved).  params: the block's ten parameters in state-dict order; groups: 8 (GroupNorm) or C
+    (InstanceNorm); x2 (or None): the second source of the 1x1x1 convolution (the virtual concat [x | x2]); x may carry zero
+    channels beyond the weight's (a narrow input padded to a channel vector).
+    Per application: convolution (+ tile statistics), finalize, and ONE normalise pass that writes the next unit input xb + z
+    directly (affine_act_add) -- the plain affine_act only for the first block's result; the last pass of the second block adds
+    x0 and writes the output.  save=True: the producers write into slices of the stacked buffers S (unit inputs: x0 is S_A[0:N],
+    the first block's result S_B[0:N]) and Y (raw convolution outputs) that rrcnn_bwd reads.  save=False: nothing is kept,
+    four activation buffers are reused throughout, saved is None."""
+    if x3_active():
+        raise NotImplementedError("rrcnn_fwd: the split-precision modes are not built for the recurrent block")
+    ps, c, cin = _rrcnn_params(params)
+    if t < 1:
+        raise _lib.BratsHipError(f"rrcnn_fwd: t = {t} (t >= 1)")
+    n, d, h, w, c1 = x.shape
+    c2 = x2.shape[-1] if x2 is not None else 0
+    if (x2 is not None and (c1 + c2 != cin or x2.dtype != x.dtype or x2.shape[:4] != x.shape[:4])) or (x2 is None and c1 < cin):
+        raise _lib.BratsHipError(f"rrcnn_fwd: the block is built for {cin} input channels, the tensors have {c1} + {c2}")
+    if c % groups:
+        raise _lib.BratsHipError(f"rrcnn_fwd: {c} channels in {groups} groups")
+    dtype, dev, vox = x.dtype, x.device, d * h * w
+    sv = RrcnnSaved()
+    sv.x, sv.x2, sv.groups, sv.act, sv.t, sv.n = x, x2, groups, act, t, n
+    sv.S, sv.Y, sv.ss, sv.mr = [], [], [[], []], [[], []]
+    if save:
+        for _ in range(4):
+            (sv.S if len(sv.S) < 2 else sv.Y).append(new_act((t + 1) * n, d, h, w, c, dtype, dev))
+        x0 = sv.S[0][:n]
+    else:
+        x0 = new_act(n, d, h, w, c, dtype, dev)
+        ybuf, ping = new_act(n, d, h, w, c, dtype, dev), [new_act(n, d, h, w, c, dtype, dev) for _ in range(2)]
+    # (the parameter objects themselves go to pack_weights: its no_grad cache is keyed by them)
+    wpk = pack_weights(params[8], dtype, PACK_FWD, cin_pad=c1 + c2, c1=c1 if x2 is not None else None)
+    conv3d(x, wpk, c, 1, 1, bias=ps[9], out=x0, x2=x2)
+    xb = x0
+    for b in (0, 1):
+        _, bias, gamma, beta = ps[4 * b:4 * b + 4]
+        wpk = pack_weights(params[4 * b], dtype, PACK_FWD)
+        cur = xb
+        for k in range(t + 1):
+            yk = sv.Y[b][k * n:(k + 1) * n] if save else ybuf
+            _, stats = conv3d(cur, wpk, c, 3, 1, bias=bias, out=yk, want_stats=True)
+            mean_rstd, scale_shift = gn_finalize(stats, n, c, groups, vox, gamma, beta)
+            if save:
+                sv.ss[b].append(scale_shift)
+                sv.mr[b].append(mean_rstd)
+            if k < t:
+                # the next unit input xb + z.  (save=False: block b's unit inputs live in ping[b]; the convolution that read the
+                # previous one has run, so the pass may overwrite it -- it is neither its y nor its add)
+                nxt = sv.S[b][(k + 1) * n:(k + 2) * n] if save else ping[b]
+                cur = affine_act_add(yk, scale_shift, xb, act, out=nxt)
+            elif b == 0:
+                # the first block's result has no sum in front of it.  (save=False: it takes over ping[0], which the second block
+                # only reads)
+                xb = affine_act(yk, scale_shift, act, out=sv.S[1][:n] if save else ping[0])
+            else:
+                out = affine_act_add(yk, scale_shift, x0, act, out=None if save else ping[1])
+    return out, (sv if save else None)
+
+
+def rrcnn_bwd(dout, saved, params, need_dx=True):
+    """Backward of rrcnn_fwd: -> (dx, dx2, grads) with grads the ten parameter gradients in state-dict order, each produced exactly
+    once as the finished sum over the t + 1 applications of its unit.  Per RecurrentBlock, from the last application down:
+    dy_k = gn_act_bwd(dz_k) written into slice k of a stacked DY, ds_k = dgrad(dy_k) = dz_{k-1}; the gradient of the block input
+    is ONE grad_sum over ds_0 .. ds_t (+ dout for x0: the residual); the weight gradient is ONE conv3d_wgrad launch over the
+    stacked batch (t + 1) N of (S, DY) -- the sum over applications is the kernel's own reduction over the batch --, the bias
+    gradient one channel_dot over DY, dgamma / dbeta the sum of the t + 1 [C] vectors.  need_dx=False: dx (dx2) are None."""
+    sv = saved
+    if not isinstance(sv, RrcnnSaved):
+        raise _lib.BratsHipError("rrcnn_bwd: saved must come from rrcnn_fwd(save=True)")
+    if x3_active():
+        raise NotImplementedError("rrcnn_bwd: the split-precision modes are not built for the recurrent block")
+    ps, c, cin = _rrcnn_params(params)
+    n, t, x, x2 = sv.n, sv.t, sv.x, sv.x2
+    dtype = x.dtype
+    if dout.dtype != dtype or tuple(dout.shape) != tuple(sv.S[0][:n].shape):
+        raise _lib.BratsHipError("rrcnn_bwd: dout must have the output's shape and the block's storage type")
+    grads = [None] * 10
+    dz = dout
+    for b in (1, 0):
+        gamma = ps[4 * b + 2]
+        S, Y = sv.S[b], sv.Y[b]
+        DY = torch.empty_like(Y)
+        wpk = pack_weights(params[4 * b], dtype, PACK_DGRAD)
+        ds, small = [None] * (t + 1), []
+        for k in range(t, -1, -1):
+            sl = slice(k * n, (k + 1) * n)
+            _, dgamma, dbeta = gn_act_bwd(dz, Y[sl], sv.ss[b][k], sv.mr[b][k], gamma, sv.groups, sv.act, out=DY[sl])
+            small.append((dgamma, dbeta))
+            ds[k], _ = conv3d(DY[sl], wpk, c, 3, 1)
+            dz = ds[k]
+        dz = grad_sum(*(ds + ([dout] if b == 0 else [])))  # every reader of the block input in one pass
+        grads[4 * b], _ = conv3d_wgrad(S, DY, 3, 1)
+        grads[4 * b + 1] = channel_dot(DY).sum(0)
+        gb = torch.stack([g for g, _ in small] + [g for _, g in small]).view(2, t + 1, c).sum(1)  # [C]-sized: dgamma | dbeta
+        grads[4 * b + 2], grads[4 * b + 3] = gb[0], gb[1]
+    d_x0 = dz
+    c1 = x.shape[-1]
+    dws = [conv3d_wgrad_shift(s, d_x0, 1)[0] for s in ((x,) if x2 is None else (x, x2))]
+    dw1 = dws[0] if x2 is None else torch.cat(dws, 1)  # (weight-sized)
+    grads[8] = dw1[:, :cin].contiguous() if dw1.shape[1] != cin else dw1
+    grads[9] = channel_dot(d_x0).sum(0)
+    if not need_dx:
+        return None, None, grads
+    wpk = pack_weights(params[8], dtype, PACK_DGRAD, cin_pad=c1 if x2 is None else None)
+    if x2 is None:
+        dx, _ = conv3d(d_x0, wpk, c1, 1, 1)
+        return dx, None, grads
+    if c1 % split_granule(cin) == 0:
+        (dx, dx2), _ = conv3d(d_x0, wpk, cin, 1, 1, split=c1)  # two dense tensors, one launch
+        return dx, dx2, grads
+    dx, _ = conv3d(d_x0, wpk, cin, 1, 1)
+    return dx[..., :c1], dx[..., c1:], grads
 
 
 # ------------------------------------------------------------------------------------------ box calibration

@@ -56,7 +56,7 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk; brats_staple_blocks / _pack /
  * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd; brats_softmax_stats / _grad / _planes + the workspace
  * query, brats_label_stats + its workspace query, brats_argmax_labels; the brats_cbam_* passes; brats_cbam_apply_pool, brats_cbam_bwd_reduce_pool / _bwd_apply_pool;
- * brats_upsample_nearest_fwd / _bwd, brats_planes_nearest_fwd / _bwd): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * brats_upsample_nearest_fwd / _bwd, brats_planes_nearest_fwd / _bwd; brats_affine_act_add_fwd, brats_grad_sum): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
  * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
@@ -278,6 +278,18 @@ int brats_gn_finalize(const float* stats, int tiles_per_sample, int N, int C, in
 int brats_affine_act_fwd(const void* y, int ypitch, const float* scale_shift, void* z, int zpitch,
                          int dtype, int act, float slope, const float* slope_dev, int N, int voxels, int C, float* amax,
                          brats_stream_t s);
+/* s = add + act(y*scale + shift): the normalise pass of a recurrent unit (RecurrentBlock, networks/unet_family.py:60-86, whose
+ * next convolution reads x + previous result) and of the block's residual.  Bit-identical to brats_affine_act_fwd followed by an
+ * elementwise add of the two STORED tensors: the activation is rounded to the storage type, added to `add` in f32 and rounded once.
+ * All activations of brats_affine_act_fwd; `add` and `s` may be channel slices (pitch > C); `s` must not overlap `y` or `add`. */
+int brats_affine_act_add_fwd(const void* y, int ypitch, const float* scale_shift, const void* add, int addpitch, void* s,
+                             int spitch, int dtype, int act, float slope, const float* slope_dev, int N, int voxels, int C,
+                             brats_stream_t stream);
+/* dst = src0 + src1 (+ src2 (+ src3)), nsrc = 2 .. 4 (the unused sources are ignored and may be NULL): the gradient of a tensor with
+ * several readers.  f32 accumulation in argument order, rounded once to the storage type; no atomics, no workspace; dst must not
+ * overlap a source.  Viewed as N = 1, voxels = rows, dtype = BRATS_F32 it adds small f32 tensors (weight gradients). */
+int brats_grad_sum(const void* src0, int pitch0, const void* src1, int pitch1, const void* src2, int pitch2, const void* src3,
+                   int pitch3, int nsrc, void* dst, int dpitch, int dtype, int N, int voxels, int C, brats_stream_t stream);
 /* The same pass for a layer that ends an encoder level (ConvBnRelu -> MaxPool3d(2, 2), equiunet2020.py:469-475): writes z
  * AND its 2x2x2 max pool (with_avg: MaxAvgPool's [max | mean], 2C channels) -- z is not read back by a pooling kernel.
  * Bit-identical to brats_affine_act_fwd + brats_maxpool2_fwd; relu / leakyrelu; amax receives max|z|. */
