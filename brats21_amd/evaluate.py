@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._tensors import _vec
 from .inferers import GraphedPredictor, _first, sliding_window_inference
 from .transforms import convert_to_multichannel
 
@@ -96,7 +97,8 @@ def finalize_segmentation(prob_sum, passes=1, img=None, thresh=0.5, want_labels=
             raise ValueError(f"image {tuple(im.shape)} does not match predictions {tuple(p.shape)}")
     seg = torch.empty_like(p)
     labels = torch.empty((n, 1) + tuple(p.shape[2:]), dtype=torch.uint8, device=p.device) if want_labels else None
-    _lib.check(_lib.lib().brats_post_threshold(p.data_ptr(), im.data_ptr() if im is not None else None, seg.data_ptr(),
+    _lib.check(_lib.lib().brats_post_threshold(p.data_ptr(), _vec(im, None, "finalize_segmentation: image", p, null=True),
+                                               seg.data_ptr(),
                                                labels.data_ptr() if labels is not None else None, n, k,
                                                im.shape[1] if im is not None else 0, vox, 1.0 / passes, float(thresh),
                                                _stream()), "post_threshold")
@@ -121,7 +123,8 @@ def overlap_counts(pred, target):
         raise ValueError(f"prediction {tuple(p.shape)} and target {tuple(t.shape)} differ")
     n, k = p.shape[:2]
     counts = torch.empty((n, k, 3), dtype=torch.int64, device=p.device)
-    _lib.check(_lib.lib().brats_overlap_counts(p.data_ptr(), t.data_ptr(), counts.data_ptr(), n * k, p[0, 0].numel(),
+    _lib.check(_lib.lib().brats_overlap_counts(p.data_ptr(), _vec(t, p.numel(), "overlap_counts: target", p), counts.data_ptr(),
+                                               n * k, p[0, 0].numel(),
                                                _stream()), "overlap_counts")
     return counts
 

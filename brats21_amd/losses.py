@@ -13,6 +13,8 @@ from collections.abc import Sequence
 import torch
 import torch.nn as nn
 
+from ._tensors import _vec
+
 
 class DiceLoss(nn.Module):
     def __init__(self, jaccard=False, smooth_nr=1e-5, smooth_dr=1e-5):
@@ -85,6 +87,8 @@ class _FusedDiceFn(torch.autograd.Function):
             ctx.save_for_backward(t, coef, *heads)
             return loss
         hs = [h.contiguous().float() for h in heads]
+        for h in hs:  # (the fused path compared every head with the target above; this one indexes them by the target's sizes too)
+            _vec(h, t.numel(), "fused Dice: head", t)
         sums = torch.empty((len(hs), k, 3), dtype=torch.float32, device=t.device)
         ws = torch.empty(lib.brats_dice_ws_floats(n, k), dtype=torch.float32, device=t.device)  # per-block partials
         for i, h in enumerate(hs):
@@ -197,7 +201,9 @@ class _HausdorffFn(torch.autograd.Function):
         total = x.numel()
         s = torch.empty(1, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.brats_hd_loss_stats(x.data_ptr(), t.data_ptr(), tdm.data_ptr(), pdm.data_ptr(), alpha, s.data_ptr(),
+            _lib.check(lib.brats_hd_loss_stats(_vec(x, None, "HausdorffLoss: logits", None), _vec(t, total, "HausdorffLoss: target", x),
+                                               _vec(tdm, total, "HausdorffLoss: target field", x),
+                                               _vec(pdm, total, "HausdorffLoss: predicted field", x), alpha, s.data_ptr(),
                                                _loss_ws(lib, x.device).data_ptr(), total,
                                                torch.cuda.current_stream().cuda_stream), "hd_loss_stats")
         ctx.save_for_backward(x, t, tdm, pdm)
@@ -229,7 +235,9 @@ class _BoundaryFn(torch.autograd.Function):
         total = x.numel()
         s = torch.empty(1, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.brats_boundary_loss_stats(x.data_ptr(), dist.data_ptr(), s.data_ptr(), _loss_ws(lib, x.device).data_ptr(),
+            _lib.check(lib.brats_boundary_loss_stats(_vec(x, None, "BoundaryLoss: logits", None),
+                                                     _vec(dist, total, "BoundaryLoss: distance map", x), s.data_ptr(),
+                                                     _loss_ws(lib, x.device).data_ptr(),
                                                      total, torch.cuda.current_stream().cuda_stream), "boundary_loss_stats")
         ctx.save_for_backward(x, dist)
         return s[0] / total
@@ -259,6 +267,8 @@ class _DiceFn(torch.autograd.Function):
         x = logits.contiguous().float()
         n, k = x.shape[:2]
         vox = x[0, 0].numel()
+        _vec(x, None, "Dice: logits", None)
+        _vec(t, x.numel(), "Dice: target", x)
         groups = [(x, t, n)] if batch else [(x[i], t[i], 1) for i in range(n)]
         sums = torch.empty((len(groups), k, 3), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
@@ -487,7 +497,8 @@ class _SoftmaxDiceCEFn(torch.autograd.Function):
         sums = torch.empty((n, 3 * k + 1), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             ws = torch.empty(lib.brats_softmax_ws_floats(n, k), dtype=torch.float32, device=x.device)
-            _lib.check(lib.brats_softmax_stats(x.data_ptr(), y.data_ptr(), sums.data_ptr(), ws.data_ptr(), n, k, vox,
+            _lib.check(lib.brats_softmax_stats(x.data_ptr(), _vec(y, n * vox, "SoftmaxDiceCELoss: labels", x, torch.uint8),
+                                               sums.data_ptr(), ws.data_ptr(), n, k, vox,
                                                torch.cuda.current_stream().cuda_stream), "softmax_stats")
         s = sums[:, :3 * k].reshape(n, k, 3)
         if opt.batch:  # the batch dimension is reduced too: one Dice value per class
@@ -596,7 +607,8 @@ class _SigmoidLossFn(torch.autograd.Function):
         sums = torch.empty((n, 4 * k + 1), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             ws = torch.empty(lib.brats_sigmoid_loss_ws_floats(n, k), dtype=torch.float32, device=x.device)
-            _lib.check(lib.brats_sigmoid_loss_stats(x.data_ptr(), prep.t.data_ptr(), classmap.data_ptr() if classmap is not None else None,
+            _lib.check(lib.brats_sigmoid_loss_stats(x.data_ptr(), _vec(prep.t, x.numel(), "criterion: target", x),
+                                                    _vec(classmap, n * vox, "criterion: class map", x, torch.uint8, null=True),
                                                     sums.data_ptr(), ws.data_ptr(), n, k, vox, crit.terms, crit.gamma,
                                                     torch.cuda.current_stream().cuda_stream), "sigmoid_loss_stats")
         inter, p2, p1, focal = sums[:, :4 * k].reshape(n, k, 4).unbind(-1)

@@ -64,8 +64,8 @@ _CONFUSION_OTHER = {
 def _pair(y_pred, y, what):
     _need_cuda(y_pred, what)
     _need_cuda(y, what)
-    if y_pred.shape != y.shape:
-        raise ValueError(f"y_pred {tuple(y_pred.shape)} and y {tuple(y.shape)} differ")
+    if y_pred.shape != y.shape or y_pred.device != y.device:
+        raise ValueError(f"y_pred {tuple(y_pred.shape)} on {y_pred.device} and y {tuple(y.shape)} on {y.device} differ")
     if y_pred.dim() != 5:
         raise ValueError(f"expected [N, K, D, H, W] masks, got {tuple(y_pred.shape)}")
     return y_pred.contiguous().float(), y.contiguous().float()

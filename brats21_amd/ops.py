@@ -14,6 +14,9 @@ import torch
 from . import _lib
 from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, BF16, F16, F32, PACK_DGRAD, PACK_FWD, X3_BF16, X3_F16  # noqa: F401
 
+from ._tensors import (X3B, X3F, _NO_ACT, _SIZES, _act, _act2, _code, _conv_packed, _desc, _desc2, _even, _f32, _finalize_in,  # noqa: F401
+                       _groups, _head_weight, _out, _packed, _planes, _tile_stats, _vec)
+
 ACTS = {"none": ACT_NONE, "relu": ACT_RELU, "leakyrelu": ACT_LEAKY, "elu": _lib.ACT_ELU, "swish": _lib.ACT_SWISH,
         "mish": _lib.ACT_MISH}
 
@@ -81,8 +84,6 @@ def _stream():
 
 
 # ---- split precision ("x3"): f32 tensors, 3x3x3 convolutions on three 16-bit MFMA products (csrc/conv_igemm_x3.hpp) ----
-X3F = "x3_f16"    # operands split into fp16 pairs: f32-class products inside fp16's range (the forward pass)
-X3B = "x3_bf16"   # ... into bf16 pairs: 2^-16 per product over f32's whole range (the gradients)
 _X3 = None        # the split the 3x3x3 convolutions of f32 tensors use inside a split_precision() block; None = exact f32
 
 
@@ -116,20 +117,6 @@ def _conv_dtype(dtype, ksize):
     return dtype
 
 
-def _code(dtype):
-    if dtype == X3F:
-        return X3_F16
-    if dtype == X3B:
-        return X3_BF16
-    if dtype == torch.bfloat16:
-        return BF16
-    if dtype == torch.float32:
-        return F32
-    if dtype == torch.float16:
-        return F16
-    raise _lib.BratsHipError(f"unsupported activation dtype {dtype}")
-
-
 def is16(dtype):
     """16-bit storage (bf16 or fp16): the MFMA kernels with f32 accumulation; fp16 is the reference's autocast dtype."""
     return dtype in (torch.bfloat16, torch.float16)
@@ -140,30 +127,6 @@ def _fn16(name, dtype):
     return getattr(_lib.lib(), name + ("_f16" if dtype == torch.float16 else ""))
 
 
-def _desc(t):
-    """(data_ptr, C, pitch) of an NDHWC tensor or channel-slice view."""
-    if t.dim() != 5 or not t.is_cuda:
-        raise _lib.BratsHipError("expected a CUDA tensor of shape [N, D, H, W, C]")
-    n, d, h, w, c = t.shape
-    p = t.stride(3)
-    if t.stride(4) != 1 or t.stride(2) != w * p or t.stride(1) != h * w * p or t.stride(0) != d * h * w * p:
-        raise _lib.BratsHipError(f"tensor is not NDHWC with a channel pitch: shape {tuple(t.shape)} strides {t.stride()}")
-    return t.data_ptr(), c, p
-
-
-def _desc2(t):
-    """_desc of an optional second source (the virtual concat [x | x2]); (None, 0, 0) without one."""
-    return _desc(t) if t is not None else (None, 0, 0)
-
-
-def _f32(t):
-    if t is None:
-        return None
-    if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
-        raise _lib.BratsHipError("expected a contiguous CUDA float32 tensor")
-    return t.data_ptr()
-
-
 def new_act(n, d, h, w, c, dtype, device):
     return torch.empty((n, d, h, w, c), dtype=dtype, device=device)
 
@@ -171,9 +134,13 @@ def new_act(n, d, h, w, c, dtype, device):
 # ------------------------------------------------------------------------------------------ layout
 def ncdhw_to_ndhwc(x, dtype, cpad=None):
     """[N,C,D,H,W] f32 -> [N,D,H,W,cpad] dtype (extra channels zero)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 5 or not x.is_cuda:
+        raise _lib.BratsHipError("ncdhw_to_ndhwc: expected a CUDA tensor of shape [N, C, D, H, W]")
+    x = x.contiguous().float()  # (any dtype: images arrive as integers too)
     n, c, d, h, w = x.shape
     cpad = cpad or c
-    x = x.contiguous().float()
+    if cpad < c:
+        raise _lib.BratsHipError(f"ncdhw_to_ndhwc: cpad = {cpad} is below the tensor's {c} channels")
     out = new_act(n, d, h, w, cpad, dtype, x.device)
     _lib.check(_lib.lib().brats_ncdhw_to_ndhwc(x.data_ptr(), out.data_ptr(), _code(dtype), n, c, cpad, cpad, d, h, w,
                                                _stream()), "ncdhw_to_ndhwc")
@@ -181,10 +148,9 @@ def ncdhw_to_ndhwc(x, dtype, cpad=None):
 
 
 def ndhwc_to_ncdhw(x):
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
-    out = torch.empty((n, c, d, h, w), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().brats_ndhwc_to_ncdhw(ptr, p, out.data_ptr(), _code(x.dtype), n, c, d, h, w, _stream()),
+    a = _act(x, "ndhwc_to_ncdhw: x")
+    out = torch.empty((a.n, a.c, a.d, a.h, a.w), dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().brats_ndhwc_to_ncdhw(a.ptr, a.pitch, out.data_ptr(), a.code, a.n, a.c, a.d, a.h, a.w, _stream()),
                "ndhwc_to_ncdhw")
     return out
 
@@ -257,8 +223,21 @@ def _pack_geometry(w, mode, cin_pad=None, cin_off=0, cin_cnt=None, c1=None):
     return cin_w, cnt, kdim, rows, ((kdim, 0) if (c1 is None or mode != PACK_FWD) else (c1, kdim - c1))
 
 
+def _on(t, device):
+    """Is the tensor t on the CUDA device `device` (a torch.device or string; without an index: any CUDA device)?"""
+    d = torch.device(device)
+    return t.is_cuda and d.type == "cuda" and d.index in (None, t.device.index)
+
+
+def _weight(w):
+    if not isinstance(w, torch.Tensor) or w.dim() != 5 or not w.is_cuda or not w.is_floating_point():
+        raise _lib.BratsHipError("pack_weights: expected a floating-point CUDA tensor [Cout, Cin, k, k, k]")
+
+
 def _padded(w, cin_w):
-    """w detached, contiguous f32, its input channels zero-padded to cin_w."""
+    """w (checked: a floating-point CUDA tensor [Cout, Cin, k, k, k]) detached, contiguous f32, its input channels zero-padded
+    to cin_w."""
+    _weight(w)
     w = w.detach()
     if cin_w != w.shape[1]:
         wp = torch.zeros((w.shape[0], cin_w) + tuple(w.shape[2:]), dtype=torch.float32, device=w.device)
@@ -297,13 +276,13 @@ class PackPlan:
         jobs, blocks, entries, off = {False: [], True: []}, {False: [], True: []}, {}, 0
         for key, (wref, (dtype, mode, cin_pad, cin_off, cin_cnt, dil, c1)) in self.recorded.items():
             w = wref()
-            if w is None or w.dtype != torch.float32 or not w.is_contiguous():
-                continue
+            if w is None or w.dtype != torch.float32 or not w.is_contiguous() or not _on(w, device):
+                continue  # (pack_weights finds no entry for it and takes the per-layer path, which checks it)
             cin_real, k = w.shape[1], w.shape[2]
             cin_w, _, kdim, rows, src = _pack_geometry(w, mode, cin_pad, cin_off, cin_cnt, c1)
             ck = conv_chunk(dtype, k, dil, *src, rows)
             code = _code(dtype)
-            nbytes = _lib.lib().brats_conv3d_packed_bytes(code, k, kdim, rows, ck)
+            nbytes = _SIZES[("conv", code, k, dil, *src, rows)] = _lib.lib().brats_conv3d_packed_bytes(code, k, kdim, rows, ck)
             rows16 = (rows + 15) // 16
             x3 = code in (X3_BF16, X3_F16)  # (hi and lo fragments side by side)
             ms_n = nbytes // ((kdim // ck) * rows16 * (2048 if x3 else 1024))
@@ -411,7 +390,7 @@ def _pack_weights(w, dtype, mode, cin_pad, cin_off, cin_cnt, dil, c1):
     w = _padded(w, cin_w)
     code = _code(dtype)
     ck = conv_chunk(dtype, k, dil, *src, rows)
-    nbytes = _lib.lib().brats_conv3d_packed_bytes(code, k, kdim, rows, ck)
+    nbytes = _SIZES[("conv", code, k, dil, *src, rows)] = _lib.lib().brats_conv3d_packed_bytes(code, k, kdim, rows, ck)
     packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
     _lib.check(_lib.lib().brats_conv3d_pack_weights(w.data_ptr(), packed.data_ptr(), code, mode, k, cout_w, cin_w,
                                                     cin_off, cin_cnt, ck, _stream()), "conv3d_pack_weights")
@@ -429,6 +408,7 @@ def set_vs8(mode):
     the packed-weight layout of the layers it applies to).  Returns the previous setting."""
     old = _lib.lib().brats_conv3d_set_vs8(mode)
     invalidate_packed_weights()
+    _SIZES.clear()
     for plan in list(_PLANS.values()):
         plan.dirty = True
         plan.entries = None
@@ -467,24 +447,20 @@ def conv_pre_ok(dtype, ksize, dil, c1, c2, cout):
     return is16(dtype) and bool(_lib.lib().brats_conv3d_pre_ok(_code(dtype), ksize, dil, c1, c2, cout))
 
 
-def _conv_outputs(x, cout, out, split, want_stats, what):
-    """What a convolution of x writes: -> (y, stats | None, args).  y = `out` (checked), a fresh [N, D, H, W, cout] tensor, or --
-    split -- the pair of dense tensors with the output channels [0, split) and [split, cout); stats = [N, tiles, cout, 2];
+def _conv_outputs(a, cout, out, split, want_stats, what):
+    """What a convolution of the activation a writes: -> (y, stats | None, args).  y = `out` (checked), a fresh [N, D, H, W, cout]
+    tensor, or -- split -- the pair of dense tensors with the output channels [0, split) and [split, cout); stats = [N, tiles, cout, 2];
     args = (y, pitch, y2, c2, split, stats) as the entry points take them."""
-    n, d, h, w, _ = x.shape
-    y2 = None
+    lead, y2 = a.shape[:4], None
     if split is not None:
-        out = new_act(n, d, h, w, split, x.dtype, x.device)
-        y2 = new_act(n, d, h, w, cout - split, x.dtype, x.device)
-    elif out is None:
-        out = new_act(n, d, h, w, cout, x.dtype, x.device)
-    optr, oc, op = _desc(out)
-    if (y2 is None and oc != cout) or out.dtype != x.dtype:
-        raise _lib.BratsHipError(f"{what}: bad output tensor")
-    stats = torch.empty((n, tiles_per_sample(d, h, w), cout, 2), dtype=torch.float32, device=x.device) if want_stats else None
-    args = (optr, op, y2.data_ptr() if y2 is not None else None, (cout - split) if y2 is not None else 0, split or 0,
+        if out is not None or not 0 < split < cout:
+            raise _lib.BratsHipError(f"{what}: split = {split} of {cout} channels (no out= with it)")
+        y2 = torch.empty(lead + (cout - split,), dtype=a.dtype, device=a.device)
+    o = _out(out, lead + (split or cout,), a, (what, "out"))
+    stats = torch.empty((a.n, tiles_per_sample(a.d, a.h, a.w), cout, 2), dtype=torch.float32, device=a.device) if want_stats else None
+    args = (o.ptr, o.pitch, y2.data_ptr() if y2 is not None else None, (cout - split) if y2 is not None else 0, split or 0,
             stats.data_ptr() if stats is not None else None)
-    return ((out, y2) if y2 is not None else out), stats, args
+    return ((o.t, y2) if y2 is not None else o.t), stats, args
 
 
 def conv3d(x, packed_w, cout, ksize=3, dil=1, bias=None, out=None, want_stats=False, x2=None, split=None, amax=None):
@@ -497,21 +473,25 @@ def _conv3d_pre(x, packed_w, cout, ksize, dil, bias, out, want_stats, x2):
     """conv3d whose input(s) are Pending activations: normalise + act applied while the halo tile is staged."""
     p1 = x if isinstance(x, Pending) else None
     p2 = x2 if isinstance(x2, Pending) else None
-    xa = p1.y if p1 is not None else x
-    xb = p2.y if p2 is not None else x2
     if p1 is not None and p2 is not None and (p1.act != p2.act or p1.slope != p2.slope):
         raise _lib.BratsHipError("conv3d: the two pending inputs carry different activations")
     act, slope = (p1 or p2).act, (p1 or p2).slope
-    ptr, c, p = _desc(xa)
-    n, d, h, w, _ = xa.shape
-    ptr2, c2, pp2 = _desc2(xb)
-    out, stats, (optr, op, _, _, _, sptr) = _conv_outputs(xa, cout, out, None, want_stats, "conv3d")
-    with _span("conv_igemm", c + c2, cout, ksize, dil, n, d, h, w, str(xa.dtype)):
-        _lib.check(_lib.lib().brats_conv3d_fwd_pre(ptr, c, p, p1.scale_shift.data_ptr() if p1 is not None else None, ptr2, c2, pp2,
-                                                   p2.scale_shift.data_ptr() if p2 is not None else None, ACTS[act], float(slope),
-                                                   packed_w.data_ptr(), _f32(bias), optr, op, sptr, _code(xa.dtype), dil, n, d, h, w,
-                                                   cout, _stream()), "conv3d_fwd_pre")
+    a, b = _conv_sources(p1.y if p1 is not None else x, p2.y if p2 is not None else x2, "conv3d")
+    ss1 = _vec(p1.scale_shift, a.n * a.c * 2, "conv3d: x.scale_shift", a) if p1 is not None else None
+    ss2 = _vec(p2.scale_shift, a.n * b.c * 2, "conv3d: x2.scale_shift", a) if p2 is not None else None
+    wp = _conv_packed(packed_w, a.code, ksize, dil, a.c, b.c, cout, "conv3d", a)
+    out, stats, (optr, op, _, _, _, sptr) = _conv_outputs(a, cout, out, None, want_stats, "conv3d")
+    with _span("conv_igemm", a.c + b.c, cout, ksize, dil, a.n, a.d, a.h, a.w, str(a.dtype)):
+        _lib.check(_lib.lib().brats_conv3d_fwd_pre(a.ptr, a.c, a.pitch, ss1, b.ptr, b.c, b.pitch, ss2, ACTS[act], float(slope), wp,
+                                                   _vec(bias, cout, "conv3d: bias", a, null=True), optr, op, sptr, a.code, dil, a.n,
+                                                   a.d, a.h, a.w, cout, _stream()), "conv3d_fwd_pre")
     return out, stats
+
+
+def _conv_sources(x, x2, what):
+    """The checked input [x | x2] of a convolution: -> (_Act of x, _Act of x2 or _NO_ACT)."""
+    a = _act(x, (what, "x"))
+    return a, _act2(x2, (what, "x2"), a, anyc=True)
 
 
 def _conv3d(x, packed_w, cout, ksize=3, dil=1, bias=None, out=None, want_stats=False, x2=None, split=None, amax=None):
@@ -521,18 +501,19 @@ def _conv3d(x, packed_w, cout, ksize=3, dil=1, bias=None, out=None, want_stats=F
     [0, split) and [split, cout) to two dense tensors (returns (y, y2) as y).
     amax (split precision only): 1-element f32 device tensor holding max|x| -- the input is scaled into fp16's range by the
     matching power of two and the result scaled back (brats_conv3d_x3_fwd: the input gradient, whose x = dY is tiny)."""
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
-    ptr2, c2, p2 = _desc2(x2)
-    y, stats, oargs = _conv_outputs(x, cout, out, split, want_stats, "conv3d")
-    kd = _conv_dtype(x.dtype, ksize)  # (split precision: f32 tensors, weights packed under the same mode)
-    with _span("conv_igemm", c + c2, cout, ksize, dil, n, d, h, w, str(kd)):
+    a, b = _conv_sources(x, x2, "conv3d")
+    kd = _conv_dtype(a.dtype, ksize)  # (split precision: f32 tensors, weights packed under the same mode)
+    code = _code(kd)
+    wp = _conv_packed(packed_w, code, ksize, dil, a.c, b.c, cout, "conv3d", a)
+    bp = _vec(bias, cout, "conv3d: bias", a, null=True)
+    y, stats, oargs = _conv_outputs(a, cout, out, split, want_stats, "conv3d")
+    with _span("conv_igemm", a.c + b.c, cout, ksize, dil, a.n, a.d, a.h, a.w, str(kd)):
         if amax is not None and kd in (X3F, X3B):
-            _lib.check(_lib.lib().brats_conv3d_x3_fwd(ptr, c, p, ptr2, c2, p2, _f32(amax), packed_w.data_ptr(), _f32(bias), *oargs,
-                                                      _code(kd), dil, n, d, h, w, cout, _stream()), "conv3d_x3_fwd")
+            _lib.check(_lib.lib().brats_conv3d_x3_fwd(a.ptr, a.c, a.pitch, b.ptr, b.c, b.pitch, _vec(amax, 1, "conv3d: amax", a), wp, bp,
+                                                      *oargs, code, dil, a.n, a.d, a.h, a.w, cout, _stream()), "conv3d_x3_fwd")
         else:
-            _lib.check(_lib.lib().brats_conv3d_fwd(ptr, c, p, ptr2, c2, p2, packed_w.data_ptr(), _f32(bias), *oargs, _code(kd),
-                                                   ksize, dil, n, d, h, w, cout, _stream()), "conv3d_fwd")
+            _lib.check(_lib.lib().brats_conv3d_fwd(a.ptr, a.c, a.pitch, b.ptr, b.c, b.pitch, wp, bp, *oargs, code, ksize, dil, a.n, a.d,
+                                                   a.h, a.w, cout, _stream()), "conv3d_fwd")
     return y, stats
 
 
@@ -541,7 +522,8 @@ def pack_weights_narrow(w, mode):
     """w: torch-layout [Cout, Cin, 3, 3, 3] f32 -> the f32 buffer conv3d_narrow() reads.  PACK_FWD: Cout <= 16 class rows over Cin
     channels; PACK_DGRAD: Cin <= 16 class rows over Cout channels, transposed with the taps flipped (the input gradient as a
     convolution of dy).  The channel count must be a multiple of 8.  Cached under no_grad like pack_weights()."""
-    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3):
+    _weight(w)
+    if tuple(w.shape[2:]) != (3, 3, 3):
         raise _lib.BratsHipError(f"pack_weights_narrow: expected [Cout, Cin, 3, 3, 3], got {tuple(w.shape)}")
     cout_w, cin_w = w.shape[0], w.shape[1]
     c, k = (cin_w, cout_w) if mode == PACK_FWD else (cout_w, cin_w)
@@ -567,28 +549,28 @@ def conv3d_narrow(x, packed_w, k, bias=None, add=None):
     """NCDHW f32 [N, k, D, H, W] = add + bias + conv3x3x3(x) (zero padding, dilation 1) of an NDHWC tensor or channel slice x
     (bf16, fp16 or f32; C a multiple of 8) with weights from pack_weights_narrow(); k <= 16.  bias [k] and add [N, k, D, H, W]
     (f32, never rounded) are optional.  One pass: x is read once per output tile, the result leaves as f32 planes."""
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
+    a = _act(x, "conv3d_narrow: x")
+    n, d, h, w, c = a.shape
+    # (the size query is made per call, as it always was: exact equality, not a lower bound, tells a foreign buffer)
     if packed_w.numel() * 4 != _lib.lib().brats_conv3d_narrow_packed_bytes(c, k):
         raise _lib.BratsHipError(f"conv3d_narrow: the packed weights do not belong to a {c} -> {k} layer")
     if add is not None and tuple(add.shape) != (n, k, d, h, w):
         raise _lib.BratsHipError(f"conv3d_narrow: add has shape {tuple(add.shape)}, expected {(n, k, d, h, w)}")
-    if bias is not None and bias.numel() != k:
-        raise _lib.BratsHipError(f"conv3d_narrow: bias has {bias.numel()} elements, expected {k}")
-    out = torch.empty((n, k, d, h, w), dtype=torch.float32, device=x.device)
-    with _span("conv_narrow", c, k, n, d, h, w, str(x.dtype)):
-        _lib.check(_lib.lib().brats_conv3d_narrow_fwd(ptr, c, p, packed_w.data_ptr(), _f32(bias), _f32(add), out.data_ptr(),
-                                                      _code(x.dtype), k, n, d, h, w, _stream()), "conv3d_narrow_fwd")
+    wp = _vec(packed_w, None, "conv3d_narrow: packed_w", a)
+    out = torch.empty((n, k, d, h, w), dtype=torch.float32, device=a.device)
+    with _span("conv_narrow", c, k, n, d, h, w, str(a.dtype)):
+        _lib.check(_lib.lib().brats_conv3d_narrow_fwd(a.ptr, c, a.pitch, wp, _vec(bias, k, "conv3d_narrow: bias", a, null=True),
+                                                      _vec(add, None, "conv3d_narrow: add", a, null=True), out.data_ptr(), a.code, k,
+                                                      n, d, h, w, _stream()), "conv3d_narrow_fwd")
     return out
 
 
 # ------------------------------------------------------------------------------------------ fp8 conv
 def absmax(x):
     """max|x| of an NDHWC tensor as a 1-element f32 device tensor (no host sync)."""
-    ptr, c, p = _desc(x)
-    out = torch.empty(1, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().brats_absmax(ptr, p, _code(x.dtype), x.shape[0] * x.shape[1] * x.shape[2] * x.shape[3], c,
-                                       out.data_ptr(), _stream()), "absmax")
+    a = _act(x, "absmax: x")
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().brats_absmax(a.ptr, a.pitch, a.code, a.n * a.vox, a.c, out.data_ptr(), _stream()), "absmax")
     return out
 
 
@@ -625,7 +607,7 @@ def pack_weights_f8(w, mode, cin_pad=None, cin_off=0, cin_cnt=None, c1=None):
     ck = conv_f8_chunk(*src)
     if ck <= 0:
         raise _lib.BratsHipError(f"pack_weights_f8: K channels {kdim} (c1={c1}) are not multiples of 16")
-    nbytes = _lib.lib().brats_conv3d_f8_packed_bytes(kdim, rows, ck)
+    nbytes = _SIZES[("f8", *src, rows)] = _lib.lib().brats_conv3d_f8_packed_bytes(kdim, rows, ck)
     packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
     _lib.check(_lib.lib().brats_conv3d_f8_pack_weights(w.data_ptr(), packed.data_ptr(), mode, cout_w, cin_w, cin_off,
                                                        cin_cnt, ck, _stream()), "conv3d_f8_pack_weights")
@@ -641,9 +623,7 @@ def conv3d_f8(x, packed_w, cout, dil=1, bias=None, out=None, want_stats=False, x
     unless a static power-of-two ``xscale`` is given."""
     if not is16(x.dtype):
         raise _lib.BratsHipError("conv3d_f8: bf16 activations only")
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
-    ptr2, c2, p2 = _desc2(x2)
+    a, b = _conv_sources(x, x2, "conv3d_f8")
     if xscale is None:
         if amax is None:
             amax = absmax(x)
@@ -651,47 +631,55 @@ def conv3d_f8(x, packed_w, cout, dil=1, bias=None, out=None, want_stats=False, x
             amax2 = absmax(x2)
     else:
         amax = amax2 = None
-    y, stats, oargs = _conv_outputs(x, cout, out, split, want_stats, "conv3d_f8")
-    with _span("conv_igemm_f8", c + c2, cout, 3, dil, n, d, h, w, "e4m3"):
-        _lib.check(_fn16("brats_conv3d_f8_fwd", x.dtype)(ptr, c, p, _f32(amax), ptr2, c2, p2, _f32(amax2),
-                                                  float(xscale) if xscale is not None else 0.0, packed_w.data_ptr(),
-                                                  _f32(bias), *oargs, dil, n, d, h, w, cout, _stream()), "conv3d_f8_fwd")
+    wp = _packed(packed_w, ("f8", a.c, b.c, cout), lambda: _lib.lib().brats_conv3d_f8_packed_bytes(
+        a.c + b.c, cout, max(1, conv_f8_chunk(a.c, b.c))), "conv3d_f8", a)
+    y, stats, oargs = _conv_outputs(a, cout, out, split, want_stats, "conv3d_f8")
+    with _span("conv_igemm_f8", a.c + b.c, cout, 3, dil, a.n, a.d, a.h, a.w, "e4m3"):
+        _lib.check(_fn16("brats_conv3d_f8_fwd", a.dtype)(a.ptr, a.c, a.pitch, _vec(amax, 1, "conv3d_f8: amax", a, null=True), b.ptr, b.c,
+                                                  b.pitch, _vec(amax2, 1, "conv3d_f8: amax2", a, null=True),
+                                                  float(xscale) if xscale is not None else 0.0, wp,
+                                                  _vec(bias, cout, "conv3d_f8: bias", a, null=True), *oargs, dil, a.n, a.d, a.h, a.w,
+                                                  cout, _stream()), "conv3d_f8_fwd")
     return y, stats
 
 
 def _grad_out(out, shape, device):
     """The f32 tensor a gradient kernel writes: `out` (e.g. the parameter's slice of a DDP bucket, ddp.GradientBuckets.dest)
     when it is given and fits, otherwise a fresh allocation."""
-    if out is not None and out.numel() == int(np.prod(shape)) and out.dtype == torch.float32 and out.is_contiguous():
+    if (out is not None and out.numel() == int(np.prod(shape)) and out.dtype == torch.float32 and out.is_contiguous()
+            and out.device == device):
         return out.view(shape)
     return torch.empty(shape, dtype=torch.float32, device=device)
+
+
+def _wgrad_operands(x, dy, x2, what):
+    """The checked operands of a weight gradient: the layer input [x | x2] and the output gradient dy, of x's extent and dtype."""
+    a, b = _conv_sources(x, x2, what)
+    return a, b, _act(dy, (what, "dy"), a, anyc=True)
 
 
 def conv3d_wgrad(x, dy, ksize=3, dil=1, want_dbias=False, x2=None, out=None, amax_dy=None):
     """dW [cout, cin (+cin2), k,k,k] f32 (and dbias) from the layer input [x | x2] and the output gradient dy.
     amax_dy (split precision only): 1-element f32 device tensor holding max|dy| (see conv3d's amax)."""
-    ptr, c, p = _desc(x)
-    ptr2, c2, p2 = _desc2(x2)
-    dptr, cout, dp = _desc(dy)
-    n, d, h, w, _ = x.shape
-    kd = _conv_dtype(x.dtype, ksize)
+    a, b, g = _wgrad_operands(x, dy, x2, "conv3d_wgrad")
+    n, d, h, w, c, c2, cout = a.n, a.d, a.h, a.w, a.c, b.c, g.c
+    kd = _conv_dtype(a.dtype, ksize)
     if kd in (X3F, X3B) and (c % 8 or c2 % 8 or cout % 8):
-        kd = x.dtype  # (narrow test widths: the 16-bit kernels behind the split form want multiples of 8 channels)
+        kd = a.dtype  # (narrow test widths: the 16-bit kernels behind the split form want multiples of 8 channels)
     code = _code(kd)
     nbytes = _lib.lib().brats_conv3d_wgrad_ws_bytes(code, ksize, n, d, h, w, c, c2, cout)
-    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
-    dw = _grad_out(out, (cout, c + c2, ksize, ksize, ksize), x.device)
-    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_dbias else None
-    if amax_dy is not None and kd in (X3F, X3B):
-        with _span("conv_wgrad", c + c2, cout, ksize, dil, n, d, h, w, str(kd)):
-            _lib.check(_lib.lib().brats_conv3d_x3_wgrad(ptr, c, p, ptr2, c2, p2, dptr, dp, _f32(amax_dy), ws.data_ptr(), dw.data_ptr(),
-                                                        db.data_ptr() if db is not None else None, code, dil, n, d, h, w, cout,
-                                                        _stream()), "conv3d_x3_wgrad")
-        return dw, db
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=a.device)
+    dw = _grad_out(out, (cout, c + c2, ksize, ksize, ksize), a.device)
+    db = torch.empty(cout, dtype=torch.float32, device=a.device) if want_dbias else None
+    dbp = db.data_ptr() if db is not None else None
     with _span("conv_wgrad", c + c2, cout, ksize, dil, n, d, h, w, str(kd)):
-        _lib.check(_lib.lib().brats_conv3d_wgrad(ptr, c, p, ptr2, c2, p2, dptr, dp, ws.data_ptr(), dw.data_ptr(),
-                                                 db.data_ptr() if db is not None else None, code, ksize, dil, n, d, h, w,
-                                                 cout, _stream()), "conv3d_wgrad")
+        if amax_dy is not None and kd in (X3F, X3B):
+            _lib.check(_lib.lib().brats_conv3d_x3_wgrad(a.ptr, c, a.pitch, b.ptr, c2, b.pitch, g.ptr, g.pitch,
+                                                        _vec(amax_dy, 1, "conv3d_wgrad: amax_dy", a), ws.data_ptr(), dw.data_ptr(), dbp,
+                                                        code, dil, n, d, h, w, cout, _stream()), "conv3d_x3_wgrad")
+        else:
+            _lib.check(_lib.lib().brats_conv3d_wgrad(a.ptr, c, a.pitch, b.ptr, c2, b.pitch, g.ptr, g.pitch, ws.data_ptr(), dw.data_ptr(),
+                                                     dbp, code, ksize, dil, n, d, h, w, cout, _stream()), "conv3d_wgrad")
     return dw, db
 
 
@@ -706,64 +694,58 @@ def conv3d_wgrad_f8(x, dy, amax, amax_dy, x2=None, amax2=None, out=None):
     """dW [cout, cin (+cin2), 3, 3, 3] f32 of a dilation-1 layer with X and dY rounded to e4m3 on the way into the MFMA
     (v_mfma_scale_f32_16x16x128_f8f6f4).  amax* : 1-element f32 device tensors holding max|x|, max|x2|, max|dy| (recorded
     by the kernels that produced the tensors; absmax() otherwise).  Only where conv3d_wgrad_f8_ok()."""
-    ptr, c, p = _desc(x)
-    ptr2, c2, p2 = _desc2(x2)
-    dptr, cout, dp = _desc(dy)
-    n, d, h, w, _ = x.shape
     if not is16(x.dtype) or dy.dtype != x.dtype:
         raise _lib.BratsHipError("conv3d_wgrad_f8: bf16 activations only")
+    a, b, g = _wgrad_operands(x, dy, x2, "conv3d_wgrad_f8")
+    n, d, h, w, c, c2, cout = a.n, a.d, a.h, a.w, a.c, b.c, g.c
     nbytes = _lib.lib().brats_conv3d_wgrad_f8_ws_bytes(n, d, h, w, c, c2, cout)
     if nbytes == 0:
         raise _lib.BratsHipError(f"conv3d_wgrad_f8: not built for {c}+{c2} -> {cout} channels at {n}x{d}x{h}x{w} (use conv3d_wgrad)")
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-    dw = _grad_out(out, (cout, c + c2, 3, 3, 3), x.device)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=a.device)
+    dw = _grad_out(out, (cout, c + c2, 3, 3, 3), a.device)
     with _span("conv_wgrad_f8", c + c2, cout, 3, 1, n, d, h, w, "e4m3"):
-        _lib.check(_fn16("brats_conv3d_wgrad_f8", x.dtype)(ptr, c, p, _f32(amax), ptr2, c2, p2, _f32(amax2), dptr, dp, _f32(amax_dy),
-                                                    ws.data_ptr(), dw.data_ptr(), n, d, h, w, cout, _stream()), "conv3d_wgrad_f8")
+        _lib.check(_fn16("brats_conv3d_wgrad_f8", a.dtype)(a.ptr, c, a.pitch, _vec(amax, 1, "conv3d_wgrad_f8: amax", a), b.ptr, c2, b.pitch,
+                                                    _vec(amax2, 1, "conv3d_wgrad_f8: amax2", a, null=b.t is None), g.ptr, g.pitch,
+                                                    _vec(amax_dy, 1, "conv3d_wgrad_f8: amax_dy", a), ws.data_ptr(), dw.data_ptr(), n, d,
+                                                    h, w, cout, _stream()), "conv3d_wgrad_f8")
     return dw
 
 
 # ------------------------------------------------------------------------------------------ GroupNorm + act
 def gn_finalize(stats, n, c, groups, voxels, gamma, beta, eps=1e-5):
+    sp, tiles = _finalize_in(stats, n, c, groups, "gn_finalize")
     mean_rstd = torch.empty((n, groups, 2), dtype=torch.float32, device=stats.device)
     scale_shift = torch.empty((n, c, 2), dtype=torch.float32, device=stats.device)
     chan = torch.empty(_lib.lib().brats_gn_ws_doubles(n, c), dtype=torch.float64, device=stats.device)
-    _lib.check(_lib.lib().brats_gn_finalize(stats.data_ptr(), stats.shape[1], n, c, groups, float(voxels), eps,
-                                            _f32(gamma), _f32(beta), mean_rstd.data_ptr(), scale_shift.data_ptr(),
-                                            chan.data_ptr(), _stream()), "gn_finalize")
+    _lib.check(_lib.lib().brats_gn_finalize(sp, tiles, n, c, groups, float(voxels), eps, _vec(gamma, c, "gn_finalize: gamma", stats, null=True),
+                                            _vec(beta, c, "gn_finalize: beta", stats, null=True), mean_rstd.data_ptr(),
+                                            scale_shift.data_ptr(), chan.data_ptr(), _stream()), "gn_finalize")
     return mean_rstd, scale_shift
 
 
 def affine_act(y, scale_shift, act="relu", out=None, slope=0.01, amax=None, slope_t=None):
     """amax: optional zero-initialised 1-element f32 tensor that receives max|out| (scale source of conv3d_f8).
     slope_t: 1-element f32 device tensor overriding ``slope`` (nn.PReLU's learnable weight, act = "leakyrelu")."""
-    ptr, c, p = _desc(y)
-    n, d, h, w, _ = y.shape
-    if out is None:
-        out = new_act(n, d, h, w, c, y.dtype, y.device)
-    optr, oc, op = _desc(out)
-    _lib.check(_lib.lib().brats_affine_act_fwd(ptr, p, scale_shift.data_ptr(), optr, op, _code(y.dtype), ACTS[act], slope,
-                                               _f32(slope_t), n, d * h * w, c, _f32(amax), _stream()), "affine_act_fwd")
-    return out
+    a = _act(y, "affine_act: y")
+    o = _out(out, a.shape, a, "affine_act: out")
+    _lib.check(_lib.lib().brats_affine_act_fwd(a.ptr, a.pitch, _vec(scale_shift, a.n * a.c * 2, "affine_act: scale_shift", a), o.ptr, o.pitch,
+                                               a.code, ACTS[act], slope, _vec(slope_t, 1, "affine_act: slope_t", a, null=True), a.n, a.vox,
+                                               a.c, _vec(amax, 1, "affine_act: amax", a, null=True), _stream()), "affine_act_fwd")
+    return o.t
 
 
 def affine_act_add(y, scale_shift, add, act="relu", out=None, slope=0.01, slope_t=None):
     """out = add + act(y * scale + shift) in one pass (include/brats_hip.h: brats_affine_act_add_fwd): bit-identical to
     affine_act(y, ...) followed by an elementwise add of the two stored tensors.  add / out may be channel-slice views; out must
     not overlap y or add."""
-    ptr, c, p = _desc(y)
-    aptr, ac, ap = _desc(add)
-    n, d, h, w, _ = y.shape
-    if add.shape != y.shape or add.dtype != y.dtype:
-        raise _lib.BratsHipError("affine_act_add: add must have y's shape and dtype")
-    if out is None:
-        out = new_act(n, d, h, w, c, y.dtype, y.device)
-    optr, oc, op = _desc(out)
-    if out.shape != y.shape or out.dtype != y.dtype:
-        raise _lib.BratsHipError("affine_act_add: bad output tensor")
-    _lib.check(_lib.lib().brats_affine_act_add_fwd(ptr, p, scale_shift.data_ptr(), aptr, ap, optr, op, _code(y.dtype), ACTS[act], slope,
-                                                   _f32(slope_t), n, d * h * w, c, _stream()), "affine_act_add_fwd")
-    return out
+    a = _act(y, "affine_act_add: y")
+    b = _act(add, "affine_act_add: add", a)
+    o = _out(out, a.shape, a, "affine_act_add: out")
+    _lib.check(_lib.lib().brats_affine_act_add_fwd(a.ptr, a.pitch, _vec(scale_shift, a.n * a.c * 2, "affine_act_add: scale_shift", a), b.ptr,
+                                                   b.pitch, o.ptr, o.pitch, a.code, ACTS[act], slope,
+                                                   _vec(slope_t, 1, "affine_act_add: slope_t", a, null=True), a.n, a.vox, a.c, _stream()),
+               "affine_act_add_fwd")
+    return o.t
 
 
 def grad_sum(*srcs, out=None):
@@ -773,88 +755,81 @@ def grad_sum(*srcs, out=None):
     Small f32 tensors (weight gradients) go through a [1, 1, 1, rows, C] view.  out must not overlap a source."""
     if len(srcs) < 2:
         raise _lib.BratsHipError("grad_sum: at least two sources")
-    first = srcs[0]
-    if any(s.shape != first.shape or s.dtype != first.dtype for s in srcs[1:]):
-        raise _lib.BratsHipError("grad_sum: the sources must have one shape and dtype")
     if len(srcs) > 4:
         return grad_sum(grad_sum(*srcs[:4]), *srcs[4:], out=out)
-    n, d, h, w, c = first.shape
-    if out is None:
-        out = new_act(n, d, h, w, c, first.dtype, first.device)
-    optr, oc, op = _desc(out)
-    if out.shape != first.shape or out.dtype != first.dtype:
-        raise _lib.BratsHipError("grad_sum: bad output tensor")
-    args = []
-    for s in srcs:
-        ptr, _, p = _desc(s)
-        args += [ptr, p]
+    a = _act(srcs[0], "grad_sum: source 0")
+    args = [a.ptr, a.pitch]
+    for s in srcs[1:]:
+        b = _act(s, "grad_sum: source", a)
+        args += [b.ptr, b.pitch]
     args += [None, 0] * (4 - len(srcs))
-    _lib.check(_lib.lib().brats_grad_sum(*args, len(srcs), optr, op, _code(first.dtype), n, d * h * w, c, _stream()), "grad_sum")
-    return out
+    o = _out(out, a.shape, a, "grad_sum: out")
+    _lib.check(_lib.lib().brats_grad_sum(*args, len(srcs), o.ptr, o.pitch, a.code, a.n, a.vox, a.c, _stream()), "grad_sum")
+    return o.t
 
 
 def dropout(x, p, state, unit, out=None):
     """nn.Dropout(p) on an NDHWC activation (or, with the same arguments, on the gradient flowing back through it): x * keep /
     (1 - p) with keep a pure function of (state[0] = seed, state[1] = step counter, unit id, element index) -- brats_dropout.
     state: int64[2] DEVICE tensor.  out=x: in place."""
-    ptr, c, pitch = _desc(x)
-    n, d, h, w, _ = x.shape
-    if state.dtype != torch.int64 or state.numel() != 2 or not state.is_cuda:
-        raise _lib.BratsHipError("dropout: state must be an int64[2] device tensor (seed, step counter)")
-    if out is None:
-        out = new_act(n, d, h, w, c, x.dtype, x.device)
-    optr, oc, op = _desc(out)
-    if oc != c or out.dtype != x.dtype:
-        raise _lib.BratsHipError("dropout: bad output tensor")
-    _lib.check(_lib.lib().brats_dropout(ptr, pitch, optr, op, _code(x.dtype), n * d * h * w, c, float(p), state.data_ptr(), int(unit),
-                                        _stream()), "dropout")
-    return out
+    a = _act(x, "dropout: x")
+    o = _out(out, a.shape, a, "dropout: out")
+    _lib.check(_lib.lib().brats_dropout(a.ptr, a.pitch, o.ptr, o.pitch, a.code, a.n * a.vox, a.c, float(p),
+                                        _vec(state, 2, "dropout: state (seed, step counter)", a, torch.int64), int(unit), _stream()),
+               "dropout")
+    return o.t
 
 
 def affine_act_pool(y, scale_shift, act="relu", slope=0.01, amax=None, slope_t=None, with_avg=False, want_argmax=False):
     """(z, pooled) = (affine_act(y), maxpool2(z)) in one pass (include/brats_hip.h: brats_affine_act_pool_fwd).
     want_argmax: z._pool_argmax = the uint8 window index of every pooled element, which maxpool2_bwd(z, ...) then reads
     instead of the window itself."""
-    ptr, c, p = _desc(y)
-    n, d, h, w, _ = y.shape
-    z = new_act(n, d, h, w, c, y.dtype, y.device)
-    pooled = new_act(n, d // 2, h // 2, w // 2, c * (2 if with_avg else 1), y.dtype, y.device)
-    idx = torch.empty((n, d // 2, h // 2, w // 2, c), dtype=torch.uint8, device=y.device) if want_argmax else None
-    zp, _, zpitch = _desc(z)
-    pp, _, ppitch = _desc(pooled)
-    _lib.check(_lib.lib().brats_affine_act_pool_fwd(ptr, p, scale_shift.data_ptr(), zp, zpitch, pp, ppitch,
-                                                    idx.data_ptr() if idx is not None else None, _code(y.dtype), ACTS[act],
-                                                    slope, _f32(slope_t), n, d, h, w, c, int(with_avg), _f32(amax), _stream()),
+    a = _act(y, "affine_act_pool: y")
+    half = _even(a, "affine_act_pool")
+    z = torch.empty(a.shape, dtype=a.dtype, device=a.device)
+    pooled = torch.empty(half + (a.c * (2 if with_avg else 1),), dtype=a.dtype, device=a.device)
+    idx = torch.empty(half + (a.c,), dtype=torch.uint8, device=a.device) if want_argmax else None
+    _lib.check(_lib.lib().brats_affine_act_pool_fwd(a.ptr, a.pitch, _vec(scale_shift, a.n * a.c * 2, "affine_act_pool: scale_shift", a),
+                                                    z.data_ptr(), a.c, pooled.data_ptr(), pooled.shape[-1],
+                                                    idx.data_ptr() if idx is not None else None, a.code, ACTS[act], slope,
+                                                    _vec(slope_t, 1, "affine_act_pool: slope_t", a, null=True), a.n, a.d, a.h, a.w, a.c,
+                                                    int(with_avg), _vec(amax, 1, "affine_act_pool: amax", a, null=True), _stream()),
                "affine_act_pool_fwd")
     if idx is not None:
         z._pool_argmax = idx
     return z, pooled
 
 
-def _gn_bwd_bufs(y, dy=None):
-    """(dy like y, reduction workspace, dgamma [C], dbeta [C]) of the GroupNorm + activation backward entry points."""
-    n, c = y.shape[0], y.shape[-1]
-    red = torch.empty(_lib.lib().brats_gn_bwd_ws_floats(n, c), dtype=torch.float32, device=y.device)
-    dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
-    dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
-    return (torch.empty(y.shape, dtype=y.dtype, device=y.device) if dy is None else dy), red, dgamma, dbeta
+def _gn_bwd_args(a, scale_shift, mean_rstd, gamma, groups, what):
+    """The checked small operands every GroupNorm + activation backward reads: -> (scale_shift, mean_rstd, gamma) pointers."""
+    _groups(a.c, groups, what)
+    return (_vec(scale_shift, a.n * a.c * 2, (what, "scale_shift"), a), _vec(mean_rstd, a.n * groups * 2, (what, "mean_rstd"), a),
+            _vec(gamma, a.c, (what, "gamma"), a, null=True))
+
+
+def _norm_bwd_bufs(a, red_floats, what, out=None, chan=False):
+    """What a normalisation backward of the activation a writes: (dy like a -- `out`, checked, when given --, reduction workspace,
+    dgamma [C], dbeta [C], dconvbias [C] | None, the one asked for with chan (EvoNorm: the forward's per-channel sums are there))."""
+    f32 = dict(dtype=torch.float32, device=a.device)
+    return (_out(out, a.shape, a, (what, "out")), torch.empty(red_floats, **f32), torch.empty(a.c, **f32), torch.empty(a.c, **f32),
+            torch.empty(a.c, **f32) if chan else None)
+
+
+def _gn_bwd_bufs(a, what, out=None):
+    return _norm_bwd_bufs(a, _lib.lib().brats_gn_bwd_ws_floats(a.n, a.c), what, out)[:4]
 
 
 def gn_act_bwd(dz, y, scale_shift, mean_rstd, gamma, groups=8, act="relu", slope=0.01, amax=None, slope_t=None, out=None):
     """Returns (dy, dgamma, dbeta) for z = act(GroupNorm(y)); amax (optional, zero-initialised) receives max|dy|.
     out: the tensor dy is written to (e.g. a slice of a stacked buffer) instead of a fresh one."""
-    dzp, c, dzpitch = _desc(dz)
-    yp, _, ypitch = _desc(y)
-    n, d, h, w, _ = y.shape
-    dy, red, dgamma, dbeta = _gn_bwd_bufs(y, out)
-    dyp, dyc, dypitch = _desc(dy)
-    if dy.shape != y.shape or dy.dtype != y.dtype:
-        raise _lib.BratsHipError("gn_act_bwd: bad output tensor")
-    _lib.check(_lib.lib().brats_gn_act_bwd(dzp, dzpitch, yp, ypitch, scale_shift.data_ptr(), mean_rstd.data_ptr(),
-                                           _f32(gamma), dyp, dypitch, red.data_ptr(), dgamma.data_ptr(),
-                                           dbeta.data_ptr(), _code(y.dtype), ACTS[act], slope, _f32(slope_t), n, d * h * w, c,
-                                           groups, _f32(amax), _stream()), "gn_act_bwd")
-    return dy, dgamma, dbeta
+    a = _act(y, "gn_act_bwd: y")
+    g = _act(dz, "gn_act_bwd: dz", a)
+    ss, mr, gm = _gn_bwd_args(a, scale_shift, mean_rstd, gamma, groups, "gn_act_bwd")
+    dy, red, dgamma, dbeta = _gn_bwd_bufs(a, "gn_act_bwd", out)
+    _lib.check(_lib.lib().brats_gn_act_bwd(g.ptr, g.pitch, a.ptr, a.pitch, ss, mr, gm, dy.ptr, dy.pitch, red.data_ptr(), dgamma.data_ptr(),
+                                           dbeta.data_ptr(), a.code, ACTS[act], slope, _vec(slope_t, 1, "gn_act_bwd: slope_t", a, null=True),
+                                           a.n, a.vox, a.c, groups, _vec(amax, 1, "gn_act_bwd: amax", a, null=True), _stream()), "gn_act_bwd")
+    return dy.t, dgamma, dbeta
 
 
 def conv_bstats_ok(dtype, dil, c1, cout, act="relu", slope_t=None):
@@ -870,75 +845,86 @@ def conv3d_bstats(x, packed_w, cout, dil, fwd_y, scale_shift, act="relu", slope=
     GroupNorm backward's first pass for the block's FIRST unit (include/brats_hip.h: brats_conv3d_fwd_bstats): per tile and
     channel sum u and sum u * fwd_y, u = dz * act'(fwd_y * scale + shift).  -> (dz, tile_stats) for gn_act_bwd_tiles().
     f32 tensors inside a split_precision() block run brats_conv3d_x3_fwd_bstats; amax = max|x| as for conv3d (fp16 pairs)."""
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
-    fp, fc, fpitch = _desc(fwd_y)
-    if fc != cout or fwd_y.dtype != x.dtype or tuple(fwd_y.shape[:4]) != (n, d, h, w):
-        raise _lib.BratsHipError("conv3d_bstats: the forward tensor must have the output's shape and dtype")
-    out = new_act(n, d, h, w, cout, x.dtype, x.device)
-    stats = torch.empty((n, tiles_per_sample(d, h, w), cout, 2), dtype=torch.float32, device=x.device)
+    a = _act(x, "conv3d_bstats: x")
+    n, d, h, w, c = a.shape
+    f = _act(fwd_y, "conv3d_bstats: the forward tensor", a, shape=(n, d, h, w, cout))
+    kd = _conv_dtype(a.dtype, 3)
+    code = _code(kd)
+    wp = _conv_packed(packed_w, code, 3, dil, c, 0, cout, "conv3d_bstats", a)
+    ss = _vec(scale_shift, n * cout * 2, "conv3d_bstats: scale_shift", a)
+    out = new_act(n, d, h, w, cout, a.dtype, a.device)
+    stats = torch.empty((n, tiles_per_sample(d, h, w), cout, 2), dtype=torch.float32, device=a.device)
     # (a family of its own in the bench's kernel table: these launches carry a GroupNorm-backward pass in their epilogue and
     #  are not the plain implicit GEMM the roofline line is about)
-    kd = _conv_dtype(x.dtype, 3)
-    if kd in (X3F, X3B):
-        with _span("conv_igemm_bst", c, cout, 3, dil, n, d, h, w, str(kd)):
-            _lib.check(_lib.lib().brats_conv3d_x3_fwd_bstats(ptr, c, p, _f32(amax), packed_w.data_ptr(), out.data_ptr(), cout, fp, fpitch,
-                                                             scale_shift.data_ptr(), ACTS[act], float(slope), stats.data_ptr(),
-                                                             _code(kd), dil, n, d, h, w, cout, _stream()), "conv3d_x3_fwd_bstats")
-        return out, stats
-    with _span("conv_igemm_bst", c, cout, 3, dil, n, d, h, w, str(x.dtype)):
-        _lib.check(_lib.lib().brats_conv3d_fwd_bstats(ptr, c, p, packed_w.data_ptr(), out.data_ptr(), cout, fp, fpitch,
-                                                      scale_shift.data_ptr(), ACTS[act], float(slope), stats.data_ptr(),
-                                                      _code(x.dtype), dil, n, d, h, w, cout, _stream()), "conv3d_fwd_bstats")
+    with _span("conv_igemm_bst", c, cout, 3, dil, n, d, h, w, str(kd)):
+        if kd in (X3F, X3B):
+            _lib.check(_lib.lib().brats_conv3d_x3_fwd_bstats(a.ptr, c, a.pitch, _vec(amax, 1, "conv3d_bstats: amax", a, null=True), wp,
+                                                             out.data_ptr(), cout, f.ptr, f.pitch, ss, ACTS[act], float(slope),
+                                                             stats.data_ptr(), code, dil, n, d, h, w, cout, _stream()), "conv3d_x3_fwd_bstats")
+        else:
+            _lib.check(_lib.lib().brats_conv3d_fwd_bstats(a.ptr, c, a.pitch, wp, out.data_ptr(), cout, f.ptr, f.pitch, ss, ACTS[act],
+                                                          float(slope), stats.data_ptr(), code, dil, n, d, h, w, cout, _stream()),
+                       "conv3d_fwd_bstats")
     return out, stats
 
 
 def gn_act_bwd_tiles(tile_stats, dz, y, scale_shift, mean_rstd, gamma, groups=8, act="relu", slope=0.01, amax=None):
     """gn_act_bwd whose first pass was taken by conv3d_bstats (tile_stats): -> (dy, dgamma, dbeta)."""
-    dzp, c, dzpitch = _desc(dz)
-    yp, _, ypitch = _desc(y)
-    n, d, h, w, _ = y.shape
-    dy, red, dgamma, dbeta = _gn_bwd_bufs(y)
-    _lib.check(_lib.lib().brats_gn_act_bwd_tiles(tile_stats.data_ptr(), tile_stats.shape[1], dzp, dzpitch, yp, ypitch,
-                                                 scale_shift.data_ptr(), mean_rstd.data_ptr(), _f32(gamma), dy.data_ptr(), c,
-                                                 red.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), _code(y.dtype), ACTS[act],
-                                                 float(slope), n, d * h * w, c, groups, _f32(amax), _stream()), "gn_act_bwd_tiles")
-    return dy, dgamma, dbeta
+    a = _act(y, "gn_act_bwd_tiles: y")
+    g = _act(dz, "gn_act_bwd_tiles: dz", a)
+    ts = _tile_stats(tile_stats, a, a.c, "gn_act_bwd_tiles: tile_stats")
+    ss, mr, gm = _gn_bwd_args(a, scale_shift, mean_rstd, gamma, groups, "gn_act_bwd_tiles")
+    dy, red, dgamma, dbeta = _gn_bwd_bufs(a, "gn_act_bwd_tiles")
+    _lib.check(_lib.lib().brats_gn_act_bwd_tiles(ts, tile_stats.shape[1], g.ptr, g.pitch, a.ptr, a.pitch, ss, mr, gm, dy.ptr, a.c,
+                                                 red.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), a.code, ACTS[act], float(slope), a.n,
+                                                 a.vox, a.c, groups, _vec(amax, 1, "gn_act_bwd_tiles: amax", a, null=True), _stream()),
+               "gn_act_bwd_tiles")
+    return dy.t, dgamma, dbeta
+
+
+def _head_bwd_in(a, head_weight, dlogits, what):
+    """The checked inputs and fresh outputs of a folded head backward: -> (K, [K, C] f32 weight, f32 dlogits planes, workspace,
+    dweight [K, C], dbias [K])."""
+    k, hw = _head_weight(head_weight, a, what)
+    dl = _planes(dlogits, (what, "dlogits"), a, (a.n, k, a.d, a.h, a.w))
+    f32 = dict(dtype=torch.float32, device=a.device)
+    return (k, hw, dl, torch.empty(_lib.lib().brats_gn_bwd_head_ws_floats(a.n, a.c, k), **f32), torch.empty((k, a.c), **f32),
+            torch.empty(k, **f32))
 
 
 def gn_act_bwd_head(dlogits, head_weight, y, scale_shift, mean_rstd, gamma, groups=8, act="relu", slope=0.01, amax=None):
     """GroupNorm + activation backward of the layer under the 1x1x1 output head, the head's backward folded in
     (include/brats_hip.h: brats_gn_act_bwd_head): -> (dy, dgamma, dbeta, dhead_weight [K,C,1,1,1], dhead_bias [K])."""
-    yp, c, ypitch = _desc(y)
-    n, d, h, w, _ = y.shape
-    k = head_weight.shape[0]
-    dev = y.device
-    hw = head_weight.detach().reshape(k, c).contiguous().float()
-    dl = dlogits.contiguous().float()
-    dy, red, dgamma, dbeta = _gn_bwd_bufs(y)
-    hws = torch.empty(_lib.lib().brats_gn_bwd_head_ws_floats(n, c, k), dtype=torch.float32, device=dev)
-    dhw = torch.empty((k, c), dtype=torch.float32, device=dev)
-    dhb = torch.empty(k, dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().brats_gn_act_bwd_head(dl.data_ptr(), hw.data_ptr(), k, yp, ypitch, scale_shift.data_ptr(),
-                                                mean_rstd.data_ptr(), _f32(gamma), dy.data_ptr(), c, red.data_ptr(), hws.data_ptr(),
-                                                dgamma.data_ptr(), dbeta.data_ptr(), dhw.data_ptr(), dhb.data_ptr(), _code(y.dtype),
-                                                ACTS[act], slope, n, d * h * w, c, groups, _f32(amax), _stream()), "gn_act_bwd_head")
-    return dy, dgamma, dbeta, dhw.reshape(k, c, 1, 1, 1), dhb
+    a = _act(y, "gn_act_bwd_head: y")
+    ss, mr, gm = _gn_bwd_args(a, scale_shift, mean_rstd, gamma, groups, "gn_act_bwd_head")
+    dy, red, dgamma, dbeta = _gn_bwd_bufs(a, "gn_act_bwd_head")
+    k, hw, dl, hws, dhw, dhb = _head_bwd_in(a, head_weight, dlogits, "gn_act_bwd_head")
+    _lib.check(_lib.lib().brats_gn_act_bwd_head(dl.data_ptr(), hw.data_ptr(), k, a.ptr, a.pitch, ss, mr, gm, dy.ptr, a.c, red.data_ptr(),
+                                                hws.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), dhw.data_ptr(), dhb.data_ptr(), a.code,
+                                                ACTS[act], slope, a.n, a.vox, a.c, groups, _vec(amax, 1, "gn_act_bwd_head: amax", a, null=True),
+                                                _stream()), "gn_act_bwd_head")
+    return dy.t, dgamma, dbeta, dhw.reshape(k, a.c, 1, 1, 1), dhb
+
+
+def _pool_grads(a, dskip, dpool, argmax, with_avg, what):
+    """The checked gradient sources of a level-ending layer with output a: d_skip like a, d_pooled (even extents, twice the
+    channels with_avg) and the uint8 arg-max plane of the pooling -> (_Act, _Act, pointer)."""
+    half = _even(a, what)
+    return (_act(dskip, (what, "dskip"), a), _act(dpool, (what, "dpool"), a, shape=half + (a.c * (2 if with_avg else 1),)),
+            _vec(argmax, a.n * (a.vox // 8) * a.c, (what, "argmax"), a, torch.uint8))
 
 
 def gn_act_bwd_pool(dskip, dpool, argmax, y, scale_shift, mean_rstd, gamma, groups=8, act="relu", slope=0.01, amax=None):
     """GroupNorm + activation backward of the layer that ends an encoder level, its output gradient dskip +
     maxpool-backward(dpool) composed inside the two passes (include/brats_hip.h: brats_gn_act_bwd_pool): -> (dy, dgamma, dbeta)."""
-    yp, c, ypitch = _desc(y)
-    n, d, h, w, _ = y.shape
-    sp, _, spitch = _desc(dskip)
-    pp, _, ppitch = _desc(dpool)
-    dy, red, dgamma, dbeta = _gn_bwd_bufs(y)
-    _lib.check(_lib.lib().brats_gn_act_bwd_pool(sp, spitch, pp, ppitch, argmax.data_ptr(), yp, ypitch, scale_shift.data_ptr(),
-                                                mean_rstd.data_ptr(), _f32(gamma), dy.data_ptr(), c, red.data_ptr(),
-                                                dgamma.data_ptr(), dbeta.data_ptr(), _code(y.dtype), ACTS[act], slope, n, d, h, w, c,
-                                                groups, _f32(amax), _stream()), "gn_act_bwd_pool")
-    return dy, dgamma, dbeta
+    a = _act(y, "gn_act_bwd_pool: y")
+    s, q, ip = _pool_grads(a, dskip, dpool, argmax, False, "gn_act_bwd_pool")
+    ss, mr, gm = _gn_bwd_args(a, scale_shift, mean_rstd, gamma, groups, "gn_act_bwd_pool")
+    dy, red, dgamma, dbeta = _gn_bwd_bufs(a, "gn_act_bwd_pool")
+    _lib.check(_lib.lib().brats_gn_act_bwd_pool(s.ptr, s.pitch, q.ptr, q.pitch, ip, a.ptr, a.pitch, ss, mr, gm, dy.ptr, a.c, red.data_ptr(),
+                                                dgamma.data_ptr(), dbeta.data_ptr(), a.code, ACTS[act], slope, a.n, a.d, a.h, a.w, a.c,
+                                                groups, _vec(amax, 1, "gn_act_bwd_pool: amax", a, null=True), _stream()), "gn_act_bwd_pool")
+    return dy.t, dgamma, dbeta
 
 
 def head_fold_ok(head_weight, act, slope_t):
@@ -948,61 +934,68 @@ def head_fold_ok(head_weight, act, slope_t):
 
 def prelu_slope_grad(dz, y, scale_shift):
     """d loss / d slope [1] of z = PReLU(y * scale + shift) with one shared slope (nn.PReLU()): sum dz * min(pre, 0)."""
-    dzp, c, dzpitch = _desc(dz)
-    yp, _, ypitch = _desc(y)
-    n, d, h, w, _ = y.shape
-    ws = torch.empty(_lib.lib().brats_prelu_ws_floats(n), dtype=torch.float32, device=y.device)
-    out = torch.empty(1, dtype=torch.float32, device=y.device)
-    _lib.check(_lib.lib().brats_prelu_slope_grad(dzp, dzpitch, yp, ypitch, scale_shift.data_ptr(), ws.data_ptr(), out.data_ptr(),
-                                                 _code(y.dtype), n, d * h * w, c, _stream()), "prelu_slope_grad")
+    a = _act(y, "prelu_slope_grad: y")
+    g = _act(dz, "prelu_slope_grad: dz", a)
+    ws = torch.empty(_lib.lib().brats_prelu_ws_floats(a.n), dtype=torch.float32, device=a.device)
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().brats_prelu_slope_grad(g.ptr, g.pitch, a.ptr, a.pitch, _vec(scale_shift, a.n * a.c * 2, "prelu_slope_grad: scale_shift", a),
+                                                 ws.data_ptr(), out.data_ptr(), a.code, a.n, a.vox, a.c, _stream()), "prelu_slope_grad")
     return out
 
 
 # ------------------------------------------------------------------------------------------ pool / upsample
+def _argmax_plane(idx, a, what):
+    """Pointer of the uint8 window-index plane of a 2x2x2 pooling of the activation a: one byte per pooled element."""
+    return _vec(idx, a.n * (a.vox // 8) * a.c, what, a, torch.uint8)
+
+
 def maxpool2(x, with_avg=False, out=None, want_argmax=False):
     """want_argmax (training): x._pool_argmax = the uint8 window index of every pooled element; maxpool2_bwd(x, ...) then
     reads those bytes instead of the eight window voxels of x."""
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
-    co = 2 * c if with_avg else c
-    if out is None:
-        out = new_act(n, d // 2, h // 2, w // 2, co, x.dtype, x.device)
-    optr, oc, op = _desc(out)
-    idx = torch.empty((n, d // 2, h // 2, w // 2, c), dtype=torch.uint8, device=x.device) if want_argmax else None
-    _lib.check(_lib.lib().brats_maxpool2_fwd(ptr, p, optr, op, idx.data_ptr() if idx is not None else None, _code(x.dtype), n, c, d,
-                                             h, w, int(with_avg), _stream()), "maxpool2_fwd")
+    a = _act(x, "maxpool2: x")
+    half = _even(a, "maxpool2")
+    o = _out(out, half + (2 * a.c if with_avg else a.c,), a, "maxpool2: out")
+    idx = torch.empty(half + (a.c,), dtype=torch.uint8, device=a.device) if want_argmax else None
+    _lib.check(_lib.lib().brats_maxpool2_fwd(a.ptr, a.pitch, o.ptr, o.pitch, idx.data_ptr() if idx is not None else None, a.code, a.n, a.c,
+                                             a.d, a.h, a.w, int(with_avg), _stream()), "maxpool2_fwd")
     if idx is not None:
         x._pool_argmax = idx
-    return out
+    return o.t
 
 
 def maxpool2_bwd(x, dy, dx_skip=None, with_avg=False):
-    ptr, c, p = _desc(x)
-    dptr, _, dp = _desc(dy)
-    n, d, h, w, _ = x.shape
-    dx = new_act(n, d, h, w, c, x.dtype, x.device)
-    sptr, sp = (None, 0)
-    if dx_skip is not None:
-        sptr, _, sp = _desc(dx_skip)
+    a = _act(x, "maxpool2_bwd: x")
+    g = _act(dy, "maxpool2_bwd: dy", a, shape=_even(a, "maxpool2_bwd") + (2 * a.c if with_avg else a.c,))
+    s = _act2(dx_skip, "maxpool2_bwd: dx_skip", a)
+    dx = torch.empty(a.shape, dtype=a.dtype, device=a.device)
     idx = getattr(x, "_pool_argmax", None)
     if idx is not None:  # recorded by affine_act_pool: the window voxels of x are not read again
-        _lib.check(_lib.lib().brats_maxpool2_bwd_idx(idx.data_ptr(), dptr, dp, sptr, sp, dx.data_ptr(), c, _code(x.dtype), n, c,
-                                                     d, h, w, int(with_avg), _stream()), "maxpool2_bwd_idx")
+        _lib.check(_lib.lib().brats_maxpool2_bwd_idx(_argmax_plane(idx, a, "maxpool2_bwd: x._pool_argmax"), g.ptr, g.pitch, s.ptr, s.pitch,
+                                                     dx.data_ptr(), a.c, a.code, a.n, a.c, a.d, a.h, a.w, int(with_avg), _stream()),
+                   "maxpool2_bwd_idx")
         return dx
-    _lib.check(_lib.lib().brats_maxpool2_bwd(ptr, p, None, 0, dptr, dp, sptr, sp, dx.data_ptr(), c, _code(x.dtype), n, c,
-                                             d, h, w, int(with_avg), _stream()), "maxpool2_bwd")
+    _lib.check(_lib.lib().brats_maxpool2_bwd(a.ptr, a.pitch, None, 0, g.ptr, g.pitch, s.ptr, s.pitch, dx.data_ptr(), a.c, a.code, a.n, a.c,
+                                             a.d, a.h, a.w, int(with_avg), _stream()), "maxpool2_bwd")
     return dx
 
 
+def _scaled(a, scale):
+    return (a.n, a.d * scale, a.h * scale, a.w * scale, a.c)
+
+
+def _coarse(g, scale, what, exc):
+    """The shape of the tensor whose up-sampling by `scale` has g's shape."""
+    if scale < 1 or g.d % scale or g.h % scale or g.w % scale:
+        raise exc(f"{what}: the extent {(g.d, g.h, g.w)} is no multiple of the scale {scale}")
+    return (g.n, g.d // scale, g.h // scale, g.w // scale, g.c)
+
+
 def upsample(x, scale=2, out=None):
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
-    if out is None:
-        out = new_act(n, d * scale, h * scale, w * scale, c, x.dtype, x.device)
-    optr, oc, op = _desc(out)
-    _lib.check(_lib.lib().brats_upsample_fwd(ptr, p, optr, op, _code(x.dtype), n, c, d, h, w, scale, _stream()),
+    a = _act(x, "upsample: x")
+    o = _out(out, _scaled(a, scale), a, "upsample: out")
+    _lib.check(_lib.lib().brats_upsample_fwd(a.ptr, a.pitch, o.ptr, o.pitch, a.code, a.n, a.c, a.d, a.h, a.w, scale, _stream()),
                "upsample_fwd")
-    return out
+    return o.t
 
 
 def set_upsample_bwd_fused(mode):
@@ -1015,67 +1008,40 @@ def upsample_bwd(dy, scale=2, add=None, out=None):
     """The adjoint of upsample; add (a tensor of the result's shape and dtype, e.g. the gradient another consumer of the same
     activation produced): the result is upsample_bwd(dy) + add, bit for bit, in the same launches (brats_upsample_bwd_add).
     out: a channel-slice view to write into instead of a new tensor."""
-    dptr, c, dp = _desc(dy)
-    n, do, ho, wo, _ = dy.shape
-    d, h, w = do // scale, ho // scale, wo // scale
-    code = _code(dy.dtype)
-    ws = torch.empty(_lib.lib().brats_upsample_bwd_ws_bytes(code, n, c, d, h, w, scale), dtype=torch.uint8, device=dy.device)
-    dx = new_act(n, d, h, w, c, dy.dtype, dy.device) if out is None else out
-    xptr, xc, xp = _desc(dx)
-    if tuple(dx.shape) != (n, d, h, w, c) or dx.dtype != dy.dtype:
-        raise ValueError(f"upsample_bwd: out {tuple(dx.shape)} {dx.dtype} does not match {(n, d, h, w, c)} {dy.dtype}")
+    g = _act(dy, "upsample_bwd: dy")
+    n, d, h, w, c = shape = _coarse(g, scale, "upsample_bwd", _lib.BratsHipError)
+    ws = torch.empty(_lib.lib().brats_upsample_bwd_ws_bytes(g.code, n, c, d, h, w, scale), dtype=torch.uint8, device=g.device)
+    dx = _out(out, shape, g, "upsample_bwd: out", exc=ValueError)
     if add is None:
-        _lib.check(_lib.lib().brats_upsample_bwd(dptr, dp, xptr, xp, ws.data_ptr(), code, n, c, d, h, w, scale, _stream()), "upsample_bwd")
-        return dx
-    if tuple(add.shape) != (n, d, h, w, c) or add.dtype != dy.dtype:
-        raise ValueError(f"upsample_bwd: addend {tuple(add.shape)} {add.dtype} does not match {(n, d, h, w, c)} {dy.dtype}")
-    aptr, _, ap = _desc(add)
-    _lib.check(_lib.lib().brats_upsample_bwd_add(dptr, dp, aptr, ap, xptr, xp, ws.data_ptr(), code, n, c, d, h, w, scale, _stream()),
-               "upsample_bwd_add")
-    return dx
+        _lib.check(_lib.lib().brats_upsample_bwd(g.ptr, g.pitch, dx.ptr, dx.pitch, ws.data_ptr(), g.code, n, c, d, h, w, scale, _stream()),
+                   "upsample_bwd")
+        return dx.t
+    b = _act(add, "upsample_bwd: addend", g, shape=shape, exc=ValueError)
+    _lib.check(_lib.lib().brats_upsample_bwd_add(g.ptr, g.pitch, b.ptr, b.pitch, dx.ptr, dx.pitch, ws.data_ptr(), g.code, n, c, d, h, w, scale,
+                                                 _stream()), "upsample_bwd_add")
+    return dx.t
 
 
 def upsample_nearest(x, scale=2, out=None):
     """nn.Upsample(scale_factor=2) in its default mode on an NDHWC tensor: out[n][z][y][x] = x[n][z // 2][y // 2][x // 2], a copy.
     out: a channel-slice view to write into instead of a new tensor."""
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
-    if out is None:
-        out = new_act(n, d * scale, h * scale, w * scale, c, x.dtype, x.device)
-    optr, oc, op = _desc(out)
-    if tuple(out.shape) != (n, d * scale, h * scale, w * scale, c) or out.dtype != x.dtype:
-        raise ValueError(f"upsample_nearest: out {tuple(out.shape)} {out.dtype} does not match {(n, d * scale, h * scale, w * scale, c)} {x.dtype}")
-    _lib.check(_lib.lib().brats_upsample_nearest_fwd(ptr, p, optr, op, _code(x.dtype), n, c, d, h, w, scale, _stream()),
+    a = _act(x, "upsample_nearest: x")
+    o = _out(out, _scaled(a, scale), a, "upsample_nearest: out", exc=ValueError)
+    _lib.check(_lib.lib().brats_upsample_nearest_fwd(a.ptr, a.pitch, o.ptr, o.pitch, a.code, a.n, a.c, a.d, a.h, a.w, scale, _stream()),
                "upsample_nearest_fwd")
-    return out
+    return o.t
 
 
 def upsample_nearest_bwd(dy, scale=2, add=None, out=None):
     """The adjoint of upsample_nearest: every coarse voxel = the f32 sum of its 8 children, in one launch without a workspace.
     add / out: as in upsample_bwd (the result is upsample_nearest_bwd(dy) + add, bit for bit)."""
-    dptr, c, dp = _desc(dy)
-    n, do, ho, wo, _ = dy.shape
-    if do % scale or ho % scale or wo % scale:
-        raise ValueError(f"upsample_nearest_bwd: the extent {(do, ho, wo)} is no multiple of the scale {scale}")
-    d, h, w = do // scale, ho // scale, wo // scale
-    dx = new_act(n, d, h, w, c, dy.dtype, dy.device) if out is None else out
-    xptr, xc, xp = _desc(dx)
-    if tuple(dx.shape) != (n, d, h, w, c) or dx.dtype != dy.dtype:
-        raise ValueError(f"upsample_nearest_bwd: out {tuple(dx.shape)} {dx.dtype} does not match {(n, d, h, w, c)} {dy.dtype}")
-    aptr, ap = None, 0
-    if add is not None:
-        if tuple(add.shape) != (n, d, h, w, c) or add.dtype != dy.dtype:
-            raise ValueError(f"upsample_nearest_bwd: addend {tuple(add.shape)} {add.dtype} does not match {(n, d, h, w, c)} {dy.dtype}")
-        aptr, _, ap = _desc(add)
-    _lib.check(_lib.lib().brats_upsample_nearest_bwd(dptr, dp, aptr, ap, xptr, xp, _code(dy.dtype), n, c, d, h, w, scale, _stream()),
+    g = _act(dy, "upsample_nearest_bwd: dy")
+    n, d, h, w, c = shape = _coarse(g, scale, "upsample_nearest_bwd", ValueError)
+    dx = _out(out, shape, g, "upsample_nearest_bwd: out", exc=ValueError)
+    b = _act2(add, "upsample_nearest_bwd: addend", g, shape=shape, exc=ValueError)
+    _lib.check(_lib.lib().brats_upsample_nearest_bwd(g.ptr, g.pitch, b.ptr, b.pitch, dx.ptr, dx.pitch, g.code, n, c, d, h, w, scale, _stream()),
                "upsample_nearest_bwd")
-    return dx
-
-
-def _planes(t, what):
-    if t.dim() != 5 or not t.is_cuda:
-        raise _lib.BratsHipError(f"{what}: expected a CUDA tensor of shape [N, K, D, H, W]")
-    return t.contiguous().float()
+    return dx.t
 
 
 def planes_nearest(low, scale):
@@ -1100,162 +1066,178 @@ def planes_nearest_bwd(dout, scale):
 
 
 # ------------------------------------------------------------------------------------------ heads
+def _bias(bias, k, what, a):
+    """Pointer of an optional bias parameter of k elements."""
+    return _vec(bias.detach() if bias is not None else None, k, what, a, null=True)
+
+
 def head(x, weight, bias, scale=1):
     """NCDHW f32 logits [N, K, D*s, H*s, W*s] = upsample_s(conv1x1(x)); weight [K, C, 1,1,1]."""
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
-    k = weight.shape[0]
-    wf = weight.detach().reshape(k, c).contiguous().float()
-    out = torch.empty((n, k, d * scale, h * scale, w * scale), dtype=torch.float32, device=x.device)
-    low = torch.empty((n, k, d, h, w), dtype=torch.float32, device=x.device) if scale > 1 else None
-    _lib.check(_lib.lib().brats_head_fwd(ptr, p, wf.data_ptr(), _f32(bias.detach()) if bias is not None else None,
-                                         low.data_ptr() if low is not None else None, out.data_ptr(), _code(x.dtype), n, c,
-                                         k, d, h, w, scale, _stream()), "head_fwd")
+    a = _act(x, "head: x")
+    n, d, h, w, c = a.shape
+    k, wf = _head_weight(weight, a, "head")
+    out = torch.empty((n, k, d * scale, h * scale, w * scale), dtype=torch.float32, device=a.device)
+    low = torch.empty((n, k, d, h, w), dtype=torch.float32, device=a.device) if scale > 1 else None
+    _lib.check(_lib.lib().brats_head_fwd(a.ptr, a.pitch, wf.data_ptr(), _bias(bias, k, "head: bias", a),
+                                         low.data_ptr() if low is not None else None, out.data_ptr(), a.code, n, c, k, d, h, w, scale,
+                                         _stream()), "head_fwd")
     return out
 
 
 def gn_head(y, scale_shift, weight, bias, act="relu", slope=0.01):
     """NCDHW f32 logits of the output head on act(GroupNorm(y)) without storing that activation
     (include/brats_hip.h: brats_gn_head_fwd); bit-identical to head(affine_act(y, scale_shift, act), weight, bias)."""
-    ptr, c, p = _desc(y)
-    n, d, h, w, _ = y.shape
-    k = weight.shape[0]
-    wf = weight.detach().reshape(k, c).contiguous().float()
-    out = torch.empty((n, k, d, h, w), dtype=torch.float32, device=y.device)
-    _lib.check(_lib.lib().brats_gn_head_fwd(ptr, p, scale_shift.data_ptr(), ACTS[act], slope, wf.data_ptr(),
-                                            _f32(bias.detach()) if bias is not None else None, out.data_ptr(), _code(y.dtype), n, c,
-                                            k, d * h * w, _stream()), "gn_head_fwd")
+    a = _act(y, "gn_head: y")
+    k, wf = _head_weight(weight, a, "gn_head")
+    out = torch.empty((a.n, k, a.d, a.h, a.w), dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().brats_gn_head_fwd(a.ptr, a.pitch, _vec(scale_shift, a.n * a.c * 2, "gn_head: scale_shift", a), ACTS[act], slope,
+                                            wf.data_ptr(), _bias(bias, k, "gn_head: bias", a), out.data_ptr(), a.code, a.n, a.c, k, a.vox,
+                                            _stream()), "gn_head_fwd")
     return out
 
 
 def head_bwd(x, weight, dout, scale=1, want_dx=True):
     """Returns (dx | None, dweight [K,C,1,1,1], dbias [K])."""
-    ptr, c, p = _desc(x)
-    n, d, h, w, _ = x.shape
-    k = weight.shape[0]
-    wf = weight.detach().reshape(k, c).contiguous().float()
-    dout = dout.contiguous().float()
+    a = _act(x, "head_bwd: x")
+    n, d, h, w, c = a.shape
+    k, wf = _head_weight(weight, a, "head_bwd")
+    dout = _planes(dout, "head_bwd: dout", a, (n, k, d * scale, h * scale, w * scale))
     nbytes = _lib.lib().brats_head_bwd_ws_bytes(n, c, k, d, h, w, scale)
-    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
-    dx = new_act(n, d, h, w, c, x.dtype, x.device) if want_dx else None
-    dw = torch.empty((k, c), dtype=torch.float32, device=x.device)
-    db = torch.empty(k, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().brats_head_bwd(ptr, p, wf.data_ptr(), dout.data_ptr(), ws.data_ptr(),
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=a.device)
+    dx = new_act(n, d, h, w, c, a.dtype, a.device) if want_dx else None
+    dw = torch.empty((k, c), dtype=torch.float32, device=a.device)
+    db = torch.empty(k, dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().brats_head_bwd(a.ptr, a.pitch, wf.data_ptr(), dout.data_ptr(), ws.data_ptr(),
                                          dx.data_ptr() if dx is not None else None, c, dw.data_ptr(), db.data_ptr(),
-                                         _code(x.dtype), n, c, k, d, h, w, scale, _stream()), "head_bwd")
+                                         a.code, n, c, k, d, h, w, scale, _stream()), "head_bwd")
     return dx, dw.reshape(k, c, 1, 1, 1), db
 
 
 # ------------------------------------------------------------------------------------------ EvoNorm-S0 / SE helpers
+def _chan_sums(chan, a, what):
+    """Pointer of the f64 per-channel sums evonorm_finalize keeps for the backward (None: no convolution-bias gradient): the
+    kernels read the totals [N, C, 2] at its start (csrc/norm.hip), the finaliser's workspace behind them is not touched again."""
+    return _vec(chan, a.n * a.c * 2, what, a, torch.float64, null=True, at_least=True)
+
+
 def evonorm_finalize(stats, n, c, groups, voxels, eps=1e-5):
     """Returns (mean_rstd [N, groups, 2], chan [N, C, 2] f64 per-channel sums kept for the backward)."""
+    sp, tiles = _finalize_in(stats, n, c, groups, "evonorm_finalize")
     mean_rstd = torch.empty((n, groups, 2), dtype=torch.float32, device=stats.device)
     chan = torch.empty(_lib.lib().brats_gn_ws_doubles(n, c), dtype=torch.float64, device=stats.device)  # totals first
-    _lib.check(_lib.lib().brats_evonorm_finalize(stats.data_ptr(), stats.shape[1], n, c, groups, float(voxels), eps,
-                                                 mean_rstd.data_ptr(), chan.data_ptr(), _stream()), "evonorm_finalize")
+    _lib.check(_lib.lib().brats_evonorm_finalize(sp, tiles, n, c, groups, float(voxels), eps, mean_rstd.data_ptr(), chan.data_ptr(),
+                                                 _stream()), "evonorm_finalize")
     return mean_rstd, chan
+
+
+def _evo_args(a, mean_rstd, gamma, beta, groups, what):
+    """The checked small operands of the EvoNorm entry points: -> (mean_rstd, gamma, beta) pointers."""
+    _groups(a.c, groups, what)
+    return (_vec(mean_rstd, a.n * groups * 2, (what, "mean_rstd"), a), _vec(gamma, a.c, (what, "gamma"), a, null=True),
+            _vec(beta, a.c, (what, "beta"), a, null=True))
 
 
 def evonorm(y, mean_rstd, gamma, beta, groups=8, out=None, want_chansum=False, amax=None):
     """z = y*sigmoid(y) * rstd_g * gamma + beta; optionally also sum_v z per (n, c) (SE's pooling)."""
-    ptr, c, p = _desc(y)
-    n, d, h, w, _ = y.shape
-    if out is None:
-        out = new_act(n, d, h, w, c, y.dtype, y.device)
-    optr, _, op = _desc(out)
-    cs = torch.empty(_lib.lib().brats_chan_ws_floats(n, c, 1), dtype=torch.float32, device=y.device) if want_chansum else None
-    _lib.check(_lib.lib().brats_evonorm_fwd(ptr, p, mean_rstd.data_ptr(), _f32(gamma), _f32(beta), optr, op,
-                                            cs.data_ptr() if cs is not None else None, _code(y.dtype), n, d * h * w, c,
-                                            groups, _f32(amax), _stream()), "evonorm_fwd")
-    return out, (cs[:n * c].view(n, c) if cs is not None else None)
+    a = _act(y, "evonorm: y")
+    mr, gm, bt = _evo_args(a, mean_rstd, gamma, beta, groups, "evonorm")
+    o = _out(out, a.shape, a, "evonorm: out")
+    cs = torch.empty(_lib.lib().brats_chan_ws_floats(a.n, a.c, 1), dtype=torch.float32, device=a.device) if want_chansum else None
+    _lib.check(_lib.lib().brats_evonorm_fwd(a.ptr, a.pitch, mr, gm, bt, o.ptr, o.pitch, cs.data_ptr() if cs is not None else None, a.code,
+                                            a.n, a.vox, a.c, groups, _vec(amax, 1, "evonorm: amax", a, null=True), _stream()), "evonorm_fwd")
+    return o.t, (cs[:a.n * a.c].view(a.n, a.c) if cs is not None else None)
 
 
 def evonorm_bwd(dz, y, mean_rstd, gamma, groups=8, chan=None, amax=None, gscale=None, gadd=None):
     """Returns (dy, dgamma, dbeta, dconvbias|None); dconvbias = sum_v dy needs the forward's `chan` sums.
     gscale / gadd ([N, C] f32): the incoming gradient is read as dz * gscale + gadd (the SE layer's backward folded in)."""
-    dzp, c, dzpitch = _desc(dz)
-    yp, _, ypitch = _desc(y)
-    n, d, h, w, _ = y.shape
-    dy = new_act(n, d, h, w, c, y.dtype, y.device)
-    red = torch.empty(_lib.lib().brats_chan_ws_floats(n, c, 3), dtype=torch.float32, device=y.device)
-    dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
-    dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
-    dcb = torch.empty(c, dtype=torch.float32, device=y.device) if chan is not None else None
-    _lib.check(_lib.lib().brats_evonorm_bwd(dzp, dzpitch, yp, ypitch, mean_rstd.data_ptr(), _f32(gamma), dy.data_ptr(), c,
-                                            red.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                            chan.data_ptr() if chan is not None else None,
-                                            dcb.data_ptr() if dcb is not None else None, _code(y.dtype), n,
-                                            d * h * w, c, groups, _f32(amax), _f32(gscale.contiguous()) if gscale is not None else None,
-                                            _f32(gadd.contiguous()) if gadd is not None else None, _stream()), "evonorm_bwd")
-    return dy, dgamma, dbeta, dcb
+    a = _act(y, "evonorm_bwd: y")
+    g = _act(dz, "evonorm_bwd: dz", a)
+    mr, gm, _ = _evo_args(a, mean_rstd, gamma, None, groups, "evonorm_bwd")
+    dy, red, dgamma, dbeta, dcb = _norm_bwd_bufs(a, _lib.lib().brats_chan_ws_floats(a.n, a.c, 3), "evonorm_bwd", chan=chan is not None)
+    _lib.check(_lib.lib().brats_evonorm_bwd(g.ptr, g.pitch, a.ptr, a.pitch, mr, gm, dy.ptr, a.c, red.data_ptr(), dgamma.data_ptr(),
+                                            dbeta.data_ptr(), _chan_sums(chan, a, "evonorm_bwd: chan"),
+                                            dcb.data_ptr() if dcb is not None else None, a.code, a.n, a.vox, a.c, groups,
+                                            _vec(amax, 1, "evonorm_bwd: amax", a, null=True),
+                                            _vec(gscale, a.n * a.c, "evonorm_bwd: gscale", a, null=True),
+                                            _vec(gadd, a.n * a.c, "evonorm_bwd: gadd", a, null=True), _stream()), "evonorm_bwd")
+    return dy.t, dgamma, dbeta, dcb
 
 
 def evonorm_bwd_tiles(tile_stats, dz, y, mean_rstd, gamma, beta, groups=8, chan=None, amax=None):
     """evonorm_bwd whose first pass was taken by conv3d_bstats(..., fwd_y = z, act="leakyrelu", slope=1.0) -- tile_stats = per tile
     and channel (sum dz, sum dz * z) with z the EvoNorm's stored output (include/brats_hip.h: brats_evonorm_bwd_tiles).
     -> (dy, dgamma, dbeta, dconvbias|None)."""
-    dzp, c, dzpitch = _desc(dz)
-    yp, _, ypitch = _desc(y)
-    n, d, h, w, _ = y.shape
-    dy = new_act(n, d, h, w, c, y.dtype, y.device)
-    red = torch.empty(_lib.lib().brats_evonorm_bwd_tiles_ws_floats(n, c), dtype=torch.float32, device=y.device)
-    dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
-    dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
-    dcb = torch.empty(c, dtype=torch.float32, device=y.device) if chan is not None else None
-    _lib.check(_lib.lib().brats_evonorm_bwd_tiles(tile_stats.data_ptr(), tile_stats.shape[1], dzp, dzpitch, yp, ypitch, mean_rstd.data_ptr(),
-                                                  _f32(gamma), _f32(beta), dy.data_ptr(), c, red.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                                  chan.data_ptr() if chan is not None else None, dcb.data_ptr() if dcb is not None else None,
-                                                  _code(y.dtype), n, d * h * w, c, groups, _f32(amax), _stream()), "evonorm_bwd_tiles")
-    return dy, dgamma, dbeta, dcb
+    a = _act(y, "evonorm_bwd_tiles: y")
+    g = _act(dz, "evonorm_bwd_tiles: dz", a)
+    ts = _tile_stats(tile_stats, a, a.c, "evonorm_bwd_tiles: tile_stats")
+    mr, gm, bt = _evo_args(a, mean_rstd, gamma, beta, groups, "evonorm_bwd_tiles")
+    dy, red, dgamma, dbeta, dcb = _norm_bwd_bufs(a, _lib.lib().brats_evonorm_bwd_tiles_ws_floats(a.n, a.c), "evonorm_bwd_tiles",
+                                                 chan=chan is not None)
+    _lib.check(_lib.lib().brats_evonorm_bwd_tiles(ts, tile_stats.shape[1], g.ptr, g.pitch, a.ptr, a.pitch, mr, gm, bt, dy.ptr, a.c,
+                                                  red.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), _chan_sums(chan, a, "evonorm_bwd_tiles: chan"),
+                                                  dcb.data_ptr() if dcb is not None else None, a.code, a.n, a.vox, a.c, groups,
+                                                  _vec(amax, 1, "evonorm_bwd_tiles: amax", a, null=True), _stream()), "evonorm_bwd_tiles")
+    return dy.t, dgamma, dbeta, dcb
 
 
 def channel_dot(a, b=None):
     """[N, C] f32 = sum over voxels of a (* b)."""
-    ap, c, apitch = _desc(a)
-    bp, bpitch = (None, 0)
-    if b is not None:
-        bp, _, bpitch = _desc(b)
-    n, d, h, w, _ = a.shape
-    out = torch.empty(_lib.lib().brats_chan_ws_floats(n, c, 1), dtype=torch.float32, device=a.device)
-    _lib.check(_lib.lib().brats_channel_dot(ap, apitch, bp, bpitch, out.data_ptr(), _code(a.dtype), n, d * h * w, c,
-                                            _stream()), "channel_dot")
-    return out[:n * c].view(n, c)
+    a = _act(a, "channel_dot: a")
+    b = _act2(b, "channel_dot: b", a)
+    out = torch.empty(_lib.lib().brats_chan_ws_floats(a.n, a.c, 1), dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().brats_channel_dot(a.ptr, a.pitch, b.ptr, b.pitch, out.data_ptr(), a.code, a.n, a.vox, a.c, _stream()), "channel_dot")
+    return out[:a.n * a.c].view(a.n, a.c)
 
 
 def channel_scale(a, scale, add=None, out=None, amax=None):
     """out[v][c] = a[v][c] * scale[n][c] (+ add[n][c])."""
-    ap, c, apitch = _desc(a)
-    n, d, h, w, _ = a.shape
-    if out is None:
-        out = new_act(n, d, h, w, c, a.dtype, a.device)
-    optr, _, op = _desc(out)
-    _lib.check(_lib.lib().brats_channel_scale(ap, apitch, _f32(scale.contiguous()), _f32(add.contiguous()) if add is not None else None,
-                                              optr, op, _code(a.dtype), n, d * h * w, c, _f32(amax), _stream()), "channel_scale")
-    return out
+    a = _act(a, "channel_scale: a")
+    o = _out(out, a.shape, a, "channel_scale: out")
+    _lib.check(_lib.lib().brats_channel_scale(a.ptr, a.pitch, _vec(scale, a.n * a.c, "channel_scale: scale", a),
+                                              _vec(add, a.n * a.c, "channel_scale: add", a, null=True), o.ptr, o.pitch, a.code, a.n, a.vox,
+                                              a.c, _vec(amax, 1, "channel_scale: amax", a, null=True), _stream()), "channel_scale")
+    return o.t
+
+
+def _se_in(chansum, w1, what):
+    """The checked channel sums [N, C] an SE gate starts from and its hidden width: -> (n, c, ch, pointer)."""
+    if not isinstance(chansum, torch.Tensor) or chansum.dim() != 2 or not isinstance(w1, torch.Tensor) or w1.dim() != 2:
+        raise _lib.BratsHipError((what, "chansum must be [N, C] and w1 [C/r, C]"))
+    return tuple(chansum.shape) + (w1.shape[0], _vec(chansum, None, (what, "chansum"), None))
+
+
+def _se_weights(like, c, ch, what, w1, w2, b1=None, b2=None):
+    """Pointers of the SE layer's parameters: w1 [ch, c], w2 [c, ch] and, where the entry point reads them, b1 [ch], b2 [c]."""
+    return (_vec(w1.detach(), ch * c, (what, "w1"), like), _bias(b1, ch, (what, "b1"), like),
+            _vec(w2.detach(), c * ch, (what, "w2"), like), _bias(b2, c, (what, "b2"), like))
 
 
 def se_gate(chansum, voxels, w1, b1, w2, b2):
     """ResidualSELayer gate from the channel sums of z: -> (1 + gate [N, C], hidden [N, C/r]) in one launch."""
-    n, c = chansum.shape
-    ch = w1.shape[0]
+    n, c, ch, cp = _se_in(chansum, w1, "se_gate")
+    if b1 is None or b2 is None:
+        raise _lib.BratsHipError("se_gate: the SE layer's biases are missing")
     gate1p = torch.empty((n, c), dtype=torch.float32, device=chansum.device)
     hidden = torch.empty((n, ch), dtype=torch.float32, device=chansum.device)
-    _lib.check(_lib.lib().brats_se_fwd(_f32(chansum.contiguous()), 1.0 / float(voxels), _f32(w1.detach().contiguous()), _f32(b1.detach()),
-                                       _f32(w2.detach().contiguous()), _f32(b2.detach()), gate1p.data_ptr(), hidden.data_ptr(),
-                                       n, c, ch, _stream()), "se_fwd")
+    _lib.check(_lib.lib().brats_se_fwd(cp, 1.0 / float(voxels), *_se_weights(chansum, c, ch, "se_gate", w1, w2, b1, b2), gate1p.data_ptr(),
+                                       hidden.data_ptr(), n, c, ch, _stream()), "se_fwd")
     return gate1p, hidden
+
+
+def _se_saved(like, n, c, ch, what, hidden, gate1p):
+    return _vec(hidden, n * ch, (what, "hidden"), like), _vec(gate1p, n * c, (what, "gate1p"), like)
 
 
 def se_gate_bwd(dgate, chansum, voxels, hidden, gate1p, w1, w2):
     """-> (gadd [N, C] = d loss / d gap / V, dW1, db1, dW2, db2) in one launch."""
-    n, c = chansum.shape
-    ch = w1.shape[0]
-    dev = chansum.device
-    gadd = torch.empty((n, c), dtype=torch.float32, device=dev)
-    dw1, db1 = torch.empty((ch, c), dtype=torch.float32, device=dev), torch.empty((ch,), dtype=torch.float32, device=dev)
-    dw2, db2 = torch.empty((c, ch), dtype=torch.float32, device=dev), torch.empty((c,), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().brats_se_bwd(_f32(dgate.contiguous()), _f32(chansum.contiguous()), 1.0 / float(voxels), _f32(hidden), _f32(gate1p),
-                                       _f32(w1.detach().contiguous()), _f32(w2.detach().contiguous()), gadd.data_ptr(), dw1.data_ptr(),
+    n, c, ch, cp = _se_in(chansum, w1, "se_gate_bwd")
+    f32 = dict(dtype=torch.float32, device=chansum.device)
+    gadd = torch.empty((n, c), **f32)
+    dw1, db1, dw2, db2 = torch.empty((ch, c), **f32), torch.empty((ch,), **f32), torch.empty((c, ch), **f32), torch.empty((c,), **f32)
+    wp1, _, wp2, _ = _se_weights(chansum, c, ch, "se_gate_bwd", w1, w2)
+    _lib.check(_lib.lib().brats_se_bwd(_vec(dgate, n * c, "se_gate_bwd: dgate", chansum), cp, 1.0 / float(voxels),
+                                       *_se_saved(chansum, n, c, ch, "se_gate_bwd", hidden, gate1p), wp1, wp2, gadd.data_ptr(), dw1.data_ptr(),
                                        db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), n, c, ch, _stream()), "se_bwd")
     return gadd, dw1, db1, dw2, db2
 
@@ -1264,40 +1246,35 @@ def evonorm_se(y, mean_rstd, gamma, beta, w1, b1, w2, b2, groups=8, out=None, am
     """EvoNorm + ResidualSELayer in one call, the EvoNorm output never stored (csrc/se.hpp):
     -> (out = z * (1 + gate), chansum [N, C] = sum_v z, gate1p [N, C], hidden [N, C/r]).
     apply=False: statistics pass + gate only (out = None): the consumer recomputes the output on load (evonorm_head)."""
-    ptr, c, p = _desc(y)
-    n, d, h, w, _ = y.shape
-    ch = w1.shape[0]
-    dev = y.device
-    if not apply:
-        out, optr, op = None, None, 0
-    else:
-        if out is None:
-            out = new_act(n, d, h, w, c, y.dtype, dev)
-        optr, _, op = _desc(out)
-    ws = torch.empty(_lib.lib().brats_chan_ws_floats(n, c, 1), dtype=torch.float32, device=dev)
-    cs = torch.empty((n, c), dtype=torch.float32, device=dev)
-    gate1p = torch.empty((n, c), dtype=torch.float32, device=dev)
-    hidden = torch.empty((n, ch), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().brats_evonorm_se_fwd(ptr, p, mean_rstd.data_ptr(), _f32(gamma), _f32(beta), _f32(w1.detach().contiguous()),
-                                               _f32(b1.detach()), _f32(w2.detach().contiguous()), _f32(b2.detach()), optr, op,
-                                               ws.data_ptr(), cs.data_ptr(), gate1p.data_ptr(), hidden.data_ptr(), ch,
-                                               _code(y.dtype), n, d * h * w, c, groups, _f32(amax), _stream()), "evonorm_se_fwd")
-    return out, cs, gate1p, hidden
+    a = _act(y, "evonorm_se: y")
+    n, c, ch = a.n, a.c, w1.shape[0]
+    if b1 is None or b2 is None:
+        raise _lib.BratsHipError("evonorm_se: the SE layer's biases are missing")
+    mr, gm, bt = _evo_args(a, mean_rstd, gamma, beta, groups, "evonorm_se")
+    o = _out(out, a.shape, a, "evonorm_se: out") if apply else _NO_ACT
+    f32 = dict(dtype=torch.float32, device=a.device)
+    ws = torch.empty(_lib.lib().brats_chan_ws_floats(n, c, 1), **f32)
+    cs, gate1p, hidden = torch.empty((n, c), **f32), torch.empty((n, c), **f32), torch.empty((n, ch), **f32)
+    _lib.check(_lib.lib().brats_evonorm_se_fwd(a.ptr, a.pitch, mr, gm, bt, *_se_weights(a, c, ch, "evonorm_se", w1, w2, b1, b2), o.ptr, o.pitch,
+                                               ws.data_ptr(), cs.data_ptr(), gate1p.data_ptr(), hidden.data_ptr(), ch, a.code, n, a.vox, c,
+                                               groups, _vec(amax, 1, "evonorm_se: amax", a, null=True), _stream()), "evonorm_se_fwd")
+    return o.t, cs, gate1p, hidden
 
 
 def evonorm_head(y, mean_rstd, gamma, beta, gate1p, weight, bias, groups=8):
     """NCDHW f32 logits of the output head on the gated EvoNorm output of y without storing it
     (include/brats_hip.h: brats_evonorm_head_fwd); bit-identical to head(evonorm_se(...)[0], weight, bias)."""
-    ptr, c, p = _desc(y)
-    n, d, h, w, _ = y.shape
-    k = weight.shape[0]
+    a = _act(y, "evonorm_head: y")
+    n, c = a.n, a.c
+    _evo_args(a, mean_rstd, gamma, beta, groups, "evonorm_head")
+    _vec(gate1p, n * c, "evonorm_head: gate1p", a)
+    k, wf = _head_weight(weight, a, "evonorm_head")
     # the per-(n, channel) constants in the kernel's own order of operations: (rstd * gamma) * gate1p, beta * gate1p
-    rstd = mean_rstd[:, :, 1].repeat_interleave(c // groups, dim=1)
-    ss = torch.stack(((rstd * gamma.float()) * gate1p, beta.float() * gate1p), -1).contiguous()
-    wf = weight.detach().reshape(k, c).contiguous().float()
-    out = torch.empty((n, k, d, h, w), dtype=torch.float32, device=y.device)
-    _lib.check(_lib.lib().brats_evonorm_head_fwd(ptr, p, ss.data_ptr(), wf.data_ptr(), _f32(bias.detach()) if bias is not None else None,
-                                                 out.data_ptr(), _code(y.dtype), n, c, k, d * h * w, _stream()), "evonorm_head_fwd")
+    rstd = mean_rstd.view(n, groups, 2)[:, :, 1].repeat_interleave(c // groups, dim=1)
+    ss = torch.stack(((rstd * gamma.float()) * gate1p.view(n, c), beta.float() * gate1p.view(n, c)), -1).contiguous()
+    out = torch.empty((n, k, a.d, a.h, a.w), dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().brats_evonorm_head_fwd(a.ptr, a.pitch, ss.data_ptr(), wf.data_ptr(), _bias(bias, k, "evonorm_head: bias", a),
+                                                 out.data_ptr(), a.code, n, c, k, a.vox, _stream()), "evonorm_head_fwd")
     return out
 
 
@@ -1309,42 +1286,38 @@ def evonorm_se_bwd(do, y, mean_rstd, gamma, beta, se_chansum, hidden, gate1p, w1
     whose backward is folded in too; two more results: dhead_weight [K,C,1,1,1], dhead_bias [K].
     pool = (d_skip, d_pooled, argmax bytes, with_avg) instead of `do` (None): the block ends an encoder level, `do` = d_skip +
     pooling-backward(d_pooled) is composed inside the passes (brats_evonorm_se_bwd_pool)."""
-    yp, c, ypitch = _desc(y)
-    n, d, h, w, _ = y.shape
-    ch = w1.shape[0]
-    dev = y.device
+    a = _act(y, "evonorm_se_bwd: y")
+    n, c, ch = a.n, a.c, w1.shape[0]
+    mr, gm, bt = _evo_args(a, mean_rstd, gamma, beta, groups, "evonorm_se_bwd")
 
     def f32(*shape):
-        return torch.empty(shape, dtype=torch.float32, device=dev)
+        return torch.empty(shape, dtype=torch.float32, device=a.device)
 
-    dy = new_act(n, d, h, w, c, y.dtype, dev)
-    ws = f32(_lib.lib().brats_chan_ws_floats(n, c, 5) + n * c * 3)
-    dgamma, dbeta, dcb = f32(c), f32(c), (f32(c) if chan is not None else None)
+    dy, ws, dgamma, dbeta, dcb = _norm_bwd_bufs(a, _lib.lib().brats_chan_ws_floats(n, c, 5) + n * c * 3, "evonorm_se_bwd", chan=chan is not None)
     gadd, dw1, db1, dw2, db2 = f32(n, c), f32(ch, c), f32(ch), f32(c, ch), f32(c)
+    wp1, _, wp2, _ = _se_weights(a, c, ch, "evonorm_se_bwd", w1, w2)
+    amaxp, st = _vec(amax, 1, "evonorm_se_bwd: amax", a, null=True), _stream()
     # the arguments the two entry points share, in their order
-    norm = (yp, ypitch, mean_rstd.data_ptr(), _f32(gamma), _f32(beta), dy.data_ptr(), c, ws.data_ptr(), dgamma.data_ptr(),
-            dbeta.data_ptr(), chan.data_ptr() if chan is not None else None, dcb.data_ptr() if dcb is not None else None,
-            _f32(se_chansum.contiguous()), _f32(hidden), _f32(gate1p), _f32(w1.detach().contiguous()),
-            _f32(w2.detach().contiguous()), gadd.data_ptr(), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), ch)
-    res = (dy, dgamma, dbeta, dcb, dw1, db1, dw2, db2)
+    norm = (a.ptr, a.pitch, mr, gm, bt, dy.ptr, c, ws.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+            _chan_sums(chan, a, "evonorm_se_bwd: chan"), dcb.data_ptr() if dcb is not None else None,
+            _vec(se_chansum, n * c, "evonorm_se_bwd: se_chansum", a), *_se_saved(a, n, c, ch, "evonorm_se_bwd", hidden, gate1p), wp1, wp2,
+            gadd.data_ptr(), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), ch)
+    res = (dy.t, dgamma, dbeta, dcb, dw1, db1, dw2, db2)
     if pool is not None:
-        sp, _, spitch = _desc(pool[0])
-        pp, _, ppitch = _desc(pool[1])
-        _lib.check(_lib.lib().brats_evonorm_se_bwd_pool(sp, spitch, pp, ppitch, pool[2].data_ptr(), int(pool[3]), d, h, w, *norm,
-                                                        _code(y.dtype), n, c, groups, _f32(amax), _stream()), "evonorm_se_bwd_pool")
+        s, q, ip = _pool_grads(a, pool[0], pool[1], pool[2], pool[3], "evonorm_se_bwd(pool=)")
+        _lib.check(_lib.lib().brats_evonorm_se_bwd_pool(s.ptr, s.pitch, q.ptr, q.pitch, ip, int(pool[3]), a.d, a.h, a.w, *norm, a.code, n, c,
+                                                        groups, amaxp, st), "evonorm_se_bwd_pool")
         return res
     if head is None:
-        dop, _, dopitch = _desc(do)
+        g = _act(do, "evonorm_se_bwd: do", a)
         dl = hw = hws = dhw = dhb = None
         k = 0
     else:
-        dop, dopitch = None, 0
-        k = head[0].shape[0]
-        hw = head[0].detach().reshape(k, c).contiguous().float()
-        dl = head[1].contiguous().float()
-        hws, dhw, dhb = f32(_lib.lib().brats_gn_bwd_head_ws_floats(n, c, k)), f32(k, c), f32(k)
-    _lib.check(_lib.lib().brats_evonorm_se_bwd(dop, dopitch, *norm, _f32(dl), _f32(hw), k, _f32(hws), _f32(dhw), _f32(dhb),
-                                               _code(y.dtype), n, d * h * w, c, groups, _f32(amax), _stream()), "evonorm_se_bwd")
+        g = _NO_ACT
+        k, hw, dl, hws, dhw, dhb = _head_bwd_in(a, head[0], head[1], "evonorm_se_bwd(head=)")
+    _lib.check(_lib.lib().brats_evonorm_se_bwd(g.ptr, g.pitch, *norm, *(t.data_ptr() if t is not None else None for t in (dl, hw)), k,
+                                               *(t.data_ptr() if t is not None else None for t in (hws, dhw, dhb)), a.code, n, a.vox, c,
+                                               groups, amaxp, st), "evonorm_se_bwd")
     return res if head is None else res + (dhw.reshape(k, c, 1, 1, 1), dhb)
 
 
@@ -1365,7 +1338,7 @@ def pack_weights_direct(w, dtype, mode, cin_off=0, cin_cnt=None):
     cout_w, k = w.shape[0], w.shape[2]
     cin_w, cnt, kdim, rows, _ = _pack_geometry(w, mode, None, cin_off, cin_cnt)
     code = _code(dtype)
-    nbytes = _lib.lib().brats_dconv_packed_bytes(code, k, kdim, rows)
+    nbytes = _SIZES[("dconv", code, k, kdim, rows)] = _lib.lib().brats_dconv_packed_bytes(code, k, kdim, rows)
     if nbytes == 0:
         raise _lib.BratsHipError(f"pack_weights_direct: K channels {kdim} must be a multiple of {16 if code in (BF16, F16) else 8}")
     wd = _padded(w, cin_w)
@@ -1381,46 +1354,48 @@ def dconv_run(jobs, n, d, h, w, dtype):
     """One launch of the direct (gather) convolution.  jobs: up to 4 of (terms, bias | None, out) with terms = up to 4 of
     (x, packed_w, ksize, dil); out[..., :] = bias + sum over the terms of conv(x, w).  x / out: NDHWC tensors or
     channel-slice views of [n, d, h, w, *]."""
+    if not 1 <= len(jobs) <= 4 or any(not 1 <= len(terms) <= 4 for terms, _, _ in jobs):
+        raise _lib.BratsHipError("dconv_run: one to four jobs of one to four terms each")
     rec = np.zeros(len(jobs), _DCONV_JOB)
-    keep = []
+    code, first = _code(dtype), None
     for j, (terms, bias, out) in enumerate(jobs):
-        optr, rows, opitch = _desc(out)
-        if out.dtype != dtype or tuple(out.shape[:4]) != (n, d, h, w):
+        o = _act(out, "dconv_run: out", first, dtype=dtype, anyc=True)
+        first = first or o
+        if o.shape[:4] != (n, d, h, w):
             raise _lib.BratsHipError("dconv_run: bad output tensor")
-        rec[j]["nterms"], rec[j]["rows"], rec[j]["y"], rec[j]["ypitch"] = len(terms), rows, optr, opitch
-        rec[j]["bias"] = _f32(bias) or 0
+        rec[j]["nterms"], rec[j]["rows"], rec[j]["y"], rec[j]["ypitch"] = len(terms), o.c, o.ptr, o.pitch
+        rec[j]["bias"] = _vec(bias, o.c, "dconv_run: bias", o, null=True) or 0
         for t, (x, wpk, ksize, dil) in enumerate(terms):
-            xptr, cin, xpitch = _desc(x)
-            if x.dtype != dtype or tuple(x.shape[:4]) != (n, d, h, w):
-                raise _lib.BratsHipError("dconv_run: bad input tensor")
-            rec[j]["term"][t] = (xptr, wpk.data_ptr(), xpitch, cin, ksize, dil)
-            keep.append(wpk)
+            a = _act(x, "dconv_run: input", o, anyc=True)
+            wp = _packed(wpk, ("dconv", code, ksize, a.c, o.c), lambda: _lib.lib().brats_dconv_packed_bytes(code, ksize, a.c, o.c),
+                         "dconv_run", o)
+            rec[j]["term"][t] = (a.ptr, wp, a.pitch, a.c, ksize, dil)
     buf = rec.tobytes()
-    _lib.check(_lib.lib().brats_dconv_run(buf, len(jobs), _code(dtype), n, d, h, w, _stream()), "dconv_run")
+    _lib.check(_lib.lib().brats_dconv_run(buf, len(jobs), code, n, d, h, w, _stream()), "dconv_run")
 
 
 def conv3d_wgrad_shift(x, dy, ksize=1, dil=1, want_dbias=False, out=None, amax_dy=None):
     """dW [cout, cin, k, k, k] f32 (and dbias) of a 1x1x1 convolution, or of a 3x3x3 convolution at any dilation
     (shifted-tap form of the weight-gradient kernel: the ASPP branches with dilation 4 / 6).  Inside a split_precision()
     block f32 tensors run the three-product form (amax_dy: the scale source of dy, see conv3d_wgrad)."""
-    ptr, c, p = _desc(x)
-    dptr, cout, dp = _desc(dy)
-    n, d, h, w, _ = x.shape
-    kd = x.dtype
-    if _X3 is not None and x.dtype == torch.float32 and c % 8 == 0 and cout % 8 == 0:
+    a, _, g = _wgrad_operands(x, dy, None, "conv3d_wgrad_shift")
+    n, d, h, w, c, cout = a.n, a.d, a.h, a.w, a.c, g.c
+    kd = a.dtype
+    if _X3 is not None and a.dtype == torch.float32 and c % 8 == 0 and cout % 8 == 0:
         kd = _X3  # (1x1x1 too: the voxel GEMM is MFMA-bound in exact f32 -- 3.0 of EquiUnetASSPEvo-48's 44 ms x3 step)
     code = _code(kd)
     nbytes = _lib.lib().brats_conv3d_wgrad_shift_ws_bytes(code, ksize, n, d, h, w, c, cout)
-    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
-    dw = _grad_out(out, (cout, c, ksize, ksize, ksize), x.device)
-    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_dbias else None
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=a.device)
+    dw = _grad_out(out, (cout, c, ksize, ksize, ksize), a.device)
+    db = torch.empty(cout, dtype=torch.float32, device=a.device) if want_dbias else None
     dbp = db.data_ptr() if db is not None else None
     with _span("conv_wgrad", c, cout, ksize, dil, n, d, h, w, str(kd)):
         if amax_dy is not None and kd in (X3F, X3B):
-            _lib.check(_lib.lib().brats_conv3d_x3_wgrad_shift(ptr, c, p, dptr, dp, _f32(amax_dy), ws.data_ptr(), dw.data_ptr(), dbp,
-                                                              code, ksize, dil, n, d, h, w, cout, _stream()), "conv3d_x3_wgrad_shift")
+            _lib.check(_lib.lib().brats_conv3d_x3_wgrad_shift(a.ptr, c, a.pitch, g.ptr, g.pitch, _vec(amax_dy, 1, "conv3d_wgrad_shift: amax_dy", a),
+                                                              ws.data_ptr(), dw.data_ptr(), dbp, code, ksize, dil, n, d, h, w, cout, _stream()),
+                       "conv3d_x3_wgrad_shift")
         else:
-            _lib.check(_lib.lib().brats_conv3d_wgrad_shift(ptr, c, p, dptr, dp, ws.data_ptr(), dw.data_ptr(), dbp, code, ksize, dil,
+            _lib.check(_lib.lib().brats_conv3d_wgrad_shift(a.ptr, c, a.pitch, g.ptr, g.pitch, ws.data_ptr(), dw.data_ptr(), dbp, code, ksize, dil,
                                                            n, d, h, w, cout, _stream()), "conv3d_wgrad_shift")
     return dw, db
 
@@ -1489,6 +1464,8 @@ def argmax_labels(prob_sum, img=None):
     n, k = p.shape[:2]
     im = None
     if img is not None:
+        if img.device != p.device:
+            raise _lib.BratsHipError(f"argmax_labels: image on {img.device}, predictions on {p.device}")
         im = img.contiguous().float()
         if im.dim() != 5 or im.shape[0] != n or tuple(im.shape[2:]) != tuple(p.shape[2:]):
             raise ValueError(f"image {tuple(im.shape)} does not match predictions {tuple(p.shape)}")
@@ -1651,21 +1628,34 @@ class CbamSaved:
     __slots__ = ("scale", "pooled", "hidden", "argvox", "comp", "cidx", "z", "stats", "pidx")
 
 
-def _cbam_params(w1, b1, w2, b2, wc, gamma, beta):
-    ps = [p.detach().contiguous() for p in (w1, b1, w2, b2, wc, gamma, beta)]
-    ch, c = ps[0].shape
-    if tuple(ps[2].shape) != (c, ch) or ps[1].numel() != ch or ps[3].numel() != c or ps[4].numel() != 686 or ps[5].numel() != 1 \
-            or ps[6].numel() != 1:
+def _cbam_params(a, w1, b1, w2, b2, wc, gamma, beta, what):
+    """The checked parameters of one CBAM block over the activation a's channels: -> (their seven pointers, ch)."""
+    if not isinstance(w1, torch.Tensor) or w1.dim() != 2:
         raise _lib.BratsHipError("cbam: parameter shapes do not belong to one CBAM block")
-    for p in ps:
-        _f32(p)
-    return ps, c, ch
+    ch, cw = w1.shape
+    if cw != a.c:
+        raise _lib.BratsHipError(f"{what}: the block is built for {cw} channels, the tensor has {a.c}")
+    sizes = (ch * cw, ch, cw * ch, cw, 686, 1, 1)
+    names = ("w1", "b1", "w2", "b2", "wc", "gamma", "beta")
+    return [_vec(p.detach(), k, (what, nm), a) for p, k, nm in zip((w1, b1, w2, b2, wc, gamma, beta), sizes, names)], ch
 
 
 def _cbam_storage(x, what):
     if x.dtype == torch.float16:
-        raise _lib.BratsHipError(f"{what}: fp16 storage is not built for the CBAM block (float32 or bfloat16)")
+        raise _lib.BratsHipError((what, "fp16 storage is not built for the CBAM block (float32 or bfloat16)"))
     return _code(x.dtype)
+
+
+def _cbam_saved(sv, a, ch, what, pooled=False):
+    """Every field of a CbamSaved checked against the input's n, c and voxel count: -> their pointers, in __slots__ order."""
+    n, c, v = a.n, a.c, a.vox
+    if not isinstance(sv, CbamSaved):
+        raise _lib.BratsHipError((what, "saved must come from cbam_fwd(save=True)"))
+    return (_vec(sv.scale, n * c, (what, "saved.scale"), a), _vec(sv.pooled, n * 2 * c, (what, "saved.pooled"), a),
+            _vec(sv.hidden, n * 2 * ch, (what, "saved.hidden"), a), _vec(sv.argvox, n * c, (what, "saved.argvox"), a, torch.int32),
+            _vec(sv.comp, n * 2 * v, (what, "saved.comp"), a), _vec(sv.cidx, n * v, (what, "saved.cidx"), a, torch.int16),
+            _vec(sv.z, n * v, (what, "saved.z"), a), _vec(sv.stats, n * 2, (what, "saved.stats"), a),
+            _argmax_plane(sv.pidx, a, (what, "saved.pidx")) if pooled else None)
 
 
 def cbam_fwd(x, w1, b1, w2, b2, wc, gamma, beta, out=None, save=True, pool=False):
@@ -1675,22 +1665,16 @@ def cbam_fwd(x, w1, b1, w2, b2, wc, gamma, beta, out=None, save=True, pool=False
     pool=True (D, H, W even): -> (out, maxpool2(out), saved), the pooled tensor written by the last pass (brats_cbam_apply_pool);
     with save, saved.pidx holds the pooling's window-index bytes for cbam_bwd(..., d_pooled=)."""
     l = _lib.lib()
-    xp, c, xpitch = _desc(x)
+    a = _act(x, "cbam_fwd: x")
     code = _cbam_storage(x, "cbam_fwd")
-    (w1, b1, w2, b2, wc, gamma, beta), cw, ch = _cbam_params(w1, b1, w2, b2, wc, gamma, beta)
-    if cw != c:
-        raise _lib.BratsHipError(f"cbam_fwd: the block is built for {cw} channels, the tensor has {c}")
-    n, d, h, w, _ = x.shape
-    v, dev, st = d * h * w, x.device, _stream()
+    (w1, b1, w2, b2, wc, gamma, beta), ch = _cbam_params(a, w1, b1, w2, b2, wc, gamma, beta, "cbam_fwd")
+    n, d, h, w, c = a.shape
+    v, dev, st, xp, xpitch = a.vox, a.device, _stream(), a.ptr, a.pitch
     nb, tiles = l.brats_cbam_blocks(code, c, d, h, w), l.brats_cbam_tiles(d, h, w)
     if nb <= 0:
         _lib.check(-2, "cbam_fwd")
     f32 = dict(dtype=torch.float32, device=dev)
-    if out is None:
-        out = new_act(n, d, h, w, c, x.dtype, dev)
-    optr, oc, opitch = _desc(out)
-    if oc != c or out.shape != x.shape or out.dtype != x.dtype:
-        raise _lib.BratsHipError("cbam_fwd: bad output tensor")
+    o = _out(out, a.shape, a, "cbam_fwd: out")
     sv = CbamSaved()
     sv.pooled, sv.scale = torch.empty((n, 2, c), **f32), torch.empty((n, c), **f32)
     sv.hidden, sv.argvox = torch.empty((n, 2, ch), **f32), torch.empty((n, c), dtype=torch.int32, device=dev)
@@ -1698,34 +1682,31 @@ def cbam_fwd(x, w1, b1, w2, b2, wc, gamma, beta, out=None, save=True, pool=False
     sv.cidx = torch.empty((n, v), dtype=torch.int16, device=dev) if save else None
     sv.pidx = None
     if pool:
-        if d % 2 or h % 2 or w % 2:
-            raise _lib.BratsHipError(f"cbam_fwd(pool=True): D, H, W = {d}, {h}, {w} must be even")
-        pooled = new_act(n, d // 2, h // 2, w // 2, c, x.dtype, dev)
-        pp, _, ppitch = _desc(pooled)
+        half = _even(a, "cbam_fwd(pool=True)")
+        pooled = torch.empty(half + (c,), dtype=a.dtype, device=dev)
         if save:
-            sv.pidx = torch.empty((n, d // 2, h // 2, w // 2, c), dtype=torch.uint8, device=dev)
+            sv.pidx = torch.empty(half + (c,), dtype=torch.uint8, device=dev)
     part = torch.empty(max(3 * nb * n * c, 3 * n * tiles), **f32)
     with _span("cbam_pool", code, n, c, d, h, w):
         _lib.check(l.brats_cbam_pool(xp, xpitch, part.data_ptr(), sv.pooled.data_ptr(), sv.argvox.data_ptr(), code, n, c, d, h, w, st), "cbam_pool")
     with _span("cbam_gate", code, n, c, d, h, w):
-        _lib.check(l.brats_cbam_gate(sv.pooled.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), sv.hidden.data_ptr(),
-                                     sv.scale.data_ptr(), n, c, ch, st), "cbam_gate")
+        _lib.check(l.brats_cbam_gate(sv.pooled.data_ptr(), w1, b1, w2, b2, sv.hidden.data_ptr(), sv.scale.data_ptr(), n, c, ch, st), "cbam_gate")
     with _span("cbam_compress", code, n, c, d, h, w):
         _lib.check(l.brats_cbam_compress(xp, xpitch, sv.scale.data_ptr(), sv.comp.data_ptr(), sv.cidx.data_ptr() if save else None, code, n, c,
                                          d, h, w, st), "cbam_compress")
     with _span("cbam_spatial", code, n, c, d, h, w):
-        _lib.check(l.brats_cbam_spatial(sv.comp.data_ptr(), wc.data_ptr(), sv.z.data_ptr(), part.data_ptr(), sv.stats.data_ptr(), CBAM_EPS, n,
+        _lib.check(l.brats_cbam_spatial(sv.comp.data_ptr(), wc, sv.z.data_ptr(), part.data_ptr(), sv.stats.data_ptr(), CBAM_EPS, n,
                                         d, h, w, st), "cbam_spatial")
     if pool:
         with _span("cbam_apply_pool", code, n, c, d, h, w):
-            _lib.check(l.brats_cbam_apply_pool(xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(),
-                                               beta.data_ptr(), optr, opitch, pp, ppitch, sv.pidx.data_ptr() if save else None, code, n, c,
-                                               d, h, w, st), "cbam_apply_pool")
-        return out, pooled, (sv if save else None)
+            _lib.check(l.brats_cbam_apply_pool(xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma, beta, o.ptr, o.pitch,
+                                               pooled.data_ptr(), c, sv.pidx.data_ptr() if save else None, code, n, c, d, h, w, st),
+                       "cbam_apply_pool")
+        return o.t, pooled, (sv if save else None)
     with _span("cbam_apply", code, n, c, d, h, w):
-        _lib.check(l.brats_cbam_apply(xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                      optr, opitch, code, n, c, d, h, w, st), "cbam_apply")
-    return out, (sv if save else None)
+        _lib.check(l.brats_cbam_apply(xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma, beta, o.ptr, o.pitch, code,
+                                      n, c, d, h, w, st), "cbam_apply")
+    return o.t, (sv if save else None)
 
 
 def cbam_bwd(dout, x, saved, w1, b1, w2, b2, wc, gamma, beta, d_pooled=None):
@@ -1736,25 +1717,24 @@ def cbam_bwd(dout, x, saved, w1, b1, w2, b2, wc, gamma, beta, d_pooled=None):
     arrives at `out` directly (the skip connection) or None, and the two dout-reading passes compose dout + maxpool2_bwd(d_pooled)
     on load (brats_cbam_bwd_reduce_pool / _bwd_apply_pool) -- bit-identical to maxpool2_bwd(out, d_pooled, dx_skip=dout) first."""
     l = _lib.lib()
-    xp, c, xpitch = _desc(x)
-    dp, dpitch = (None, 0) if dout is None else _desc(dout)[::2]
+    a = _act(x, "cbam_bwd: x")
     code = _cbam_storage(x, "cbam_bwd")
     if dout is None and d_pooled is None:
         raise _lib.BratsHipError("cbam_bwd: no gradient given")
-    if (dout is not None and (dout.shape != x.shape or dout.dtype != x.dtype)) or not isinstance(saved, CbamSaved) or saved.cidx is None:
+    if not isinstance(saved, CbamSaved) or saved.cidx is None:
         raise _lib.BratsHipError("cbam_bwd: dout must have x's shape and dtype, saved must come from cbam_fwd(save=True)")
+    g = _act2(dout, "cbam_bwd: dout", a)
+    if d_pooled is not None and saved.pidx is None:
+        raise _lib.BratsHipError("cbam_bwd: d_pooled must have the pooled tensor's shape and x's dtype, saved must come from "
+                                 "cbam_fwd(pool=True, save=True)")
+    (w1, b1, w2, b2, wc, gamma, beta), ch = _cbam_params(a, w1, b1, w2, b2, wc, gamma, beta, "cbam_bwd")
+    scale, pooled, hidden, argvox, comp, cidx, z, stats, pidx = _cbam_saved(saved, a, ch, "cbam_bwd", d_pooled is not None)
+    src = (g.ptr, g.pitch)
     if d_pooled is not None:
-        pooled_shape = (x.shape[0], x.shape[1] // 2, x.shape[2] // 2, x.shape[3] // 2, x.shape[4])
-        if saved.pidx is None or tuple(d_pooled.shape) != pooled_shape or d_pooled.dtype != x.dtype:
-            raise _lib.BratsHipError("cbam_bwd: d_pooled must have the pooled tensor's shape and x's dtype, saved must come from "
-                                     "cbam_fwd(pool=True, save=True)")
-        qp, _, qpitch = _desc(d_pooled)
-        pooled_src = (dp, dpitch, qp, qpitch, saved.pidx.data_ptr())
-    (w1, b1, w2, b2, wc, gamma, beta), cw, ch = _cbam_params(w1, b1, w2, b2, wc, gamma, beta)
-    n, d, h, w, _ = x.shape
-    if cw != c or tuple(saved.scale.shape) != (n, c) or tuple(saved.z.shape) != (n, d * h * w):
-        raise _lib.BratsHipError("cbam_bwd: saved tensors / parameters do not belong to this input")
-    v, dev, st, sv = d * h * w, x.device, _stream(), saved
+        q = _act(d_pooled, "cbam_bwd: d_pooled", a, shape=_even(a, "cbam_bwd(d_pooled=)") + (a.c,))
+        src += (q.ptr, q.pitch, pidx)
+    n, d, h, w, c = a.shape
+    v, dev, st, xp, xpitch = a.vox, a.device, _stream(), a.ptr, a.pitch
     nb, tiles = l.brats_cbam_blocks(code, c, d, h, w), l.brats_cbam_tiles(d, h, w)
     f32 = dict(dtype=torch.float32, device=dev)
     dzn, dcomp = torch.empty((n, v), **f32), torch.empty((n, 2, v), **f32)
@@ -1763,31 +1743,25 @@ def cbam_bwd(dout, x, saved, w1, b1, w2, b2, wc, gamma, beta, d_pooled=None):
     part = torch.empty(max(nb * n * (c + 2), n * tiles * 686), **f32)
     dw1, db1_, dw2, db2_ = torch.empty((ch, c), **f32), torch.empty((ch,), **f32), torch.empty((c, ch), **f32), torch.empty((c,), **f32)
     dwc, dgamma, dbeta = torch.empty((1, 2, 7, 7, 7), **f32), torch.empty((1,), **f32), torch.empty((1,), **f32)
-    dx = new_act(n, d, h, w, c, x.dtype, dev)
-    dxp, _, dxpitch = _desc(dx)
+    dx = new_act(n, d, h, w, c, a.dtype, dev)
     # (the pooled forms take (d_skip, pitch, d_pooled, pitch, window indices) where the plain ones take (dout, pitch))
-    reduce, apply, src = (("cbam_bwd_reduce", "cbam_bwd_apply", (dp, dpitch)) if d_pooled is None else
-                          ("cbam_bwd_reduce_pool", "cbam_bwd_apply_pool", pooled_src))
+    reduce, apply = ("cbam_bwd_reduce", "cbam_bwd_apply") if d_pooled is None else ("cbam_bwd_reduce_pool", "cbam_bwd_apply_pool")
     with _span(reduce, code, n, c, d, h, w):
-        _lib.check(getattr(l, "brats_" + reduce)(*src, xp, xpitch, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(),
-                                                 beta.data_ptr(), dzn.data_ptr(), part.data_ptr(), asum.data_ptr(), s12.data_ptr(), code, n,
-                                                 c, d, h, w, st), reduce)
+        _lib.check(getattr(l, "brats_" + reduce)(*src, xp, xpitch, scale, z, stats, gamma, beta, dzn.data_ptr(), part.data_ptr(), asum.data_ptr(),
+                                                 s12.data_ptr(), code, n, c, d, h, w, st), reduce)
     with _span("cbam_bwd_spatial", code, n, c, d, h, w):
-        _lib.check(l.brats_cbam_bwd_spatial(dzn.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), s12.data_ptr(), gamma.data_ptr(),
-                                            sv.comp.data_ptr(), wc.data_ptr(), dcomp.data_ptr(), part.data_ptr(), dwc.data_ptr(), n, d, h, w, st),
-                   "cbam_bwd_spatial")
+        _lib.check(l.brats_cbam_bwd_spatial(dzn.data_ptr(), z, stats, s12.data_ptr(), gamma, comp, wc, dcomp.data_ptr(), part.data_ptr(),
+                                            dwc.data_ptr(), n, d, h, w, st), "cbam_bwd_spatial")
     with _span("cbam_bwd_chan", code, n, c, d, h, w):
-        _lib.check(l.brats_cbam_bwd_chan(xp, xpitch, dcomp.data_ptr(), sv.cidx.data_ptr(), part.data_ptr(), rsum.data_ptr(), code, n, c, d, h, w,
-                                         st), "cbam_bwd_chan")
+        _lib.check(l.brats_cbam_bwd_chan(xp, xpitch, dcomp.data_ptr(), cidx, part.data_ptr(), rsum.data_ptr(), code, n, c, d, h, w, st),
+                   "cbam_bwd_chan")
     with _span("cbam_bwd_gate", code, n, c, d, h, w):
-        _lib.check(l.brats_cbam_bwd_gate(asum.data_ptr(), rsum.data_ptr(), sv.pooled.data_ptr(), sv.hidden.data_ptr(), w1.data_ptr(),
-                                         b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), s12.data_ptr(), tmp.data_ptr(), dpool.data_ptr(), dw1.data_ptr(),
-                                         db1_.data_ptr(), dw2.data_ptr(), db2_.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), n, c, ch, st),
-                   "cbam_bwd_gate")
+        _lib.check(l.brats_cbam_bwd_gate(asum.data_ptr(), rsum.data_ptr(), pooled, hidden, w1, b1, w2, b2, s12.data_ptr(), tmp.data_ptr(),
+                                         dpool.data_ptr(), dw1.data_ptr(), db1_.data_ptr(), dw2.data_ptr(), db2_.data_ptr(), dgamma.data_ptr(),
+                                         dbeta.data_ptr(), n, c, ch, st), "cbam_bwd_gate")
     with _span(apply, code, n, c, d, h, w):
-        _lib.check(getattr(l, "brats_" + apply)(*src, sv.scale.data_ptr(), sv.z.data_ptr(), sv.stats.data_ptr(), gamma.data_ptr(),
-                                                beta.data_ptr(), dcomp.data_ptr(), sv.cidx.data_ptr(), dpool.data_ptr(), sv.argvox.data_ptr(),
-                                                dxp, dxpitch, code, n, c, d, h, w, st), apply)
+        _lib.check(getattr(l, "brats_" + apply)(*src, scale, z, stats, gamma, beta, dcomp.data_ptr(), cidx, dpool.data_ptr(), argvox,
+                                                dx.data_ptr(), c, code, n, c, d, h, w, st), apply)
     return dx, dw1, db1_, dw2, db2_, dwc, dgamma, dbeta
 
 
@@ -1798,7 +1772,7 @@ class RrcnnSaved:
     __slots__ = ("x", "x2", "S", "Y", "ss", "mr", "groups", "act", "t", "n")
 
 
-def _rrcnn_params(params):
+def _rrcnn_params(params, like):
     ps = [p.detach() for p in params]
     if len(ps) != 10:
         raise _lib.BratsHipError("rrcnn: ten parameters in the block's state-dict order (RCNN.0.conv.0.weight .. Conv_1x1.bias)")
@@ -1808,8 +1782,30 @@ def _rrcnn_params(params):
     if not ok:
         raise _lib.BratsHipError("rrcnn: parameter shapes do not belong to one RRCNNblock")
     for p in ps:
-        _f32(p.contiguous())
-    return [p.contiguous() for p in ps], c, ps[8].shape[1]
+        _vec(p, None, "rrcnn: parameter", like)
+    return ps, c, ps[8].shape[1]
+
+
+def _rrcnn_saved(sv, c, cin, dout):
+    """Every field of an RrcnnSaved checked against the block input's n and extent, the block's c, cin and t: -> the _Act of dout."""
+    if not isinstance(sv, RrcnnSaved) or not sv.S:
+        raise _lib.BratsHipError("rrcnn_bwd: saved must come from rrcnn_fwd(save=True)")
+    a = _act(sv.x, "rrcnn_bwd: saved.x")
+    a2 = _act2(sv.x2, "rrcnn_bwd: saved.x2", a, anyc=True)
+    n, t = a.n, sv.t
+    if ((a.c + a2.c != cin if a2.t is not None else a.c < cin) or sv.n != n or t < 1 or c % sv.groups
+            or [len(v) for v in (sv.S, sv.Y, sv.ss, sv.mr)] != [2] * 4):
+        raise _lib.BratsHipError("rrcnn_bwd: saved does not belong to this block")
+    g = _act(dout, "rrcnn_bwd: dout", a, shape=a.shape[:4] + (c,))
+    for b in (0, 1):
+        for buf in (sv.S[b], sv.Y[b]):
+            _act(buf, "rrcnn_bwd: saved.S / saved.Y", a, shape=((t + 1) * n,) + a.shape[1:4] + (c,))
+        if len(sv.ss[b]) != t + 1 or len(sv.mr[b]) != t + 1:
+            raise _lib.BratsHipError("rrcnn_bwd: saved holds other than t + 1 applications")
+        for ss, mr in zip(sv.ss[b], sv.mr[b]):
+            _vec(ss, n * c * 2, "rrcnn_bwd: saved.ss", a)
+            _vec(mr, n * sv.groups * 2, "rrcnn_bwd: saved.mr", a)
+    return g
 
 
 def rrcnn_fwd(x, x2, params, groups=8, act="relu", t=2, save=True):
@@ -1825,12 +1821,12 @@ def rrcnn_fwd(x, x2, params, groups=8, act="relu", t=2, save=True):
     four activation buffers are reused throughout, saved is None."""
     if x3_active():
         raise NotImplementedError("rrcnn_fwd: the split-precision modes are not built for the recurrent block")
-    ps, c, cin = _rrcnn_params(params)
+    a, a2 = _conv_sources(x, x2, "rrcnn_fwd")
+    ps, c, cin = _rrcnn_params(params, a)
     if t < 1:
         raise _lib.BratsHipError(f"rrcnn_fwd: t = {t} (t >= 1)")
-    n, d, h, w, c1 = x.shape
-    c2 = x2.shape[-1] if x2 is not None else 0
-    if (x2 is not None and (c1 + c2 != cin or x2.dtype != x.dtype or x2.shape[:4] != x.shape[:4])) or (x2 is None and c1 < cin):
+    (n, d, h, w, c1), c2 = a.shape, a2.c
+    if (x2 is not None and c1 + c2 != cin) or (x2 is None and c1 < cin):
         raise _lib.BratsHipError(f"rrcnn_fwd: the block is built for {cin} input channels, the tensors have {c1} + {c2}")
     if c % groups:
         raise _lib.BratsHipError(f"rrcnn_fwd: {c} channels in {groups} groups")
@@ -1886,11 +1882,10 @@ def rrcnn_bwd(dout, saved, params, need_dx=True):
         raise _lib.BratsHipError("rrcnn_bwd: saved must come from rrcnn_fwd(save=True)")
     if x3_active():
         raise NotImplementedError("rrcnn_bwd: the split-precision modes are not built for the recurrent block")
-    ps, c, cin = _rrcnn_params(params)
+    ps, c, cin = _rrcnn_params(params, sv.x)
+    _rrcnn_saved(sv, c, cin, dout)
     n, t, x, x2 = sv.n, sv.t, sv.x, sv.x2
     dtype = x.dtype
-    if dout.dtype != dtype or tuple(dout.shape) != tuple(sv.S[0][:n].shape):
-        raise _lib.BratsHipError("rrcnn_bwd: dout must have the output's shape and the block's storage type")
     grads = [None] * 10
     dz = dout
     for b in (1, 0):

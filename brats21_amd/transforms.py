@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._tensors import _vec
 from .tta.base import SignedPerm
 
 
@@ -102,7 +103,7 @@ def gamma_noise(x, gamma=None, noise=None):
         mn, rg = float(lo), float(hi - lo)
     nz = _need(noise, "gamma_noise") if noise is not None else None
     _lib.check(_lib.lib().brats_gamma_noise(x.data_ptr(), out.data_ptr(), x.numel(), mn, rg, float(gamma) if gamma is not None else 0.0,
-                                            nz.data_ptr() if nz is not None else None, _stream()), "gamma_noise")
+                                            _vec(nz, x.numel(), "gamma_noise: noise", x, null=True), _stream()), "gamma_noise")
     return out
 
 

@@ -1,11 +1,14 @@
-"""Library call trace of the two network programs: for each configuration, every libbrats_hip entry-point call of two training
+"""Library call trace of the network programs, the stand-alone blocks and the criteria: for each network configuration, every libbrats_hip entry-point call of two training
 steps (engine.TrainStep, deep supervision on; the second step is the one that runs on a pack plan / DDP bucket slices) and of
 two no_grad eval forwards (the second one hits the packed-weight and BCNorm fold caches), followed by a sha256 of the losses,
-every parameter gradient and the eval logits.  A call is written as its name, its arguments -- pointers as 0 (null) or 1,
+every parameter gradient and the eval logits; for a block (networks.RRCNNblock, networks.CBAM) one forward + backward, for a
+criterion of losses.py one loss + gradient at 32^3.  A call is written as its name, its arguments -- pointers as 0 (null) or 1,
 integers and floats verbatim; kinds from _lib._parse_header() -- and its return value.  Two trees compute the same thing the same
 way when their outputs are identical:
 
     python scripts/call_trace.py OUT.txt [--tree OTHER_CHECKOUT] [--only REGEX] [--no-full]
+    python scripts/call_trace.py OUT.txt --digest        (no GPU: lines and sha256 per configuration of an existing OUT.txt, the
+                                                           form small enough to commit under profiles/)
 """
 import argparse, contextlib, hashlib, io, re, sys, warnings
 
@@ -14,7 +17,14 @@ ap.add_argument("out")
 ap.add_argument("--tree", default=".", help="the checkout whose brats21_amd is traced")
 ap.add_argument("--only", default=None, help="run the configurations whose name matches")
 ap.add_argument("--no-full", action="store_true", help="skip the 128^3 case")
+ap.add_argument("--digest", action="store_true", help="print the per-configuration digest of the existing output file")
 args = ap.parse_args()
+if args.digest:
+    txt = open(args.out).read()
+    print(f"whole file: {txt.count(chr(10))} lines sha256 {hashlib.sha256(txt.encode()).hexdigest()}")
+    for sec in txt.split("==== ")[1:]:
+        print(f"{sec.split(chr(10), 1)[0]}: {sec.count(chr(10))} lines sha256 {hashlib.sha256(sec.encode()).hexdigest()}")
+    sys.exit(0)
 sys.path.insert(0, args.tree)
 
 import torch
@@ -48,6 +58,11 @@ def sha(t):
     return hashlib.sha256(t.detach().float().cpu().contiguous().numpy().tobytes()).hexdigest()
 
 
+def flat(o):
+    """The tensors of a (nested) tuple / list of outputs, in order."""
+    return [o] if torch.is_tensor(o) else [t for e in o for t in flat(e)]
+
+
 def run(name, model, width, size=32, precision="bf16", norm="group", act="relu", dropout=0, buckets=False, **attrs):
     if args.only and not re.search(args.only, name):
         return
@@ -56,7 +71,11 @@ def run(name, model, width, size=32, precision="bf16", norm="group", act="relu",
     ns = argparse.Namespace(model=model, width=width, norm=norm, act=act, num_classes=3, dropout=dropout)
     with contextlib.redirect_stdout(io.StringIO()), warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        m = get_model(ns).to(dev).train()
+        if model == "att_equiunet":  # (not in the factory: built like the factory builds EquiUnet)
+            from brats21_amd.networks import AttEquiUnet
+            m = AttEquiUnet(4, 3, [width * 2 ** i for i in range(4)], norm, act, deep_supervision=True, dropout=dropout).to(dev).train()
+        else:
+            m = get_model(ns).to(dev).train()
     m.precision = precision
     for k, v in attrs.items():
         assert hasattr(m, k), k
@@ -76,11 +95,46 @@ def run(name, model, width, size=32, precision="bf16", norm="group", act="relu",
         with torch.no_grad():
             logits = m(x)
         out += [f"-- eval forward {i}"] + LOG[:]
-        out += [f"logits {sha(o)}" for o in ([logits[0]] + list(logits[1]) if isinstance(logits, tuple) else [logits])]
+        out += [f"logits {sha(o)}" for o in flat(logits)]
     torch.cuda.synchronize()
     with open(args.out, "a") as f:
         f.write("\n".join(out) + "\n")
     print(f"{name}: {len(out)} lines", flush=True)
+
+
+def traced(name, fn):
+    """One stand-alone piece: fn() -> tensors to hash; its calls and hashes go to the output like a network's."""
+    if args.only and not re.search(args.only, name):
+        return
+    torch.manual_seed(0)
+    del LOG[:]
+    res = fn()
+    torch.cuda.synchronize()
+    out = [f"==== {name}"] + LOG[:] + [f"result {i} {sha(t) if t is not None else None}" for i, t in enumerate(res)]
+    with open(args.out, "a") as f:
+        f.write("\n".join(out) + "\n")
+    print(f"{name}: {len(out)} lines", flush=True)
+
+
+def block(make, cin, size=16):
+    """forward + backward of an nn.Module block on an NCDHW input: -> (output, input gradient, parameter gradients)."""
+    dev = torch.device("cuda:0")
+    m = make().to(dev).train()
+    x = synth.random_image(2, cin, (size,) * 3, seed=1, device=dev).requires_grad_(True)
+    y = m(x)
+    y.backward(torch.ones_like(y) / y.numel())
+    return [y, x.grad] + [p.grad for p in m.parameters()]
+
+
+def criterion(make, boundary=False, labels=False):
+    from brats21_amd import transforms
+    dev = torch.device("cuda:0")
+    t = synth.nested_spheres(2, (32,) * 3, device=dev)
+    x = (synth.random_image(2, 3, (32,) * 3, seed=2, device=dev) * 3).requires_grad_(True)
+    target = [t, transforms.one_hot_to_dist(t)] if boundary else (t.sum(1, keepdim=True) if labels else t)
+    loss = make()(x, target)
+    loss.backward()
+    return [loss, x.grad]
 
 
 _lib._lib = _Recorder(_lib.lib())
@@ -103,3 +157,24 @@ for norm in ("group", "instance", "batch", "bcn"):
 run("equiunet-16-bf16-norm_on_load=False", "equiunet", 16, norm_on_load=False)
 if not args.no_full:  # the only shape that takes the 256 MiB affine_act_pool branch
     run("equiunet-48-bf16-128", "equiunet", 48, size=128)
+for prec in ("bf16", "fp32"):
+    run(f"modified_unet-16-{prec}", "modified_unet", 16, precision=prec)
+    run(f"att_equiunet-16-{prec}", "att_equiunet", 16, precision=prec, norm="instance")
+    run(f"equiunet_ref-16-{prec}", "equiunet_ref", 16, precision=prec)
+from brats21_amd import losses
+from brats21_amd.networks import CBAM, RRCNNblock
+for norm, act in (("group", "relu"), ("instance", "leakyrelu")):
+    traced(f"RRCNNblock-{norm}-{act}", lambda: block(lambda: RRCNNblock(8, 16, norm, act, 2), 8))
+traced("CBAM-16", lambda: block(lambda: CBAM(16), 16))
+_IDC, _SIG = [0, 1, 2], dict(include_background=True, sigmoid=True, softmax=False, squared_pred=True, reduction="mean")
+for name, make, kw in (
+        ("dice", lambda: losses.DiceLoss(), {}), ("jaccard", lambda: losses.DiceLoss(jaccard=True), {}),
+        ("hd", lambda: losses.HausdorffLoss(_IDC, alpha=2, sigmoid=True), {}),
+        ("boundary", lambda: losses.BoundaryLoss(_IDC, sigmoid=True), dict(boundary=True)),
+        ("dice_hd", lambda: losses.DiceHDLoss(idc_hd=_IDC, alpha_hd=2, hybrid=False, weight_hd=0.5, weight_dice=0.5, **_SIG), {}),
+        ("dice_boundary", lambda: losses.DiceBoundaryLoss(idc_boundary=_IDC, **_SIG), dict(boundary=True)),
+        ("softmax_dice_ce", lambda: losses.SoftmaxDiceCELoss(), dict(labels=True)),
+        ("dice_ce", lambda: losses.DiceCELoss(batch=True, **_SIG), {}), ("dice_focal", lambda: losses.DiceFocalLoss(batch=False, **_SIG), {}),
+        ("focal", lambda: losses.FocalLoss(gamma=2.0, reduction="mean"), {}),
+        ("tversky", lambda: losses.TverskyLoss(include_background=True, sigmoid=True, softmax=False, alpha=0.5, beta=0.5, reduction="mean"), {})):
+    traced(f"criterion-{name}", lambda: criterion(make, **kw))
