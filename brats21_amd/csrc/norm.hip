@@ -522,11 +522,15 @@ template <> struct Raw16<float> {
 // mean in the same order: bit-identical to brats_affine_act_fwd + brats_maxpool2_fwd.  relu / leakyrelu.
 // (A first form gave a thread the whole window: its stores were 96-byte pieces at a 192-byte stride -- half-written lines
 // under the non-temporal hint -- and the fused pass was SLOWER than the two it replaced, 254 against 148 + 85 us.)
-template <typename T, bool NT = false, bool AM = false>
+// ADD: z = add + act(y*scale + shift), the last pass of an RRCNN block that ends an encoder level (brats_affine_act_add_pool_fwd):
+// the activation is rounded to T first, added to `add` in f32 and rounded once (affine_act_add_kernel's rule), and the pooling
+// half sees that stored sum.  Four more loads per item, everything else is the same walk.
+template <typename T, bool NT = false, bool AM = false, bool ADD = false>
 __global__ void __launch_bounds__(256) affine_act_pool_kernel(const T* __restrict__ y, int ypitch, const float* __restrict__ scale_shift,
-                                                              T* __restrict__ z, int zpitch, T* __restrict__ p, int ppitch, int act,
-                                                              SlopeArg sl, int D, int H, int W, int C, int with_avg,
-                                                              uint32_t* __restrict__ amax, uint8_t* __restrict__ argmax) {
+                                                              const T* __restrict__ add, int addpitch, T* __restrict__ z, int zpitch,
+                                                              T* __restrict__ p, int ppitch, int act, SlopeArg sl, int D, int H, int W,
+                                                              int C, int with_avg, uint32_t* __restrict__ amax,
+                                                              uint8_t* __restrict__ argmax) {
   constexpr int VW = 16 / sizeof(T);
   typedef typename Raw16<T>::type raw_t;
   extern __shared__ __attribute__((aligned(16))) char pool_lds[];  // [2][blockDim.x][4] raw_t
@@ -549,6 +553,7 @@ __global__ void __launch_bounds__(256) affine_act_pool_kernel(const T* __restric
     sh[j] = lane_on ? scale_shift[((size_t)n * C + c0 + j) * 2 + 1] : 0.f;
   }
   const T* yb = y + (size_t)n * voxels * ypitch + c0;
+  const T* ab = ADD ? add + (size_t)n * voxels * addpitch + c0 : nullptr;
   T* zb = z + (size_t)n * voxels * zpitch + c0;
   T* pb = p + (size_t)n * Do * Ho * Wo * ppitch + c0;
   float amx = 0.f;
@@ -561,12 +566,13 @@ __global__ void __launch_bounds__(256) affine_act_pool_kernel(const T* __restric
     const bool on = lane_on && x < W;
     raw_t mine[4];
     if (on) {
-      raw_t raw[4];
+      raw_t raw[4], rawadd[ADD ? 4 : 1];
       size_t vox[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {  // k = (dz, dy)
         vox[k] = ((size_t)(2 * zo + (k >> 1)) * H + (2 * yo + (k & 1))) * W + x;
         raw[k] = Raw16<T>::template load<NT>(yb + vox[k] * ypitch);
+        if constexpr (ADD) rawadd[k] = Raw16<T>::template load<NT>(ab + vox[k] * addpitch);
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -578,6 +584,12 @@ __global__ void __launch_bounds__(256) affine_act_pool_kernel(const T* __restric
           const float neg = relu ? 0.f : pre * slope;
           a[j] = pre > 0.f ? pre : neg;
         }
+        if constexpr (ADD) {
+          float r[VW];
+          Raw16<T>::unpack(rawadd[k], r);
+#pragma unroll
+          for (int j = 0; j < VW; ++j) a[j] = to_f<T>(from_f<T>(a[j])) + r[j];  // the activation as stored, then one f32 add
+        }
         vstore<T, VW, NT>(zb + vox[k] * zpitch, a);
         // the values as stored, packed: what the pooling half reads (its own and its neighbour's)
         if constexpr (std::is_same<T, float>::value) {
@@ -586,7 +598,7 @@ __global__ void __launch_bounds__(256) affine_act_pool_kernel(const T* __restric
 #pragma unroll
           for (int q = 0; q < 4; ++q) mine[k][q] = pack2(a[2 * q], a[2 * q + 1]);
         }
-        if (amax) {
+        if (!ADD && amax) {  // (the residual form records no |max| and writes no mean: both fold away)
           float r[VW];
           Raw16<T>::unpack(mine[k], r);
 #pragma unroll
@@ -615,7 +627,7 @@ __global__ void __launch_bounds__(256) affine_act_pool_kernel(const T* __restric
             mx[j] = (a[j] > mx[j] || a[j] != a[j]) ? a[j] : mx[j];
             mx[j] = (b[j] > mx[j] || b[j] != b[j]) ? b[j] : mx[j];
           }
-          sm[j] = (sm[j] + a[j]) + b[j];
+          if constexpr (!ADD) sm[j] = (sm[j] + a[j]) + b[j];
         }
       }
       const size_t pvox = ((size_t)zo * Ho + yo) * Wo + (x >> 1);
@@ -629,14 +641,42 @@ __global__ void __launch_bounds__(256) affine_act_pool_kernel(const T* __restric
         for (int q = 0; q < VW / 4; ++q) ap[q] = w[q];
       }
       Vec<T, VW>::store(po, mx);
-      if (with_avg) {
+      if (!ADD && with_avg) {
 #pragma unroll
         for (int j = 0; j < VW; ++j) sm[j] *= 0.125f;
         Vec<T, VW>::store(po + C, sm);
       }
     }
   }
-  if (amax) record_absmax<T>(amx, amax);
+  if (!ADD && amax) record_absmax<T>(amx, amax);
+}
+
+// x positions per item of affine_act_pool_kernel; below 2 a block holds no pooling pair
+static inline int pool_walk_xb(int vw, int W, int C) {
+  const int xb = (256 / (C / vw)) & ~1;
+  return xb > W ? W : xb;
+}
+// both forms of the walk: add == nullptr is the plain pass, otherwise the residual form (no mean, no |max|)
+static int affine_act_pool_launch(const void* y, int ypitch, const float* scale_shift, const void* add, int addpitch, void* z, int zpitch,
+                                  void* pooled, int ppitch, unsigned char* argmax, int dtype, int act, SlopeArg slope, int N, int D,
+                                  int H, int W, int C, int with_avg, float* amax, hipStream_t s) {
+  const int xb = pool_walk_xb(vec_width(dtype), W, C);
+  const size_t items = (size_t)(D / 2) * (H / 2) * ((W + xb - 1) / xb);
+  const bool big = big_tensor16(dtype, (size_t)N * D * H * W * C);
+  dim3 grid(stream_grid(items, 1, big ? 8192 : 2048), N);
+  const size_t lds = (size_t)2 * 256 * 4 * 16;
+  with_stream16(dtype, big, [&](auto t, auto nt) {
+    with_flag(argmax != nullptr, [&](auto am) {
+      with_flag(add != nullptr, [&](auto ad) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((affine_act_pool_kernel<T, decltype(nt)::value, decltype(am)::value, decltype(ad)::value>), grid, dim3(256),
+                           lds, s, (const T*)y, ypitch, scale_shift, (const T*)add, addpitch, (T*)z, zpitch, (T*)pooled, ppitch, act,
+                           slope, D, H, W, C, with_avg, (uint32_t*)amax, argmax);
+      });
+    });
+  });
+  BRATS_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int BRATS_API(brats_affine_act_pool_fwd)(const void* y, int ypitch, const float* scale_shift, void* z, int zpitch, void* pooled,
@@ -648,23 +688,30 @@ extern "C" int BRATS_API(brats_affine_act_pool_fwd)(const void* y, int ypitch, c
   if (!y || !z || !pooled || !scale_shift || C % vw || ypitch % vw || zpitch % vw || ppitch % vw || C / vw > 256 || ((D | H | W) & 1))
     BRATS_FAIL(BRATS_E_ARG, "affine_act_pool_fwd: C / pitches multiples of %d (C <= %d), even spatial dims", vw, 256 * vw);
   if (act > BRATS_ACT_LEAKY) BRATS_FAIL(BRATS_E_UNSUPPORTED, "affine_act_pool_fwd: relu / leakyrelu only (act=%d)", act);
-  int xb = (256 / (C / vw)) & ~1;
-  if (xb < 2) BRATS_FAIL(BRATS_E_UNSUPPORTED, "affine_act_pool_fwd: C=%d leaves no pooling pair per block", C);
-  if (xb > W) xb = W;
-  const size_t items = (size_t)(D / 2) * (H / 2) * ((W + xb - 1) / xb);
-  const bool big = big_tensor16(dtype, (size_t)N * D * H * W * C);
-  dim3 grid(stream_grid(items, 1, big ? 8192 : 2048), N);
-  const size_t lds = (size_t)2 * 256 * 4 * 16;
-  with_stream16(dtype, big, [&](auto t, auto nt) {
-    with_flag(argmax != nullptr, [&](auto am) {
-      using T = typename decltype(t)::type;
-      hipLaunchKernelGGL((affine_act_pool_kernel<T, decltype(nt)::value, decltype(am)::value>), grid, dim3(256), lds, (hipStream_t)s,
-                         (const T*)y, ypitch, scale_shift, (T*)z, zpitch, (T*)pooled, ppitch, act, slope, D, H, W, C, with_avg,
-                         (uint32_t*)amax, argmax);
-    });
-  });
-  BRATS_CHECK_LAUNCH();
-  return 0;
+  if (pool_walk_xb(vw, W, C) < 2) BRATS_FAIL(BRATS_E_UNSUPPORTED, "affine_act_pool_fwd: C=%d leaves no pooling pair per block", C);
+  return affine_act_pool_launch(y, ypitch, scale_shift, nullptr, 0, z, zpitch, pooled, ppitch, argmax, dtype, act, slope, N, D, H, W, C,
+                                with_avg, amax, (hipStream_t)s);
+}
+
+// s = add + act(y*scale + shift) AND pooled = maxpool2(s): the last normalise pass of an R2U-Net encoder block
+// (networks/unet_family.py:270-283: x_k = RRCNN_k(.), then Maxpool(x_k)).  3.125 activations move where brats_affine_act_add_fwd +
+// brats_maxpool2_fwd move 4.125.
+extern "C" int BRATS_API(brats_affine_act_add_pool_fwd)(const void* y, int ypitch, const float* scale_shift, const void* add, int addpitch,
+                                                        void* s, int spitch, void* pooled, int ppitch, unsigned char* argmax, int dtype,
+                                                        int act, float slope_value, const float* slope_dev, int N, int D, int H, int W,
+                                                        int C, brats_stream_t st) {
+  const SlopeArg slope{slope_value, slope_dev};
+  const int vw = vec_width(dtype);
+  if (!y || !add || !s || !pooled || !scale_shift) BRATS_FAIL(BRATS_E_ARG, "affine_act_add_pool_fwd: null pointer");
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || C % vw || ypitch % vw || addpitch % vw || spitch % vw || ppitch % vw ||
+      C / vw > 256 || ypitch < C || addpitch < C || spitch < C || ppitch < C)
+    BRATS_FAIL(BRATS_E_ARG, "affine_act_add_pool_fwd: C and pitches must be multiples of %d (C <= %d, pitch >= C)", vw, 256 * vw);
+  if ((D | H | W) & 1) BRATS_FAIL(BRATS_E_ARG, "affine_act_add_pool_fwd: D, H, W = %d, %d, %d must be even", D, H, W);
+  if (act != BRATS_ACT_RELU && act != BRATS_ACT_LEAKY)
+    BRATS_FAIL(BRATS_E_UNSUPPORTED, "affine_act_add_pool_fwd: relu / leakyrelu only (act=%d)", act);
+  if (pool_walk_xb(vw, W, C) < 2) BRATS_FAIL(BRATS_E_UNSUPPORTED, "affine_act_add_pool_fwd: C=%d leaves no pooling pair per block", C);
+  return affine_act_pool_launch(y, ypitch, scale_shift, add, addpitch, s, spitch, pooled, ppitch, argmax, dtype, act, slope, N, D, H, W,
+                                C, 0, nullptr, (hipStream_t)st);
 }
 
 // ---- backward of z = act(GN(y)) ----------------------------------------------------------------

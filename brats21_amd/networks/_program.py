@@ -273,8 +273,9 @@ def input_cpad(inplanes, dtype):
     return next(c for c in cands if c >= inplanes)
 
 
-def _fn_forward(program, ctx, model, x, dtype, params):
-    """forward() of a network's autograd Function around its forward program(ctx, cx, x0) -> tuple of logits."""
+def _fn_forward(program, ctx, model, x, dtype, params, cpad=None):
+    """forward() of a network's autograd Function around its forward program(ctx, cx, x0) -> tuple of logits.  cpad: the channels
+    the network input is zero-padded to where the program wants other than input_cpad's."""
     # training: the module packed all layers' weights up front (ops.plan_for); pack_weights() then returns views
     ctx.plan = ops._PLANS.get(model) if (model.training and model.pack_plan) else None
     ctx.x3 = model._x3_modes() if dtype == torch.float32 else (None, None)
@@ -282,7 +283,7 @@ def _fn_forward(program, ctx, model, x, dtype, params):
     with ops.use_plan(ctx.plan), ops.split_precision(ctx.x3[0]):
         ctx.cx = cx = _Ctx(model, dtype, will_bwd=any(ctx.needs_input_grad) and model._fwd_grad)  # (needs_input_grad ignores no_grad)
         cx.start_dropout(x.device)
-        x0 = ops.ncdhw_to_ndhwc(x, dtype, cpad=input_cpad(x.shape[1], dtype))
+        x0 = ops.ncdhw_to_ndhwc(x, dtype, cpad=cpad or input_cpad(x.shape[1], dtype))
         x0._net_input = True  # (un-normalised: never an e4m3 operand, whatever its padded width)
         if ops.x3_mode() == ops.X3F:
             # fp16 pairs overflow at |x| >= 65504 (hi = inf, lo = NaN: silently NaN logits).  Every other convolution

@@ -734,18 +734,60 @@ def affine_act(y, scale_shift, act="relu", out=None, slope=0.01, amax=None, slop
     return o.t
 
 
-def affine_act_add(y, scale_shift, add, act="relu", out=None, slope=0.01, slope_t=None):
+def _overlap(a, b):
+    """Do two _Acts of one storage type share memory?  Disjoint channel slices of one buffer (same pitch) do not; views whose
+    address ranges meet in any other way count as overlapping."""
+    es = a.t.element_size()
+    alo, blo = a.ptr, b.ptr
+    ahi, bhi = (p.ptr + ((p.n * p.vox - 1) * p.pitch + p.c) * es for p in (a, b))
+    if not (alo < bhi and blo < ahi):
+        return False
+    if a.pitch != b.pitch or (blo - alo) % es:
+        return True
+    d = ((blo - alo) // es) % a.pitch  # b's first channel, counted from a's, inside a voxel of the shared buffer
+    return d < a.c or d + b.c > a.pitch
+
+
+def _pool_fused_ok(a, act):
+    """Is brats_affine_act_add_pool_fwd built for the activation a?  relu / leakyrelu, and a pooling pair per block: at most 128
+    channel vectors of 16 bytes."""
+    return act in ("relu", "leakyrelu") and a.c * a.t.element_size() // 16 <= 128
+
+
+def affine_act_add(y, scale_shift, add, act="relu", out=None, slope=0.01, slope_t=None, pool=False, want_argmax=False):
     """out = add + act(y * scale + shift) in one pass (include/brats_hip.h: brats_affine_act_add_fwd): bit-identical to
     affine_act(y, ...) followed by an elementwise add of the two stored tensors.  add / out may be channel-slice views; out must
-    not overlap y or add."""
+    not overlap y or add.
+    pool=True -> (out, pooled) with pooled = maxpool2(out), written by the same pass (brats_affine_act_add_pool_fwd) where that is
+    built -- relu / leakyrelu, up to 128 channel vectors -- and by maxpool2 behind the plain pass elsewhere: the same bits.
+    want_argmax: out._pool_argmax = the uint8 window index of every pooled element, which maxpool2_bwd(out, ...) reads."""
     a = _act(y, "affine_act_add: y")
     b = _act(add, "affine_act_add: add", a)
     o = _out(out, a.shape, a, "affine_act_add: out")
-    _lib.check(_lib.lib().brats_affine_act_add_fwd(a.ptr, a.pitch, _vec(scale_shift, a.n * a.c * 2, "affine_act_add: scale_shift", a), b.ptr,
-                                                   b.pitch, o.ptr, o.pitch, a.code, ACTS[act], slope,
-                                                   _vec(slope_t, 1, "affine_act_add: slope_t", a, null=True), a.n, a.vox, a.c, _stream()),
-               "affine_act_add_fwd")
-    return o.t
+    ss = _vec(scale_shift, a.n * a.c * 2, "affine_act_add: scale_shift", a)
+    sl = _vec(slope_t, 1, "affine_act_add: slope_t", a, null=True)
+    if not pool:
+        if want_argmax:
+            raise _lib.BratsHipError("affine_act_add: want_argmax needs pool=True")
+        _lib.check(_lib.lib().brats_affine_act_add_fwd(a.ptr, a.pitch, ss, b.ptr, b.pitch, o.ptr, o.pitch, a.code, ACTS[act], slope, sl,
+                                                       a.n, a.vox, a.c, _stream()), "affine_act_add_fwd")
+        return o.t
+    half = _even(a, "affine_act_add(pool=True)")
+    for src, what in ((a, "y"), (b, "add")):
+        if _overlap(o, src):
+            raise _lib.BratsHipError(f"affine_act_add(pool=True): out overlaps {what}")
+    if not _pool_fused_ok(a, act):
+        _lib.check(_lib.lib().brats_affine_act_add_fwd(a.ptr, a.pitch, ss, b.ptr, b.pitch, o.ptr, o.pitch, a.code, ACTS[act], slope, sl,
+                                                       a.n, a.vox, a.c, _stream()), "affine_act_add_fwd")
+        return o.t, maxpool2(o.t, want_argmax=want_argmax)
+    pooled = torch.empty(half + (a.c,), dtype=a.dtype, device=a.device)
+    idx = torch.empty(half + (a.c,), dtype=torch.uint8, device=a.device) if want_argmax else None
+    _lib.check(_lib.lib().brats_affine_act_add_pool_fwd(a.ptr, a.pitch, ss, b.ptr, b.pitch, o.ptr, o.pitch, pooled.data_ptr(), a.c,
+                                                        idx.data_ptr() if idx is not None else None, a.code, ACTS[act], slope, sl,
+                                                        a.n, a.d, a.h, a.w, a.c, _stream()), "affine_act_add_pool_fwd")
+    if idx is not None:
+        o.t._pool_argmax = idx
+    return o.t, pooled
 
 
 def grad_sum(*srcs, out=None):
@@ -1808,7 +1850,14 @@ def _rrcnn_saved(sv, c, cin, dout):
     return g
 
 
-def rrcnn_fwd(x, x2, params, groups=8, act="relu", t=2, save=True):
+# Size of the block output from which rrcnn_fwd(pool=True) takes the one-pass form: tensors beyond the Infinity Cache, _cgr_fwd's rule
+# for affine_act_pool.  Measured at R2Unet-48's encoder shapes, bf16 (profiles/r2unet_time.json): 0.253 against 0.313 ms at
+# 2 x 48 x 128^3 (403 MB); at 2 x 96 x 64^3 (101 MB) the two forms are equal within their spread and at 2 x 192 x 32^3 the pooling
+# kernel re-reads the output from the cache and the two passes are faster (0.029 against 0.037 ms).  The bits are the same.
+POOL_FUSED_MIN_BYTES = 256 << 20
+
+
+def rrcnn_fwd(x, x2, params, groups=8, act="relu", t=2, save=True, pool=False):
     """RRCNNblock (networks/unet_family.py:60-101 of the reference) on NDHWC tensors: x0 = conv1x1([x | x2]) + bias, two
     RecurrentBlocks -- ONE conv3x3x3 (bias) -> norm -> act unit applied t + 1 times, to xb and then to xb + previous result --,
     out = x0 + result.  -> (out, saved).  params: the block's ten parameters in state-dict order; groups: 8 (GroupNorm) or C
@@ -1818,13 +1867,18 @@ def rrcnn_fwd(x, x2, params, groups=8, act="relu", t=2, save=True):
     directly (affine_act_add) -- the plain affine_act only for the first block's result; the last pass of the second block adds
     x0 and writes the output.  save=True: the producers write into slices of the stacked buffers S (unit inputs: x0 is S_A[0:N],
     the first block's result S_B[0:N]) and Y (raw convolution outputs) that rrcnn_bwd reads.  save=False: nothing is kept,
-    four activation buffers are reused throughout, saved is None."""
+    four activation buffers are reused throughout, saved is None.
+    pool=True (the block ends an encoder level of R2U-Net): -> ((out, maxpool2(out)), saved); the last pass writes both
+    (affine_act_add(pool=True)), with save=True also out._pool_argmax for maxpool2_bwd(out, d_pooled, dx_skip=d_skip), whose
+    result is the dout of rrcnn_bwd."""
     if x3_active():
         raise NotImplementedError("rrcnn_fwd: the split-precision modes are not built for the recurrent block")
     a, a2 = _conv_sources(x, x2, "rrcnn_fwd")
     ps, c, cin = _rrcnn_params(params, a)
     if t < 1:
         raise _lib.BratsHipError(f"rrcnn_fwd: t = {t} (t >= 1)")
+    if pool:
+        _even(a, "rrcnn_fwd(pool=True)")
     (n, d, h, w, c1), c2 = a.shape, a2.c
     if (x2 is not None and c1 + c2 != cin) or (x2 is None and c1 < cin):
         raise _lib.BratsHipError(f"rrcnn_fwd: the block is built for {cin} input channels, the tensors have {c1} + {c2}")
@@ -1865,8 +1919,14 @@ def rrcnn_fwd(x, x2, params, groups=8, act="relu", t=2, save=True):
                 # the first block's result has no sum in front of it.  (save=False: it takes over ping[0], which the second block
                 # only reads)
                 xb = affine_act(yk, scale_shift, act, out=sv.S[1][:n] if save else ping[0])
+            elif not pool:
+                out = affine_act_add(yk, scale_shift, x0, act, out=None if save else ping[1])
+            elif yk.numel() * yk.element_size() >= POOL_FUSED_MIN_BYTES:
+                # the block ends an encoder level: the output and its 2x2x2 max pool from one pass (save: + the arg-max bytes)
+                out = affine_act_add(yk, scale_shift, x0, act, out=None if save else ping[1], pool=True, want_argmax=save)
             else:
                 out = affine_act_add(yk, scale_shift, x0, act, out=None if save else ping[1])
+                out = out, maxpool2(out, want_argmax=save)
     return out, (sv if save else None)
 
 

@@ -56,7 +56,8 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * brats_boundary_loss_stats / _grad, brats_dist_loss_ws_floats; brats_gradclip + brats_gradclip_chunk; brats_staple_blocks / _pack /
  * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd; brats_softmax_stats / _grad / _planes + the workspace
  * query, brats_label_stats + its workspace query, brats_argmax_labels; the brats_cbam_* passes; brats_cbam_apply_pool, brats_cbam_bwd_reduce_pool / _bwd_apply_pool;
- * brats_upsample_nearest_fwd / _bwd, brats_planes_nearest_fwd / _bwd; brats_affine_act_add_fwd, brats_grad_sum): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * brats_upsample_nearest_fwd / _bwd, brats_planes_nearest_fwd / _bwd; brats_affine_act_add_fwd, brats_grad_sum;
+ * brats_affine_act_add_pool_fwd): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
  * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
@@ -298,6 +299,15 @@ int brats_affine_act_pool_fwd(const void* y, int ypitch, const float* scale_shif
                               0..7 (d, h, w order) of torch's first arg-max: what brats_maxpool2_bwd_idx reads */,
                               int dtype, int act, float slope, const float* slope_dev, int N, int D, int H, int W, int C,
                               int with_avg, float* amax, brats_stream_t s);
+/* The residual form of that pass, for an RRCNN block that ends an encoder level of R2U-Net (networks/unet_family.py:270-283):
+ * s = add + act(y*scale + shift) AND pooled = maxpool2(s) in one pass.  Bit-identical to brats_affine_act_add_fwd followed by
+ * brats_maxpool2_fwd on the STORED s: the activation is rounded to the storage type, added to `add` in f32 and rounded once; the
+ * maximum is taken over the stored sums, ties go to the first voxel in d, h, w order, a NaN wins; argmax (optional) as above.
+ * `add`, `s` and `pooled` may be channel slices (pitch > C); `s` must not overlap `y` or `add`; D, H, W even.  relu / leakyrelu
+ * (the other activations: BRATS_E_UNSUPPORTED, as for more than 128 channel vectors -- run the two passes). */
+int brats_affine_act_add_pool_fwd(const void* y, int ypitch, const float* scale_shift, const void* add, int addpitch, void* s,
+                                  int spitch, void* pooled, int ppitch, unsigned char* argmax, int dtype, int act, float slope,
+                                  const float* slope_dev, int N, int D, int H, int W, int C, brats_stream_t stream);
 /* backward of z = act(GN(y)): pass 1 reduces, per (n,channel), sum(u) and sum(u*xhat) with
  * u = dz * act'(.) into `red` (workspace of brats_gn_bwd_ws_floats() elements); pass 2 writes dy and finishes
  * dgamma/dbeta [C]. */
