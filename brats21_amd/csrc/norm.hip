@@ -6,6 +6,7 @@
 #include "twin_begin.hpp"
 #include "common.hpp"
 
+#include "act.hpp"
 #include "se.hpp"
 
 // ---- statistics finalize ---------------------------------------------------------------------------
@@ -205,42 +206,9 @@ extern "C" int BRATS_API(brats_gn_finalize)(const float* stats, int tiles_per_sa
 }
 
 // ---- z = act(y*scale + shift) ------------------------------------------------------------------
-// HEAVY = false instantiations contain only relu / leakyrelu (the transcendental activations cost the streaming kernels
-// ~10-20 % through code size and registers even when not selected)
+// (act_fwd / act_grad and their HEAVY switch: act.hpp)
 // negative-side slope of leakyrelu: a host value, or -- nn.PReLU's learnable scalar -- read from device memory
 struct SlopeArg { float v; const float* p; };
-template <bool HEAVY>
-DEVI float act_fwd(float x, int act, float slope) {
-  if (act == BRATS_ACT_RELU) return x > 0.f ? x : 0.f;
-  if (act == BRATS_ACT_LEAKY) return x > 0.f ? x : x * slope;
-  if constexpr (!HEAVY) return x;
-  if (act == BRATS_ACT_ELU) return x > 0.f ? x : expm1f(x);
-  if (act == BRATS_ACT_SWISH) return x / (1.f + __expf(-x));
-  if (act == BRATS_ACT_MISH) {
-    const float sp = x > 20.f ? x : log1pf(__expf(x));  // softplus with torch's threshold
-    return x * tanhf(sp);
-  }
-  return x;
-}
-template <bool HEAVY>
-DEVI float act_grad(float x, int act, float slope) {  // derivative at pre-activation x
-  if (act == BRATS_ACT_RELU) return x > 0.f ? 1.f : 0.f;
-  if (act == BRATS_ACT_LEAKY) return x > 0.f ? 1.f : slope;
-  if constexpr (!HEAVY) return 1.f;
-  if (act == BRATS_ACT_ELU) return x > 0.f ? 1.f : __expf(x);
-  if (act == BRATS_ACT_SWISH) {
-    const float sg = 1.f / (1.f + __expf(-x));
-    return sg * (1.f + x * (1.f - sg));
-  }
-  if (act == BRATS_ACT_MISH) {
-    const float sp = x > 20.f ? x : log1pf(__expf(x));
-    const float th = tanhf(sp);
-    const float sg = 1.f / (1.f + __expf(-x));
-    return th + x * (1.f - th * th) * sg;
-  }
-  return 1.f;
-}
-
 // |max| of a tensor as a side product of the kernel that writes it (the fp8 convolutions scale their input by it):
 // wave maximum by DPP-free shuffles, one integer atomicMax on the bits of the non-negative float per wave.  max is
 // order-independent, so this atomic keeps results bitwise reproducible.  The slot must be zero before the launch.

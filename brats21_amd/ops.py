@@ -2041,3 +2041,8 @@ def probe_box(device=None, mfma_ms=50.0, stream_bytes=403 << 20, modes=(0, 1)):
                     f"random operands: the sustained matrix rate, sclk = the clock behind it at 16 cycles per MFMA and SIMD; mfma_zeros = "
                     f"every second value zero); bf16 read + write stream over {stream_bytes >> 20} MiB, {sms * 1e3:.0f} us per pass")
     return rec
+
+
+# ------------------------------------------------------------------------------------------ additive attention gate
+# (defined in a module of its own, which imports this one: the import stands last)
+from ._attgate import AttGateSaved, attgate_bwd, attgate_fwd  # noqa: E402,F401

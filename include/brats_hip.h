@@ -57,7 +57,7 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd; brats_softmax_stats / _grad / _planes + the workspace
  * query, brats_label_stats + its workspace query, brats_argmax_labels; the brats_cbam_* passes; brats_cbam_apply_pool, brats_cbam_bwd_reduce_pool / _bwd_apply_pool;
  * brats_upsample_nearest_fwd / _bwd, brats_planes_nearest_fwd / _bwd; brats_affine_act_add_fwd, brats_grad_sum;
- * brats_affine_act_add_pool_fwd): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * brats_affine_act_add_pool_fwd; the brats_attgate_* passes): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
  * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
@@ -992,6 +992,57 @@ int brats_gamma_noise(const float* x, float* y, size_t total, float vmin, float 
  *     library's own streaming policy (non-temporal, 4 vectors in flight) -> 2 * bytes of HBM traffic. */
 int brats_probe_mfma(float* out, int blocks, int iters, int mode, brats_stream_t s);
 int brats_probe_stream(const void* src, void* dst, size_t bytes, brats_stream_t s);
+
+/* ---- additive attention gate (csrc/attgate.hip; AttentionBlock of networks/unet_family.py:104-131):
+ *   g1 = BN_g(W_g g + b_g), x1 = BN_x(W_x x + b_x), p = act(g1 + x1), q = w_psi . p + b_psi, out = x * sigmoid(BN_1(q))
+ * with nn.BatchNorm3d throughout.  The 1x1x1 convolutions, their gradients and the statistics of BN_g / BN_x are brats_conv3d_fwd,
+ * brats_conv3d_wgrad_shift and brats_gn_finalize on the batch viewed as one sample; these passes are the rest.  Activations: NDHWC of
+ * dtype BRATS_F32 / BRATS_BF16 / BRATS_F16, 16-byte aligned, pitches in elements (channel slices are fine); C (the padded f_int of
+ * g1raw / x1raw, or the channels of x) a multiple of the 16-byte channel vector (BRATS_E_ARG otherwise) and at most 256 vectors =
+ * 1024 channels in f32, 2048 in 16-bit storage (BRATS_E_UNSUPPORTED beyond); voxels < 2^31 per sample, any N.  The batch is walked
+ * as one sample of N * voxels voxels.  All arithmetic f32, sums over voxels f64 across lanes and workgroups; per-workgroup partials
+ * added in a fixed order, no floating-point atomics: the same bits at every run.  No host reads: capturable.
+ * Small f32 tables: ss_g / ss_x [C][2] = scale, shift and mr_g / mr_x [C][2] = mean, rstd of BN_g / BN_x (brats_gn_finalize's
+ * outputs for N = 1; in eval mode built from the running buffers); w_psi [C]; st1 [8] = {mean of q + b_psi, biased variance, rstd,
+ * sub, a, b, 0, 0} with qhat = (q - sub) * rstd and BN_1 = a * q + b on the plane q, which does NOT hold b_psi; bw1 [4] = {sum dqn *
+ * qhat (= d psi.1.weight), sum dqn (= d psi.1.bias), m1, m2}; coef [3][C]; sums [4 * C + 1] = sum ds (= d W_g.1.bias = d W_x.1.bias),
+ * sum ds * ghat (= d W_g.1.weight), sum ds * xhat (= d W_x.1.weight), sum dq * p (= d psi.0.weight), each [C], then sum dq
+ * (= d psi.0.bias).
+ *   blocks          : workgroups nb of the reducing passes over a C-channel tensor: part of psi_fwd / apply_bwd holds 2 * nb doubles,
+ *                     part of psi_bwd_stats nb * (4 * C + 4) floats.
+ *   psi_fwd         : q[N * voxels] = w_psi . act(ss_g(g1raw) + ss_x(x1raw)); part != NULL (training): per-workgroup (sum q, sum q^2).
+ *   bn1             : st1 from the partials (training: running_mean = running_var = NULL) or from the running buffers (eval; part
+ *                     may be NULL); count = N * voxels.
+ *   apply_fwd       : out = x * sigmoid(a * q + b).
+ *   apply_bwd       : dqn = (sum_c dout * x) * alpha * (1 - alpha) and per-workgroup (sum dqn, sum dqn * qhat).
+ *   bn1_bwd         : bw1 from those partials; training = 0 (frozen statistics): m1 = m2 = 0.
+ *   psi_bwd_stats   : recomputes s, p; dq = a * (dqn - m1 - qhat * m2), ds = w_psi * dq * act'(s); per-workgroup partials of `sums`.
+ *   psi_bwd_finalize: sums and coef = the means BN_g / BN_x's backward takes (training = 0: zeros).
+ *   psi_bwd_apply   : dg1raw = scale_g * (ds - mean ds - ghat * mean ds ghat), dx1raw alike, in the storage type.
+ *   dx              : dx = dout * sigmoid(a * q + b) + t, t = the input gradient of the W_x convolution. */
+int brats_attgate_blocks(int dtype, int C, int N, int voxels);
+int brats_attgate_psi_fwd(const void* g1raw, int gpitch, const void* x1raw, int xpitch, const float* ss_g, const float* ss_x,
+                          const float* w_psi, float* q, double* part, int dtype, int act, float slope, int N, int voxels, int C,
+                          brats_stream_t s);
+int brats_attgate_bn1(const double* part, int nb, double count, const float* gamma, const float* beta, const float* b_psi,
+                      const float* running_mean, const float* running_var, float eps, float* st1, brats_stream_t s);
+int brats_attgate_apply_fwd(const void* x, int xpitch, const float* q, const float* st1, void* out, int opitch, int dtype, int N,
+                            int voxels, int C, brats_stream_t s);
+int brats_attgate_apply_bwd(const void* dout, int dopitch, const void* x, int xpitch, const float* q, const float* st1, float* dqn,
+                            double* part, int dtype, int N, int voxels, int C, brats_stream_t s);
+int brats_attgate_bn1_bwd(const double* part, int nb, double count, int training, float* bw1, brats_stream_t s);
+int brats_attgate_psi_bwd_stats(const void* g1raw, int gpitch, const void* x1raw, int xpitch, const float* q, const float* dqn,
+                                const float* ss_g, const float* ss_x, const float* mr_g, const float* mr_x, const float* w_psi,
+                                const float* st1, const float* bw1, float* part, int dtype, int act, float slope, int N, int voxels,
+                                int C, brats_stream_t s);
+int brats_attgate_psi_bwd_finalize(const float* part, int nb, int C, double count, int training, float* sums, float* coef,
+                                   brats_stream_t s);
+int brats_attgate_psi_bwd_apply(const void* g1raw, int gpitch, const void* x1raw, int xpitch, const float* q, const float* dqn,
+                                const float* ss_g, const float* ss_x, const float* mr_g, const float* mr_x, const float* w_psi,
+                                const float* st1, const float* bw1, const float* coef, void* dg1raw, int dgpitch, void* dx1raw,
+                                int dxpitch, int dtype, int act, float slope, int N, int voxels, int C, brats_stream_t s);
+int brats_attgate_dx(const void* dout, int dopitch, const void* t, int tpitch, const float* q, const float* st1, void* dx, int dxpitch,
+                     int dtype, int N, int voxels, int C, brats_stream_t s);
 
 #ifdef __cplusplus
 }
