@@ -1,4 +1,5 @@
-"""Exact integer-operand references for the convolution kernels (tests/test_conv_exact_cpu.py, tests/test_conv_exact_gpu.py).
+"""Exact integer-operand references for the convolution kernels (tests/test_conv_exact_cpu.py, tests/test_conv_exact_gpu.py,
+tests/test_dconv_exact_gpu.py).
 
 The technique: every element of x, dy, w (and the bias) is a small integer, exact in bf16, fp16, f32, e4m3 and in the hi
 half of a split-precision pair.  Every product is then an integer, and while the worst-case sum of absolute values stays
@@ -13,6 +14,8 @@ The second half mirrors the host selection rules of csrc/conv_wgrad.hip (wgrad_n
 wgrad_tiles, wgrad_plan, wgrad_reduce_launch) -- the arithmetic is copied, so that a change of a rule makes the
 GPU tests fail (their mirrored workspace size no longer equals the library's) instead of quietly exercising another branch."""
 import functools
+import math
+from types import SimpleNamespace
 
 import torch
 
@@ -349,3 +352,176 @@ def dgrad_case(cin, cout, n, size, dil=1, k=3, seed=0):
     w = int_tensor((cout, cin, k, k, k), 9000 + seed)
     require_fwd_exact(dy, w.transpose(0, 1))
     return dy, w, dgrad_ref(dy, w, dil)
+
+
+# ------------------------------------------------------------------------------------------ direct (gather) convolution, csrc/dconv.hip
+# One launch of ops.dconv_run = up to 4 jobs, a job's output = bias + the sum of up to 4 terms, every term with its own input,
+# channel count, kernel size and dilation.  The reference of a job is the sum of fwd_ref (or dgrad_ref) over its terms.
+#
+# 16-bit storage: the kernel rounds its f32 accumulators once, to the storage type.  Integers up to 2^8 (bf16, 8 significand bits)
+# and 2^11 (fp16, 11 bits) are exact there, so a case whose reference stays within OUT_BOUND is stored unrounded and a change of
+# 1 in any output is visible.  The builders thin the operands for that (below) and assert it on the reference alone.
+OUT_BOUND = {torch.bfloat16: 256.0, torch.float16: 2048.0, torch.float32: None}
+DCONV_KCH = {torch.bfloat16: 16, torch.float16: 16, torch.float32: 8}  # channels per pipeline step (DcT<T>::KCH)
+DCONV_NF, DCONV_WG_VOX = 3, 256     # row fragments of 32 per workgroup; voxels per workgroup (4 waves x 2 fragments of 32)
+
+VOL_RAGGED = (2, (5, 6, 7))     # 420 voxels: partial last workgroup and fragment, fragments across the sample boundary
+VOL_TINY = (3, (2, 3, 5))       # 90 voxels: less than one workgroup, whole waves return early
+VOL_LINE = (1, (1, 1, 33))      # degenerate z and y: only the x taps survive
+VOL_WHOLE = (2, (8, 8, 8))      # 1024 voxels: whole workgroups only
+DCONV_VOLUMES = (VOL_RAGGED, VOL_TINY, VOL_LINE, VOL_WHOLE)
+
+
+def _taps_of(k):
+    return 27 if k == 3 else 1
+
+
+def thin_density(kdim, bound, other=None):
+    """The density of two operand sets (x in +-{1, 2}: E[x^2 | x != 0] = 2.5; w in +-1) at which the standard deviation of a
+    sum of `kdim` products is bound / 8 -- from the operand distributions alone; the extreme of the 10^5 outputs of a case
+    lies near 4.5 standard deviations.  other: the density of one set is given, that of the second is returned."""
+    if bound is None:
+        return 1.0
+    var = (bound / 8.0) ** 2
+    if other is None:
+        return min(1.0, math.sqrt(var / (2.5 * kdim)))
+    return min(1.0, var / (2.5 * kdim * other))
+
+
+def require_terms_exact(terms, bias=None):
+    """terms: [(x, w as [rows, cin, k, k, k])].  Sum over the terms of taps cin max|x| max|w|, plus max|bias|, below 2^24."""
+    bound = float(bias.abs().max()) if bias is not None else 0.0
+    for x, w in terms:
+        assert x.shape[-1] == w.shape[1], "term: channels of x and w differ"
+        bound += w.shape[2] ** 3 * w.shape[1] * max(float(x.abs().max()), 1.0) * max(float(w.abs().max()), 1.0)
+        for t in (x, w):
+            assert bool((t == t.round()).all()), "operands must be integers"
+    assert bias is None or bool((bias == bias.round()).all()), "operands must be integers"
+    assert bound < EXACT, f"direct-convolution precondition violated: sum of taps cin max|x| max|w| + |bias| = {bound:.0f} >= 2^24"
+
+
+def require_within(ref, bound, what=""):
+    """The 16-bit condition: max|ref| <= bound (None: f32 storage, no condition), so that the store rounds nothing."""
+    if bound is not None:
+        m = float(ref.abs().max())
+        assert m <= bound, f"{what}: max|reference| = {m:.0f} exceeds {bound:.0f}, the largest range of exact integers of the storage type"
+
+
+@functools.lru_cache(maxsize=None)
+def dconv_case(n, size, jobs, mode="fwd", bound=None, seed=0):
+    """One launch.  jobs: up to 4 of (rows, ((cin, k, dil), ... up to 4 terms), with_bias).
+    mode "fwd":   term = conv(x [.., cin], w [rows, cin, k, k, k]) at dilation dil (packed PACK_FWD)
+    mode "dgrad": term = input gradient of dy [.., cin] through w [cin, rows, k, k, k] (packed PACK_DGRAD)
+    bound None (f32 storage): dense operands in [-2, 2].  Otherwise (OUT_BOUND of a 16-bit type) x in [-2, 2] and w in
+    {-1, 0, 1} at thin_density() of the job's K, and max|reference| <= bound is asserted.
+    Terms (of any job) with the same position and channel count share ONE input tensor (the network's forward: four jobs over
+    one x).  -> namespace(n, size, mode, jobs = [namespace(rows, terms = [namespace(x, w, k, dil, cin)], bias, ref float64)])."""
+    assert 1 <= len(jobs) <= 4 and all(1 <= len(terms) <= 4 for _, terms, _ in jobs)
+    shared = {}
+    out = []
+    for j, (rows, terms, with_bias) in enumerate(jobs):
+        dens = thin_density(sum(_taps_of(k) * cin for cin, k, _ in terms), bound)
+        ts = []
+        for t, (cin, k, dil) in enumerate(terms):
+            if mode == "fwd":
+                key = (t, cin)
+                if key not in shared:  # (one density for a shared input: that of the first job that uses it)
+                    shared[key] = int_tensor((n, *size, cin), 4000 + 100 * seed + 10 * t + cin, dens)
+                x = shared[key]
+                w = int_tensor((rows, cin, k, k, k), 6000 + 100 * seed + 10 * j + t, dens, 2 if bound is None else 1)
+            else:
+                x = int_tensor((n, *size, cin), 8000 + 100 * seed + 10 * j + t, dens)
+                w = int_tensor((cin, rows, k, k, k), 9000 + 100 * seed + 10 * j + t, dens, 2 if bound is None else 1)
+            ts.append(SimpleNamespace(x=x, w=w, k=k, dil=dil, cin=cin))
+        bias = int_tensor((rows,), 7000 + 100 * seed + j) if with_bias else None
+        if mode == "fwd":
+            require_terms_exact([(t.x, t.w) for t in ts], bias)
+            ref = sum(fwd_ref(t.x, t.w, None, t.dil) for t in ts)
+        else:
+            require_terms_exact([(t.x, t.w.transpose(0, 1)) for t in ts], bias)
+            ref = sum(dgrad_ref(t.x, t.w, t.dil) for t in ts)
+        if bias is not None:
+            ref = ref + bias.double()
+        require_within(ref, bound, f"dconv_case job {j}")
+        out.append(SimpleNamespace(rows=rows, terms=ts, bias=bias, ref=ref))
+    return SimpleNamespace(n=n, size=size, mode=mode, jobs=out)
+
+
+@functools.lru_cache(maxsize=None)
+def dconv_split_case(c1, c2, cout, n, size, k, dil, bound=None, seed=0):
+    """One weight over two inputs: y = conv([x | x2], w) run as a two-term job with w[:, :c1] over x and w[:, c1:] over x2
+    (cin_off / cin_cnt of pack_weights_direct).  -> (x, x2, w, bias, y float64)."""
+    dens = thin_density(_taps_of(k) * (c1 + c2), bound)
+    x = int_tensor((n, *size, c1), 4500 + seed, dens)
+    x2 = int_tensor((n, *size, c2), 5500 + seed, dens)
+    w = int_tensor((cout, c1 + c2, k, k, k), 6500 + seed, dens, 2 if bound is None else 1)
+    bias = int_tensor((cout,), 7500 + seed)
+    require_fwd_exact(x, w, bias, x2)
+    y = fwd_ref(x, w, bias, dil, x2)
+    require_within(y, bound, "dconv_split_case")
+    return x, x2, w, bias, y
+
+
+def dconv_cases(dtype):
+    """name -> arguments of dconv_case, for every launch tests/test_dconv_exact_gpu.py makes in storage type `dtype` (channel
+    counts follow the type's KCH).  tests/test_conv_exact_cpu.py builds them all: the builders assert the preconditions."""
+    kch, bound = DCONV_KCH[dtype], OUT_BOUND[dtype]
+    c = {}
+    for n, size in DCONV_VOLUMES:
+        v = "x".join(str(s) for s in (n,) + size)
+        for s in (1, 2, 3, 4, 7):  # S = cin / KCH steps against a pipeline three deep
+            c[f"k1-S{s}-{v}"] = (n, size, ((32, ((s * kch, 1, 1),), s % 2 == 1),), "fwd", bound)
+        for dil in (1, 2, 3, 4, 6) if (n, size) in (VOL_RAGGED, VOL_WHOLE) else (1, 2):
+            for with_bias in (True, False):
+                c[f"k3-d{dil}-{'bias' if with_bias else 'nobias'}-{v}"] = (n, size, ((48, ((2 * kch, 3, dil),), with_bias),), "fwd", bound)
+    for n, size in (VOL_RAGGED, VOL_WHOLE):
+        v = "x".join(str(s) for s in (n,) + size)
+        for rows in (4, 16, 36, 96, 100, 132):
+            c[f"rows{rows}-{v}"] = (n, size, ((rows, ((kch, 3, 1),), True),), "fwd", bound)
+        net = ((1, 1), (3, 2), (3, 4), (3, 6))
+        c[f"net-equal-{v}"] = (n, size, tuple((16, ((32, k, dl),), True) for k, dl in net), "fwd", bound)
+        c[f"net-rows-{v}"] = (n, size, tuple((r, ((32, k, dl),), True) for r, (k, dl) in zip((100, 16, 36, 4), net)), "fwd", bound)
+        c[f"dgrad-four-{v}"] = (n, size, ((32, tuple((16, k, dl) for k, dl in net), False),), "dgrad", bound)
+        mixed = ((16, 1, 1), (48, 3, 3), (32, 3, 6), (kch, 3, 1))
+        for nt in (1, 2, 3, 4):
+            c[f"dgrad-mixed{nt}-{v}"] = (n, size, ((36, mixed[:nt], False),), "dgrad", bound)
+    return c
+
+
+DCONV_SPLIT_CASES = [(16, 32, 36, VOL_RAGGED, 3, 2), (32, 16, 32, VOL_WHOLE, 3, 4), (16, 48, 100, VOL_RAGGED, 1, 1)]  # c1, c2, cout, volume, k, dil
+
+ASPP_BRANCHES = {  # (kernel sizes, dilations) of SimpleASPPEVO: the default, five (two launches), nine (three launches)
+    4: ((1, 3, 3, 3), (1, 2, 4, 6)),
+    5: ((1, 3, 3, 3, 3), (1, 1, 2, 4, 6)),
+    9: ((1, 3, 3, 3, 3, 1, 3, 3, 3), (1, 1, 2, 4, 6, 1, 2, 4, 6)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def aspp_case(nb, cin, q, n, size, bound=None, seed=0):
+    """The ASPP stage with ASPP_BRANCHES[nb]: x [.., cin], per branch w [q, cin, k, k, k] and bias [q], d_acat [.., nb q].
+    -> namespace(ks, dils, x, ws, bs, dy, acat, dx, dx_parts, dws, dbs), the references in float64.  dx_parts: the partial input
+    gradients of the launches _aspp_bwd makes (four branches each); the network rounds each to the storage type before torch
+    adds them, so under a 16-bit bound every partial and the total must stay within it (then the split sum is exact)."""
+    ks, dils = ASPP_BRANCHES[nb]
+    d_fwd = thin_density(27 * cin, bound)
+    x = int_tensor((n, *size, cin), 4700 + seed, d_fwd)
+    ws = [int_tensor((q, cin, k, k, k), 6700 + 10 * seed + i, d_fwd, 2 if bound is None else 1) for i, k in enumerate(ks)]
+    bs = [int_tensor((q,), 7700 + 10 * seed + i) for i in range(nb)]
+    dy = int_tensor((n, *size, nb * q), 8700 + seed, thin_density(sum(_taps_of(k) * q for k in ks), bound, d_fwd))
+    dys = [dy[..., i * q:(i + 1) * q] for i in range(nb)]
+    for i in range(nb):
+        require_fwd_exact(x, ws[i], bs[i])
+        require_wgrad_exact(x, dys[i])
+    require_terms_exact([(dys[i], ws[i].transpose(0, 1)) for i in range(nb)])
+    acat = torch.cat([fwd_ref(x, ws[i], bs[i], dils[i]) for i in range(nb)], -1)
+    parts = [sum(dgrad_ref(dys[i], ws[i], dils[i]) for i in range(j0, min(j0 + 4, nb))) for j0 in range(0, nb, 4)]
+    dx = sum(parts)
+    for what, t in [("acat", acat), ("dx", dx)] + [(f"dx part {i}", p) for i, p in enumerate(parts)]:
+        require_within(t, bound, f"aspp_case {what}")
+    dws = [wgrad_ref(x, dys[i], dils[i], ks[i]) for i in range(nb)]
+    dbs = [dbias_ref(dys[i]) for i in range(nb)]
+    return SimpleNamespace(ks=ks, dils=dils, x=x, ws=ws, bs=bs, dy=dy, acat=acat, dx=dx, dx_parts=parts, dws=dws, dbs=dbs)
+
+
+ASPP_CASES = [(nb, 32, 16, n, size) for nb in (4, 5, 9) for n, size in (VOL_RAGGED, VOL_WHOLE)]  # nb, cin, q, n, size

@@ -155,3 +155,134 @@ def test_mirror_of_the_weight_gradient_host_rules():
     assert R.wgrad_plan(True, 1, 24, 0, 40, 2, 5, 6, 18, 0, 256)["memset"]
     s = R.wgrad_shift_plan(True, 1, 384, 96, 1, 8, 8, 16)
     assert (s["ntiles"], s["nlane"], s["cof"], s["cif"], s["nsplit"]) == (4, 1, 3, 3, 4)
+
+
+# ---------------------------------------------------------------------------------------------- direct (gather) convolution
+def _torch_term(x, w, dy, k, dil):
+    """F.conv3d (padding = dilation for k = 3) and its autograd input gradient, channels-last f32."""
+    xr = _nc(x).requires_grad_(True)
+    y = F.conv3d(xr, w, None, 1, dil if k == 3 else 0, dil)
+    y.backward(_nc(dy))
+    return y.detach().permute(0, 2, 3, 4, 1), xr.grad.permute(0, 2, 3, 4, 1)
+
+
+@pytest.mark.parametrize("k,dil,n,size", [(3, 3, 2, (5, 6, 7)), (3, 4, 1, (8, 8, 8)), (3, 6, 2, (5, 6, 7)), (3, 6, 1, (7, 13, 14)),
+                                          (1, 1, 2, (5, 6, 7)), (1, 1, 1, (1, 1, 33))])
+def test_wide_dilation_and_pointwise_references_equal_torch(k, dil, n, size):
+    """fwd_ref and dgrad_ref at the dilations of the ASPP branches (3, 4, 6; on 5x6x7 every extent is thinner than dilation 6)
+    and at k = 1, against torch's f32 CPU convolution and autograd, bit for bit."""
+    cin, cout = 24, 16
+    x, _, w, bias, y_ref = R.fwd_case(cin, 0, cout, n, size, dil, k, seed=3)
+    dy = R.int_tensor((n, *size, cout), 13)
+    R.require_fwd_exact(dy, w.transpose(0, 1))
+    y, dx = _torch_term(x, w, dy, k, dil)
+    R.assert_exact(y + bias, y_ref, what=f"forward k {k} dilation {dil}")
+    R.assert_exact(dx, R.dgrad_ref(dy, w, dil), what=f"input gradient k {k} dilation {dil}")
+
+
+def test_dilation_wider_than_the_volume_leaves_the_centre_tap():
+    """2 x (5, 6, 7) at dilation 6: every tap that moves in z (extent 5) or y (extent 6) leaves the volume, and an x tap stays
+    inside only between the columns x = 0 and x = 6 (extent 7).  So the branch equals a 1x1x1 convolution with the centre
+    weights at x = 1..5, and the three (centre, centre, *) taps everywhere -- what the direct kernel's tap masks must reproduce.
+    On 2 x (5, 6, 6) the centre tap is all that is left."""
+    x, _, w, bias, y_ref = R.fwd_case(16, 0, 32, 2, (5, 6, 7), 6, 3, seed=4)
+    centre = w[:, :, 1:2, 1:2, 1:2].contiguous()
+    assert torch.equal(y_ref[:, :, :, 1:6], R.fwd_ref(x, centre, bias, 1)[:, :, :, 1:6])
+    assert not torch.equal(y_ref[:, :, :, 0], R.fwd_ref(x, centre, bias, 1)[:, :, :, 0])
+    wx = torch.zeros_like(w)
+    wx[:, :, 1, 1, :] = w[:, :, 1, 1, :]
+    assert torch.equal(y_ref, R.fwd_ref(x, wx, bias, 6))
+    dy = R.int_tensor((2, 5, 6, 7, 32), 14)
+    assert torch.equal(R.dgrad_ref(dy, w, 6), R.dgrad_ref(dy, wx, 6))
+    assert torch.equal(R.dgrad_ref(dy, w, 6)[:, :, :, 1:6], R.dgrad_ref(dy, centre, 1)[:, :, :, 1:6])
+    x6, _, w6, b6, y6 = R.fwd_case(16, 0, 32, 2, (5, 6, 6), 6, 3, seed=4)
+    assert torch.equal(y6, R.fwd_ref(x6, w6[:, :, 1:2, 1:2, 1:2].contiguous(), b6, 1))
+
+
+def test_four_term_sum_equals_the_sum_of_four_torch_input_gradients():
+    """The reference of a four-term PACK_DGRAD job (dconv_case, mode "dgrad") = the sum of four F.conv3d autograd input gradients
+    (summed in float64: every one of them is an exact integer), and that of a forward job = the sum of four F.conv3d outputs."""
+    n, size = R.VOL_RAGGED
+    terms = ((16, 1, 1), (48, 3, 3), (32, 3, 6), (8, 3, 2))
+    case = R.dconv_case(n, size, ((36, terms, False),), "dgrad")
+    job = case.jobs[0]
+    tot = torch.zeros((n, *size, 36), dtype=torch.float64)
+    for t in job.terms:
+        xr = torch.zeros((n, 36, *size), requires_grad=True)
+        F.conv3d(xr, t.w, None, 1, t.dil if t.k == 3 else 0, t.dil).backward(_nc(t.x))
+        tot += xr.grad.permute(0, 2, 3, 4, 1).double()
+    R.assert_exact(tot.float(), job.ref, what="four-term input gradient")
+    fwd = R.dconv_case(n, size, ((36, terms, True),), "fwd").jobs[0]
+    tot = sum(F.conv3d(_nc(t.x), t.w, None, 1, t.dil if t.k == 3 else 0, t.dil).permute(0, 2, 3, 4, 1).double() for t in fwd.terms)
+    R.assert_exact((tot + fwd.bias.double()).float(), fwd.ref, what="four-term forward")
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32], ids=["bf16", "fp16", "f32"])
+def test_every_dconv_case_meets_its_preconditions(dtype):
+    """Every launch of tests/test_dconv_exact_gpu.py, built on the CPU: the builders assert the 2^24 bound on the operands and, for
+    the 16-bit types, max|reference| <= 256 (bf16) / 2048 (fp16) -- the store then rounds nothing and a change of 1 in any output
+    is visible.  Checked again here from outside the builders, with the operands' exactness in the storage type."""
+    bound = R.OUT_BOUND[dtype]
+    cases = R.dconv_cases(dtype)
+    assert len(cases) == len(R.dconv_cases(torch.float32))
+    for name, args in cases.items():
+        case = R.dconv_case(*args)
+        for job in case.jobs:
+            assert job.ref.shape == (case.n, *case.size, job.rows) and float(job.ref.abs().max()) > 0, name
+            assert torch.equal(job.ref, job.ref.round()), name
+            if bound is not None:
+                assert float(job.ref.abs().max()) <= bound, name
+                assert torch.equal(job.ref.float().to(dtype).double(), job.ref), name  # the final rounding is the identity
+            for t in job.terms:
+                assert torch.equal(t.x.to(dtype).float(), t.x) and torch.equal(t.w.to(dtype).float(), t.w), name
+    for c1, c2, cout, (n, size), k, dil in R.DCONV_SPLIT_CASES:
+        y = R.dconv_split_case(c1, c2, cout, n, size, k, dil, bound)[-1]
+        assert bound is None or torch.equal(y.float().to(dtype).double(), y)
+    for nb, cin, q, n, size in R.ASPP_CASES:
+        a = R.aspp_case(nb, cin, q, n, size, bound)
+        assert len(a.dx_parts) == (nb + 3) // 4 and torch.equal(sum(a.dx_parts), a.dx)
+        if bound is not None:
+            # each launch's partial is stored unrounded, so torch's 16-bit adds of the parts are exact too
+            run = torch.zeros_like(a.dx)
+            for p in a.dx_parts:
+                run = run + p
+                assert float(p.abs().max()) <= bound and float(run.abs().max()) <= bound
+            for t in (a.acat, a.dx):
+                assert torch.equal(t.float().to(dtype).double(), t)
+
+
+def test_dconv_case_list_reaches_the_kernel_geometry():
+    """The properties of the case list that the kernel's branches need (NF = 3 row fragments of 32 per workgroup, 256 voxels per
+    workgroup, a pipeline three steps deep), asserted on the list itself."""
+    for dtype in (torch.bfloat16, torch.float32):
+        kch, cases = R.DCONV_KCH[dtype], R.dconv_cases(dtype)
+        steps = {sum(R._taps_of(k) * cin // kch for cin, k, _ in jobs[0][1]) for name, (_, _, jobs, _, _) in cases.items() if name.startswith("k1-")}
+        assert steps == {1, 2, 3, 4, 7}   # below, at and above the pipeline depth, and no multiple of it
+        rows = sorted({jobs[0][0] for name, (_, _, jobs, _, _) in cases.items() if name.startswith("rows")})
+        assert rows == [4, 16, 36, 96, 100, 132]
+        frags = [(r + 31) // 32 for r in rows]
+        assert [(f + R.DCONV_NF - 1) // R.DCONV_NF for f in frags] == [1, 1, 1, 1, 2, 2]     # 100, 132: a second blockIdx.y ...
+        assert [f - R.DCONV_NF for f in frags[4:]] == [1, 2]                                  # ... with one and with two live fragments
+        assert [r % 32 for r in rows] == [4, 16, 4, 0, 4, 4]                                  # tails inside a fragment at a granule of 4
+        net = cases["net-rows-2x5x6x7"][2]
+        assert [j[0] for j in net] == [100, 16, 36, 4] and [j[1][0][1:] for j in net] == [(1, 1), (3, 2), (3, 4), (3, 6)]
+    vox = [n * s[0] * s[1] * s[2] for n, s in R.DCONV_VOLUMES]
+    assert vox == [420, 90, 33, 1024]
+    assert vox[0] % R.DCONV_WG_VOX and vox[0] % 32 and (vox[0] // 2) % 32     # partial workgroup and fragment, a fragment across samples
+    assert vox[1] < R.DCONV_WG_VOX - 64 and vox[3] % R.DCONV_WG_VOX == 0      # a whole wave idle / whole workgroups only
+
+
+def test_dconv_preconditions_reject_violations():
+    x, w = R.int_tensor((1, 2, 2, 4, 16), 1), R.int_tensor((8, 16, 3, 3, 3), 2)
+    R.require_terms_exact([(x, w), (x, w)], R.int_tensor((8,), 3))
+    with pytest.raises(AssertionError, match="2\\^24"):
+        R.require_terms_exact([(x * 2 ** 7, w * 2 ** 5)] * 4)      # 4 * 27 * 16 * 256 * 64 > 2^24 though one term alone is below
+    R.require_terms_exact([(x * 2 ** 7, w * 2 ** 5)])
+    with pytest.raises(AssertionError, match="integers"):
+        R.require_terms_exact([(x, w + 0.5)])
+    R.require_within(torch.tensor([256.0, -3.0]), 256.0)
+    with pytest.raises(AssertionError, match="exceeds 256"):
+        R.require_within(torch.tensor([257.0]), 256.0)
+    with pytest.raises(AssertionError, match="exceeds 256"):      # dense operands at cin = 96 do not fit bf16 (the builder thins them)
+        R.require_within(R.fwd_case(96, 0, 32, 2, (8, 8, 8), 1)[-1], 256.0)
+    assert R.thin_density(16, 256.0) == 1.0 and R.thin_density(27 * 96, 256.0) < 0.5 and R.thin_density(27 * 96, None) == 1.0
