@@ -9,7 +9,7 @@ template <> int conv_launch<bf16_t, 3, 1>(const ConvParams& p, int ck, hipStream
   // of conv_igemm_first.hpp (round 6) where the layer has its shape; the 4x8x16-tile kernel otherwise
   if (conv_first_ok(p, ck)) return conv_launch_first(p, st);
   if (ck == 8 && p.nchunks == 1 && p.rows16 % 3 == 0 && p.rows16 % 6 != 0 && conv_vs8_enabled() &&
-      (long)p.N * p.tz * p.ty * p.tx >= 2048)
+      (long)p.N * p.tz * p.ty * p.tx >= conv_first_min_tiles())
     return conv_launch_vs8<8, 1, 3>(p, st);
   switch (ck) {
     case 48: return conv_launch_ck<bf16_t, 3, 48, 1>(p, st);

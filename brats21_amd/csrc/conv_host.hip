@@ -16,6 +16,18 @@ extern "C" int BRATS_API(brats_conv3d_set_kp)(int mode) {
   g_conv_kp_mode = mode < 0 ? -1 : (mode ? 1 : 0);
   return old;
 }
+int g_conv_first_min_tiles = CONV_FIRST_MIN_TILES;  // brats_conv3d_set_first_min_tiles (conv_igemm.hpp: conv_first_min_tiles)
+extern "C" int BRATS_API(brats_conv3d_set_first_min_tiles)(int n) {
+  const int old = g_conv_first_min_tiles;
+  g_conv_first_min_tiles = n <= 0 ? CONV_FIRST_MIN_TILES : n;
+  return old;
+}
+std::atomic<unsigned long long> g_conv_form_launches[BRATS_CONV_FORM_COUNT];  // conv_igemm.hpp: conv_count_form
+extern "C" size_t BRATS_API(brats_conv3d_form_launches)(int dtype, int form) {
+  (void)dtype;  // (selects the build: twin_dispatch.cpp)
+  if (form < 0 || form >= BRATS_CONV_FORM_COUNT) return 0;
+  return (size_t)g_conv_form_launches[form].load(std::memory_order_relaxed);
+}
 bool conv_vs8_enabled() {
   if (g_conv_vs8_mode >= 0) return g_conv_vs8_mode != 0;
   static int v = -1;

@@ -706,6 +706,14 @@ int conv_launch_nf3(const ConvParams& p, hipStream_t st) {
 
 // the 4x8x16-tile kernel (conv_igemm_vs8.hpp) for the layers of its shape: BRATS_CONV_VS8 / brats_conv3d_set_vs8 (conv_host.hip)
 bool conv_vs8_enabled();
+// the first layer's two special kernels (conv_igemm_first.hpp, conv_launch_vs8<8, 1, 3>) want this many 4x4x16 tiles:
+// brats_conv3d_set_first_min_tiles (conv_host.hip)
+constexpr int CONV_FIRST_MIN_TILES = 2048;
+extern int g_conv_first_min_tiles;
+static inline long conv_first_min_tiles() { return g_conv_first_min_tiles; }
+// launches of the 16-bit 3x3x3 launchers per form (brats_conv3d_form_launches): one relaxed increment on the host
+extern std::atomic<unsigned long long> g_conv_form_launches[BRATS_CONV_FORM_COUNT];  // conv_host.hip
+static inline void conv_count_form(int form) { g_conv_form_launches[form].fetch_add(1, std::memory_order_relaxed); }
 // the 96-cout tiles of a 16-bit layer give fewer workgroups than this: the y-split roles instead (conv_launch_ck)
 constexpr long CONV_SMALL_GRID = 200;
 struct ConvTileChoice { int nf; bool ksplit; int nfw; };
@@ -719,6 +727,7 @@ static inline ConvTileChoice conv_choose_tile(int rows16) {
 
 template <typename T, int KS, int CK, int DIL, bool PRE = false>
 int conv_launch_ck(const ConvParams& p, hipStream_t st) {
+  if constexpr (std::is_same<T, bf16_t>::value && KS == 3) conv_count_form(BRATS_CONV_FORM_TILE);
   const ConvTileChoice t = conv_choose_tile(p.rows16);
   if (t.nf == 3 && !t.ksplit) {
     // small volumes (16^3 levels): 96-cout tiles give fewer workgroups than CUs; the y-split roles (48 couts per

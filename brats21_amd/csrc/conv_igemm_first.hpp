@@ -197,11 +197,14 @@ __global__ __launch_bounds__(256, 2) void conv_first_kernel(const ConvParams p, 
   }
 }
 
-// the layer this kernel is built for: one 8-channel chunk, exactly 48 output channels in a dense tensor, whole 4x4x16 tiles
+// the layer this kernel is built for: one 8-channel chunk, exactly 48 output channels in a dense tensor, whole 4x4x16 tiles;
+// enough of them to pay for the persistent walk (conv_first_min_tiles(): 2048, brats_conv3d_set_first_min_tiles), and never
+// fewer than the 8 that conv_launch_first's grid needs (one workgroup per XCD)
 static inline bool conv_first_ok(const ConvParams& p, int ck) {
+  const long ntiles = (long)p.N * p.tz * p.ty * p.tx;
   return ck == 8 && p.nchunks == 1 && p.c2 == 0 && p.stats && p.cout == 48 && p.rows16 == 3 && p.ypitch == 48 && !p.y2 && p.D % 4 == 0 &&
          p.H % 4 == 0 && p.W % 16 == 0 && ((size_t)p.y & 15) == 0 && (!p.bias || ((size_t)p.bias & 15) == 0) &&
-         (long)p.N * p.tz * p.ty * p.tx >= 2048;
+         ntiles >= 8 && ntiles >= conv_first_min_tiles();
 }
 
 static int conv_launch_first(const ConvParams& p, hipStream_t st) {
@@ -209,8 +212,12 @@ static int conv_launch_first(const ConvParams& p, hipStream_t st) {
   static std::atomic<uint64_t> attr_done{0};
   BRATS_ENSURE_LDS_ATTR(kern, FirstGeom::LDS_BYTES, attr_done);
   const int ntiles = p.N * p.tz * p.ty * p.tx;
+  // (& ~7 of fewer than 8 tiles would be an empty grid: conv_first_ok sends those to the tile kernels)
+  if (ntiles < 8) BRATS_FAIL(BRATS_E_UNSUPPORTED, "conv first layer: %d tiles, the persistent kernel needs 8", ntiles);
+  conv_count_form(BRATS_CONV_FORM_FIRST);
   const int cus = device_cus();
-  const int grid = (ntiles < 2 * cus ? ntiles : 2 * cus) & ~7;  // (a multiple of 8: the same number of workgroups on every XCD; conv_first_ok wants >= 2048 tiles)
+  int grid = (ntiles < 2 * cus ? ntiles : 2 * cus) & ~7;  // (a multiple of 8: the same number of workgroups on every XCD)
+  if (grid < 8) grid = 8;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), FirstGeom::LDS_BYTES, st, p, ntiles);
   BRATS_CHECK_LAUNCH();
   return 0;

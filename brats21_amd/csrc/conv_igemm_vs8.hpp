@@ -341,6 +341,7 @@ int conv_launch_vs8(const ConvParams& p0, hipStream_t st) {
   auto kern = conv_igemm_vs8_kernel<CK, DIL, NF, PRE, BST>;
   static std::atomic<uint64_t> attr_done{0};
   BRATS_ENSURE_LDS_ATTR(kern, lds, attr_done);
+  conv_count_form(BRATS_CONV_FORM_VS8);
   ConvParams p = p0;
   const int ty4 = p.ty;
   p.ty = ceil_div(p.H, VS8_TY);

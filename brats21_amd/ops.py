@@ -415,6 +415,24 @@ def set_vs8(mode):
     return old
 
 
+def set_first_min_tiles(n):
+    """brats_conv3d_set_first_min_tiles: the number of 4x4x16 tiles from which the first layer (one 8-channel chunk, 16-bit, 3x3x3)
+    takes its persistent kernel (dense output) or the 4x8x16-tile kernel (any other output); n <= 0 = the default of 2048.  The
+    packed weights do not depend on it.  Returns the previous value."""
+    return _lib.lib().brats_conv3d_set_first_min_tiles(int(n))
+
+
+CONV_FORM_FIRST, CONV_FORM_VS8, CONV_FORM_TILE = 0, 1, 2  # BRATS_CONV_FORM_* of include/brats_hip.h
+
+
+def conv_form_launches(dtype, form):
+    """brats_conv3d_form_launches: how many launches the 16-bit 3x3x3 launchers of `dtype`'s build (torch dtype; fp16 counts on
+    its own) have made in form CONV_FORM_FIRST / _VS8 / _TILE since the library was loaded.  Never reset: take differences."""
+    if form not in (CONV_FORM_FIRST, CONV_FORM_VS8, CONV_FORM_TILE):
+        raise _lib.BratsHipError(f"conv_form_launches: unknown form {form}")
+    return int(_lib.lib().brats_conv3d_form_launches(_code(dtype), form))
+
+
 def set_x3_wgrad_fused(mode):
     """brats_conv3d_set_x3_wgrad_fused: 1 = the fused split-precision weight gradient where it is built and pays, 2 = for any tile
     count (tests), 0 = the split pass + three 16-bit launches everywhere, -1 = default.  Returns the previous setting."""

@@ -57,7 +57,8 @@ enum { BRATS_ACT_NONE = 0, BRATS_ACT_RELU = 1, BRATS_ACT_LEAKY = 2, BRATS_ACT_EL
  * _init / _iterate / _apply; brats_conv3d_narrow_packed_bytes / _pack / _fwd; brats_softmax_stats / _grad / _planes + the workspace
  * query, brats_label_stats + its workspace query, brats_argmax_labels; the brats_cbam_* passes; brats_cbam_apply_pool, brats_cbam_bwd_reduce_pool / _bwd_apply_pool;
  * brats_upsample_nearest_fwd / _bwd, brats_planes_nearest_fwd / _bwd; brats_affine_act_add_fwd, brats_grad_sum;
- * brats_affine_act_add_pool_fwd; the brats_attgate_* passes): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
+ * brats_affine_act_add_pool_fwd; the brats_attgate_* passes;
+ * brats_conv3d_set_first_min_tiles, brats_conv3d_form_launches): an older library lacks them and says so when they are called (brats21_amd/_lib.py), and
  * tests/test_postproc_cpu.py and tests/test_gradclip_cpu.py pin the 7. */
 #define BRATS_ABI_VERSION 7
 int brats_abi_version(void);
@@ -130,6 +131,22 @@ int brats_conv3d_set_vs8(int mode);
  * partial sums through LDS: conv_igemm.hpp "KP", round 6), 0 = the 4-wave workgroup, -1 = default (BRATS_CONV_KP, on).  Same
  * packed weights, same products; the K summation order differs (two partial sums per output).  Returns the previous setting. */
 int brats_conv3d_set_kp(int mode);
+/* The 16-bit 3x3x3 dilation-1 layer with ONE 8-channel chunk (the networks' first layer: 4 modalities padded to 8) leaves the
+ * 4x4x16-tile kernels for the persistent kernel (conv_igemm_first.hpp: dense 48-channel output with statistics, whole tiles)
+ * or the 4x8x16-tile kernel with an 8-channel chunk (any other output, under brats_conv3d_set_vs8's setting) once the
+ * launch has this many 4x4x16 tiles: n > 0 sets the count, n <= 0 restores the default of 2048; returns the previous value.
+ * Whatever n says, the persistent kernel wants at least 8 tiles (one workgroup per XCD).  The switch exists so that tests reach
+ * both kernels on small volumes; it only chooses among kernels that read the same packed weights, so nothing packed has to
+ * be invalidated when it changes. */
+int brats_conv3d_set_first_min_tiles(int n);
+/* How many launches each form of the 16-bit 3x3x3 launchers has made in this process (brats_conv3d_fwd, forward and input
+ * gradient; of the normalise-on-load / backward-statistics entry points only their 4x8x16-tile launches pass a counted
+ * launcher): FIRST = the persistent first-layer kernel, VS8 = the 4x8x16-tile kernel (24- and 8-channel chunks), TILE = the
+ * 4x4x16-tile kernels behind conv_launch_ck.  `dtype` selects the build that is asked (BRATS_F16 / BRATS_X3_F16:
+ * the fp16 one, which counts on its own).  One relaxed atomic increment on the host per launch, nothing on the device; never
+ * reset -- take differences.  0 for an unknown form. */
+enum { BRATS_CONV_FORM_FIRST = 0, BRATS_CONV_FORM_VS8 = 1, BRATS_CONV_FORM_TILE = 2, BRATS_CONV_FORM_COUNT = 3 };
+size_t brats_conv3d_form_launches(int dtype, int form);
 /* y2 (may be NULL): second destination; output channels >= ysplit are written to y2 (channel index
  * minus ysplit, pitch y2pitch) -- the dgrad of a conv whose input was [x1 | x2] produces dx1 and dx2
  * as two dense tensors in one launch. */

@@ -1,5 +1,5 @@
 """Exact integer-operand references for the convolution kernels (tests/test_conv_exact_cpu.py, tests/test_conv_exact_gpu.py,
-tests/test_dconv_exact_gpu.py).
+tests/test_first_layer_gpu.py, tests/test_dconv_exact_gpu.py).
 
 The technique: every element of x, dy, w (and the bias) is a small integer, exact in bf16, fp16, f32, e4m3 and in the hi
 half of a split-precision pair.  Every product is then an integer, and while the worst-case sum of absolute values stays
@@ -187,6 +187,130 @@ def assert_stats_exact(stats, y_ref, squares=True, what=""):
     if squares:
         require_stats_exact(y_ref)
         assert torch.equal(s[..., 1], r2), f"{what}: sum of y^2 differs at {int((s[..., 1] != r2).sum())} of {r2.numel()} entries"
+
+
+TILE_Z, TILE_Y, TILE_X = 4, 4, 16  # the statistics tile of every convolution kernel (CONV_TZ, CONV_TY, CONV_TX of csrc/conv_igemm.hpp)
+
+
+def tile_stats_ref(y_ref):
+    """(sum y, sum y^2) of the unrounded result per 4x4x16 tile: float64 [N, tz * ty * tx, cout, 2] in the library's tile order
+    (x fastest, then y, then z); the tiles at the far faces of a ragged volume are clipped to it."""
+    n, d, h, w, c = y_ref.shape
+    tz, ty, tx = -(-d // TILE_Z), -(-h // TILE_Y), -(-w // TILE_X)
+    yp = torch.zeros((n, tz * TILE_Z, ty * TILE_Y, tx * TILE_X, c), dtype=torch.float64)
+    yp[:, :d, :h, :w] = y_ref.double()
+    yt = yp.reshape(n, tz, TILE_Z, ty, TILE_Y, tx, TILE_X, c)
+    return torch.stack([yt.sum((2, 4, 6)), (yt * yt).sum((2, 4, 6))], -1).reshape(n, tz * ty * tx, c, 2)
+
+
+@functools.lru_cache(maxsize=None)
+def _tile_stats_cached(y_ref):
+    """(tile_stats_ref, the largest per-(tile, channel) sum of |y|) of a shared, unchanged reference (keyed by the tensor object)."""
+    return tile_stats_ref(y_ref), float(tile_stats_ref(y_ref.double().abs())[..., 0].max())
+
+
+def tile_stats_exact_ok(y_ref, squares=True):
+    """The precondition of assert_tile_stats_exact: per (tile, channel) the sum of |y| -- and, with squares, of y^2 -- is below
+    2^24, which bounds every partial sum of either in any order."""
+    ref, tot = _tile_stats_cached(y_ref)
+    return tot < EXACT and (not squares or float(ref[..., 1].max()) < EXACT)
+
+
+def assert_tile_stats_exact(stats, y_ref, squares=True, what=""):
+    """The tile statistics [N, tiles, cout, 2] equal the reference's per-tile sums entry by entry.  assert_stats_exact adds the
+    tiles up first, so sums written to another tile's slot of the same sample pass it; here they do not."""
+    ref, tot = _tile_stats_cached(y_ref)
+    assert tot < EXACT, f"tile statistics precondition violated: per-(tile, channel) sum of |y| = {tot:.0f} >= 2^24"
+    s = stats.detach().double().cpu()
+    assert s.shape == ref.shape, f"{what}: statistics shape {tuple(s.shape)} != {tuple(ref.shape)}"
+
+    def compare(e, name):
+        if not torch.equal(s[..., e], ref[..., e]):
+            bad = (s[..., e] != ref[..., e]).nonzero()
+            first = tuple(int(i) for i in bad[0])
+            raise AssertionError(f"{what}: per-tile sum of {name} differs at {bad.shape[0]} of {ref[..., e].numel()} (n, tile, channel) "
+                                 f"entries; first at {first}: got {float(s[..., e][first])}, want {float(ref[..., e][first])}")
+    compare(0, "y")
+    if squares:
+        tot2 = float(ref[..., 1].max())
+        assert tot2 < EXACT, f"tile statistics precondition violated: per-(tile, channel) sum of y^2 = {tot2:.0f} >= 2^24"
+        compare(1, "y^2")
+
+
+# ------------------------------------------------------------------------------------------ mirror of csrc/conv_igemm_first.hpp
+FIRST_MIN_TILES = 2048  # CONV_FIRST_MIN_TILES: the default of brats_conv3d_set_first_min_tiles
+
+
+def first_walk(ntiles, ncu):
+    """The tile walk of conv_first_kernel as conv_launch_first starts it on a device of `ncu` CUs -- the arithmetic of the
+    launcher's grid line and of the kernel's three walk lines (per_xcd / wg_per_xcd, t_lo / t_hi, the loop) copied.
+    -> namespace(grid, per_xcd, wg_per_xcd, slices = [(t_lo, t_hi)] per XCD, tiles = [[tile, ...]] per workgroup, trips)."""
+    assert ntiles >= 8
+    grid = max(min(ntiles, 2 * ncu) & ~7, 8)
+    per_xcd, wg_per_xcd = (ntiles + 7) >> 3, grid >> 3
+    slices = [(x * per_xcd, min(ntiles, x * per_xcd + per_xcd)) for x in range(8)]
+    tiles = []
+    for b in range(grid):
+        t_lo, t_hi = slices[b & 7]
+        tiles.append(list(range(t_lo + (b >> 3), t_hi, wg_per_xcd)))
+    return SimpleNamespace(ntiles=ntiles, grid=grid, per_xcd=per_xcd, wg_per_xcd=wg_per_xcd, slices=slices, tiles=tiles,
+                           trips=[len(t) for t in tiles])
+
+
+def first_layer_form(n, size, min_tiles=FIRST_MIN_TILES, dense=True, aligned=True, stats=True, vs8=True):
+    """"first" | "vs8" | "tile": what conv_launch<bf16_t, 3, 1> does with an 8 -> 48 layer (conv_first_ok, then the ck == 8 rule)."""
+    d, h, w = size
+    ntiles = n * ceil_div(d, TILE_Z) * ceil_div(h, TILE_Y) * ceil_div(w, TILE_X)
+    if dense and aligned and stats and d % 4 == 0 and h % 4 == 0 and w % 16 == 0 and ntiles >= 8 and ntiles >= min_tiles:
+        return "first"
+    return "vs8" if vs8 and ntiles >= min_tiles else "tile"
+
+
+def ntiles_of(n, size):
+    return n * ceil_div(size[0], TILE_Z) * ceil_div(size[1], TILE_Y) * ceil_div(size[2], TILE_X)
+
+
+# the volumes of tests/test_first_layer_gpu.py, named by their tile count: n, (d, h, w)
+FIRST_WALKS = {8: (1, (8, 16, 16)), 9: (1, (12, 12, 16)), 36: (2, (8, 12, 48)), 525: (1, (20, 28, 240)), 1170: (1, (36, 52, 160))}
+FIRST_NOBIAS = (36, 1170)                               # these run without a bias as well
+FIRST_RAGGED = [(2, (9, 21, 37)), (1, (12, 20, 40))]    # no whole tiles / H a multiple of 4 and not of 8: the slice kernel only
+FIRST_DEFAULT = [(1, (36, 60, 272)), (1, (36, 52, 240))]  # 2295 and 1755 tiles: above and below the default threshold
+
+
+def first_walk_properties(ntiles, n, ncu):
+    """What the volume with `ntiles` tiles (FIRST_WALKS, FIRST_DEFAULT[0]) is in the tests for, evaluated on the walk a device of
+    `ncu` CUs makes: [(description, holds)].  The GPU tests assert every one as a precondition -- on a device with another CU count
+    a shape that no longer exercises its property fails there by name and is not silently weaker."""
+    w = first_walk(ntiles, ncu)
+    tps = ntiles // n
+    lens = [max(hi - lo, 0) for lo, hi in w.slices]
+    xcd = [[w.trips[b] for b in range(x, w.grid, 8)] for x in range(8)]  # trip counts of each XCD's workgroups, in walk order
+    once = sorted(t for ts in w.tiles for t in ts) == list(range(ntiles))
+    props = [("the mirrored walk visits every tile exactly once", once)]
+    if ntiles == 8:
+        props += [("grid 8", w.grid == 8), ("one tile per workgroup: no prefetch anywhere", set(w.trips) == {1})]
+    elif ntiles == 9:
+        props += [("grid 8, below 2 * CUs", w.grid == 8 < 2 * ncu), ("per_xcd 2", w.per_xcd == 2),
+                  ("XCDs 0-3 do two tiles (both halo buffers), XCD 4 one", w.trips[:5] == [2, 2, 2, 2, 1]),
+                  ("XCDs 5-7 have t_lo > ntiles", all(lo > ntiles for lo, _ in w.slices[5:]) and w.trips[5:] == [0, 0, 0])]
+    elif ntiles == 36:
+        props += [("grid 32 (ntiles & ~7), below 2 * CUs", w.grid == 32 < 2 * ncu), ("per_xcd 5 over 4 workgroups", (w.per_xcd, w.wg_per_xcd) == (5, 4)),
+                  ("unequal trip counts inside an XCD", xcd[0] == [2, 1, 1, 1]),
+                  ("a slice crosses the sample boundary", any(lo < tps < hi for lo, hi in w.slices)),
+                  ("the last slice has one tile and three idle workgroups", lens[7] == 1 and xcd[7] == [1, 0, 0, 0])]
+    elif ntiles == 525:
+        props += [("grid capped at 2 * CUs", w.grid == 2 * ncu < ntiles), ("per_xcd no multiple of the workgroups", w.per_xcd % w.wg_per_xcd != 0),
+                  ("one or two tiles per workgroup in the full slices", set(xcd[0]) == {1, 2}),
+                  ("the last slice is shorter than its workgroups: the last one has no tile", 0 < lens[7] < w.wg_per_xcd and xcd[7][-1] == 0)]
+    elif ntiles == 1170:
+        props += [("grid capped at 2 * CUs", w.grid == 2 * ncu), ("two and three tiles per workgroup", set(w.trips) == {2, 3}),
+                  ("the last slice is shorter", 0 < lens[7] < w.per_xcd)]
+    elif ntiles == 2295:
+        props += [("an odd tile count at or above the default threshold", ntiles % 2 == 1 and ntiles >= FIRST_MIN_TILES),
+                  ("four and five tiles per workgroup", set(w.trips) == {4, 5}), ("the last slice is one tile shorter", lens[7] == w.per_xcd - 1)]
+    else:
+        raise AssertionError(f"no walk properties written down for {ntiles} tiles")
+    return props
 
 
 # ------------------------------------------------------------------------------------------ mirror of csrc/conv_wgrad.hip

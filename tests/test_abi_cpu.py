@@ -74,6 +74,50 @@ def test_host_side_queries_and_argument_errors():
     assert l.brats_gn_bwd_head_ws_floats(2, 48, 3) == 2 * 2048 * (3 * 48 + 3)
 
 
+def test_first_layer_threshold_switch_and_launch_counters():
+    """brats_conv3d_set_first_min_tiles / brats_conv3d_form_launches: declared, bound, host-only; additions that leave the ABI at 7."""
+    from brats21_amd import ops
+    l = _lib.lib()
+    sigs = _lib._parse_header()
+    assert sigs["brats_conv3d_set_first_min_tiles"] == ("i", "i") and sigs["brats_conv3d_form_launches"] == ("z", "ii")
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for n in ("brats_conv3d_set_first_min_tiles", "brats_conv3d_form_launches"):
+        for suffix in ("", "_bf16", "_f16"):  # the dispatcher and both builds behind it
+            assert hasattr(raw, n + suffix), n + suffix
+    assert l.brats_abi_version() == 7 == _lib._header_abi_version()
+    # the setter returns the previous value; n <= 0 restores the default of 2048
+    first = l.brats_conv3d_set_first_min_tiles(8)
+    try:
+        assert first == 2048
+        assert l.brats_conv3d_set_first_min_tiles(100) == 8
+        assert l.brats_conv3d_set_first_min_tiles(0) == 100
+        assert l.brats_conv3d_set_first_min_tiles(-5) == 2048
+        assert l.brats_conv3d_set_first_min_tiles(1) == 2048
+        assert ops.set_first_min_tiles(first) == 1 and ops.set_first_min_tiles(first) == first
+        # both builds carry the state: each one's own entry point reports the value set through the dispatcher
+        for suffix in ("_bf16", "_f16"):
+            fn = getattr(raw, "brats_conv3d_set_first_min_tiles" + suffix)
+            fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_int]
+            assert fn(first) == first
+    finally:
+        l.brats_conv3d_set_first_min_tiles(first)
+    # the counters read without a device, for every dtype code and form; an unknown form reads 0
+    forms = (ops.CONV_FORM_FIRST, ops.CONV_FORM_VS8, ops.CONV_FORM_TILE)
+    assert forms == (0, 1, 2)
+    for code in (_lib.BF16, _lib.F16, _lib.X3_BF16, _lib.X3_F16, _lib.F32):
+        for form in forms:
+            assert l.brats_conv3d_form_launches(code, form) >= 0
+        assert l.brats_conv3d_form_launches(code, 3) == 0 and l.brats_conv3d_form_launches(code, -1) == 0
+    for dtype in (torch.bfloat16, torch.float16):
+        assert all(isinstance(ops.conv_form_launches(dtype, f), int) and ops.conv_form_launches(dtype, f) >= 0 for f in forms)
+    with pytest.raises(_lib.BratsHipError):
+        ops.conv_form_launches(torch.bfloat16, 3)
+    # a launch refused before it reaches a launcher counts nothing
+    before = [l.brats_conv3d_form_launches(_lib.BF16, f) for f in forms]
+    assert l.brats_conv3d_fwd(None, 8, 8, None, 0, 0, None, None, None, 8, None, 0, 0, None, _lib.BF16, 3, 1, 1, 8, 8, 8, 8, None) == -1
+    assert [l.brats_conv3d_form_launches(_lib.BF16, f) for f in forms] == before
+
+
 def test_state_dict_contract_and_factory_errors():
     from brats21_amd import get_model
     from oracle import unet

@@ -157,6 +157,161 @@ def test_mirror_of_the_weight_gradient_host_rules():
     assert (s["ntiles"], s["nlane"], s["cof"], s["cif"], s["nsplit"]) == (4, 1, 3, 3, 4)
 
 
+# ---------------------------------------------------------------------------------------------- first layer: per-tile statistics, walk
+def test_tile_statistics_reference_and_what_the_summed_check_cannot_see():
+    """tile_stats_ref against a loop over the clipped tiles of a ragged volume; then a correct statistics tensor with two tile rows
+    of one sample swapped: the summed comparison (assert_stats_exact) passes it, the per-tile one reports it."""
+    x, _, w, bias, y_ref = R.fwd_case(8, 0, 48, 2, (9, 6, 37), real_cin=4)
+    ref = R.tile_stats_ref(y_ref)
+    tz, ty, tx = 3, 2, 3
+    assert ref.shape == (2, tz * ty * tx, 48, 2) and ref.dtype == torch.float64
+    for n in range(2):
+        for t in range(tz * ty * tx):
+            z, y, xx = t // (ty * tx), t // tx % ty, t % tx   # x fastest, then y, then z
+            blk = y_ref[n, 4 * z:4 * z + 4, 4 * y:4 * y + 4, 16 * xx:16 * xx + 16].double()
+            assert blk.numel() > 0
+            assert torch.equal(ref[n, t, :, 0], blk.sum((0, 1, 2))) and torch.equal(ref[n, t, :, 1], (blk * blk).sum((0, 1, 2)))
+    assert R.tile_stats_exact_ok(y_ref) and R.stats_exact_ok(y_ref)
+    good = ref.float()
+    R.assert_stats_exact(good, y_ref, what="summed")
+    R.assert_tile_stats_exact(good, y_ref, what="per tile")
+    swapped = good.clone()
+    swapped[1, 4], swapped[1, 11] = good[1, 11], good[1, 4]
+    assert not torch.equal(swapped, good)
+    R.assert_stats_exact(swapped, y_ref, what="summed")          # the old check cannot see it
+    with pytest.raises(AssertionError, match="per-tile sum of y differs at"):
+        R.assert_tile_stats_exact(swapped, y_ref, what="per tile")
+    sq = good.clone()
+    sq[0, 7, 5, 1] += 1                                            # one sum of squares off by one
+    with pytest.raises(AssertionError, match="per-tile sum of y\\^2 differs at 1 of"):
+        R.assert_tile_stats_exact(sq, y_ref, what="per tile")
+    R.assert_tile_stats_exact(sq, y_ref, squares=False, what="per tile")
+    # the preconditions, asserted on the reference alone: one tile of 256 voxels at 2^16 sums to 2^24; at 256, its squares do
+    with pytest.raises(AssertionError, match="sum of \\|y\\| = 16777216 >= 2\\^24"):
+        R.assert_tile_stats_exact(good, torch.full((1, 4, 4, 16, 2), 2.0 ** 16))
+    y256 = torch.full((1, 4, 4, 16, 2), 256.0)
+    s256 = R.tile_stats_ref(y256).float()
+    with pytest.raises(AssertionError, match="sum of y\\^2 = 16777216 >= 2\\^24"):
+        R.assert_tile_stats_exact(s256, y256)
+    R.assert_tile_stats_exact(s256, y256, squares=False)
+    assert not R.tile_stats_exact_ok(y256) and R.tile_stats_exact_ok(y256, squares=False) and R.tile_stats_exact_ok(y256 / 2)
+
+
+def test_mirror_of_the_first_layer_walk_and_dispatch():
+    """first_walk / first_layer_form: values worked out by hand from csrc/conv_igemm_first.hpp and csrc/conv_bf16_k3_d1.hip for a
+    256-CU device, and every property the GPU volumes are listed for."""
+    for ntiles, (n, size) in list(R.FIRST_WALKS.items()) + [(2295, R.FIRST_DEFAULT[0])]:
+        assert R.ntiles_of(n, size) == ntiles
+        for what, holds in R.first_walk_properties(ntiles, n, 256):
+            assert holds, (ntiles, what)
+    w = R.first_walk(9, 256)
+    assert (w.grid, w.per_xcd, w.wg_per_xcd) == (8, 2, 1) and w.slices[4:] == [(8, 9), (10, 9), (12, 9), (14, 9)]
+    assert w.tiles == [[0, 1], [2, 3], [4, 5], [6, 7], [8], [], [], []]
+    w = R.first_walk(36, 256)
+    assert w.slices[3] == (15, 20) and w.slices[7] == (35, 36) and w.tiles[0] == [0, 4] and w.tiles[8] == [1] and w.tiles[31] == []
+    w = R.first_walk(525, 256)
+    assert (w.grid, w.per_xcd, w.wg_per_xcd) == (512, 66, 64) and w.slices[7] == (462, 525) and w.tiles[0] == [0, 64] and w.tiles[16] == [2]
+    assert w.tiles[7 + 8 * 62] == [462 + 62] and w.tiles[7 + 8 * 63] == []
+    w = R.first_walk(1170, 256)
+    assert (w.per_xcd, w.slices[7][1] - w.slices[7][0]) == (147, 141) and w.trips.count(3) == 7 * 19 + 13
+    w = R.first_walk(2295, 256)
+    assert (w.per_xcd, w.slices[7][1] - w.slices[7][0]) == (287, 286)
+    w = R.first_walk(2048, 256)                                   # the one shape the suite ran before: even in every respect
+    assert set(w.trips) == {4} and all(hi - lo == 256 for lo, hi in w.slices)
+    assert R.first_walk(12, 2).grid == 8                          # never an empty grid
+    # the dispatch: conv_first_ok, then the ck == 8 rule
+    assert R.first_layer_form(1, (64, 64, 128)) == "first" and R.first_layer_form(1, (64, 64, 128), dense=False) == "vs8"
+    assert R.first_layer_form(1, (64, 64, 128), dense=False, vs8=False) == "tile" and R.first_layer_form(2, (32, 64, 64)) == "tile"
+    assert R.first_layer_form(1, (36, 52, 240)) == "tile" and R.first_layer_form(1, (36, 60, 272)) == "first"
+    assert R.first_layer_form(1, (28, 4, 16), 8) == "tile" and R.first_layer_form(1, (28, 4, 16), 1) == "vs8"
+    assert R.first_layer_form(1, (12, 12, 24), 8) == "vs8" and R.first_layer_form(1, (8, 16, 16), 8, aligned=False) == "vs8"
+    assert R.first_layer_form(1, (8, 16, 16), 8, stats=False) == "vs8" and R.first_layer_form(1, (8, 16, 16), 8) == "first"
+    for n, size in R.FIRST_RAGGED:
+        assert R.first_layer_form(n, size, 8) == "vs8"
+
+
+@pytest.mark.parametrize("real_cin", [4, 8])
+def test_first_layer_cases_meet_the_per_tile_bound_on_dense_operands(real_cin):
+    """Every volume of tests/test_first_layer_gpu.py up to 1170 tiles, built here: the dense operand set meets the per-tile bounds
+    of assert_tile_stats_exact (sum of |y| and of y^2 below 2^24 per tile and channel), so none of them needs the thinned set --
+    although the two largest miss the per-sample bound of the summed check.  (The sum of |y| cannot miss: 1024 voxels x
+    (27 taps x 8 channels x 2 x 2 + 2) = 886,784.  The two volumes of the default-threshold test assert the same when they run.)"""
+    cases = [(n, size, True) for n, size in list(R.FIRST_WALKS.values()) + R.FIRST_RAGGED + [(1, (28, 4, 16)), (1, (12, 12, 24))]]
+    cases.append((*R.FIRST_WALKS[36], False))
+    if real_cin == 4:   # (half the terms per output: the two large volumes are built once, with all 8 channels)
+        cases = [c for c in cases if R.ntiles_of(c[0], c[1]) < 500]
+    per_sample = {}
+    for n, size, with_bias in cases:
+        y_ref = R.fwd_case(8, 0, 48, n, size, with_bias=with_bias, real_cin=real_cin)[4]
+        assert R.tile_stats_exact_ok(y_ref), (n, size, with_bias)
+        assert float(R.tile_stats_ref(y_ref)[..., 1].max()) < R.EXACT / 4, (n, size)   # not by a hair either
+        per_sample[(n, size)] = R.stats_exact_ok(y_ref)
+    assert per_sample[(2, (8, 12, 48))]
+    assert real_cin == 4 or (not per_sample[(1, (36, 52, 160))] and not per_sample[(1, (20, 28, 240))])
+
+
+def _emulated_first_kernel(y_ref, n, ncu, rig=None):
+    """What conv_first_kernel leaves behind in an output full of 7s and a statistics buffer full of NaN if its walk is the mirrored
+    one and every visited tile gets the reference's values -- or, rigged, with one of three faults put into conv_launch_first's kernel:
+    "skip_last": the last tile of every XCD slice is not done; "slot_t": a tile's statistics go to slot t instead of t % tps (a
+    slot beyond the buffer is dropped here; on the device it would be a write out of bounds); "no_flip": cur ^= 1 is dropped,
+    so from its second tile on a workgroup computes on the halo buffer of its first."""
+    _, d, h, w, c = y_ref.shape
+    tz, ty, tx = d // 4, h // 4, w // 16
+    tps = tz * ty * tx
+    walk = R.first_walk(n * tps, ncu)
+    ref = R.tile_stats_ref(y_ref)
+    y = torch.full(y_ref.shape, 7.0, dtype=torch.float64)
+    stats = torch.full((n * tps, c, 2), float("nan"), dtype=torch.float64)
+
+    def block(t):
+        s, r = t // tps, t % tps
+        z, yy, x = r // (ty * tx), r // tx % ty, r % tx
+        return (s, slice(4 * z, 4 * z + 4), slice(4 * yy, 4 * yy + 4), slice(16 * x, 16 * x + 16))
+    for b, tiles in enumerate(walk.tiles):
+        for k, t in enumerate(tiles):
+            if rig == "skip_last" and t == walk.slices[b & 7][1] - 1:
+                continue
+            src = tiles[0] if rig == "no_flip" and k else t
+            y[block(t)] = y_ref[block(src)].double()
+            slot = (t // tps) * tps + (t if rig == "slot_t" else t % tps)
+            if slot < n * tps:
+                stats[slot] = ref[src // tps, src % tps]
+    return y, stats.reshape(n, tps, c, 2)
+
+
+@pytest.mark.parametrize("ntiles", [8, 9, 36])
+def test_the_first_layer_checks_see_a_rigged_walk(ntiles):
+    """The evidence that the GPU cases would fail on a subtly wrong persistent kernel, from the walk mirror and the reference (no
+    rigged kernel is run on a device: the second fault writes out of bounds there).  Unrigged, the emulation passes the two
+    assertions the GPU tests make; a skipped last tile of a slice fails both on every volume; statistics in slot t fail on the
+    two-sample volume (36 tiles), the only way to tell t from t % tps; a dropped buffer flip fails wherever a workgroup has a
+    second tile (9 and 36 tiles; not 8: no workgroup prefetches there)."""
+    n, size = R.FIRST_WALKS[ntiles]
+    y_ref = R.fwd_case(8, 0, 48, n, size, real_cin=4)[4]
+
+    def check(rig):
+        y, stats = _emulated_first_kernel(y_ref, n, 256, rig)
+        R.assert_exact(y.float().to(torch.bfloat16), y_ref, torch.bfloat16, what="y")
+        R.assert_tile_stats_exact(stats.float(), y_ref, what="stats")
+    check(None)
+    with pytest.raises(AssertionError, match="y: .* entries differ"):
+        check("skip_last")
+    y, stats = _emulated_first_kernel(y_ref, n, 256, "skip_last")
+    with pytest.raises(AssertionError, match="per-tile sum of y differs"):
+        R.assert_tile_stats_exact(stats.float(), y_ref, what="stats")
+    if n > 1:
+        with pytest.raises(AssertionError, match="per-tile sum of y differs"):
+            check("slot_t")
+    else:
+        check("slot_t")     # one sample: t == t % tps, nothing to see
+    if ntiles > 8:
+        with pytest.raises(AssertionError, match="y: .* entries differ"):
+            check("no_flip")
+    else:
+        check("no_flip")
+
+
 # ---------------------------------------------------------------------------------------------- direct (gather) convolution
 def _torch_term(x, w, dy, k, dil):
     """F.conv3d (padding = dilation for k = 3) and its autograd input gradient, channels-last f32."""

@@ -308,16 +308,28 @@ def test_e4m3_forward(dtype, cin, cin2, cout, dil, size):
 
 
 # ---------------------------------------------------------------------------------------------- 8. forward and input gradient
-def _fwd(dtype, c1, c2, cout, n, size, dil=1, k=3, views=False, real_cin=None, out_slice=False, x3=None, chunk=None):
+def _poison(numel, dtype=torch.float32):
+    """Hands the caching allocator blocks full of NaN for the next torch.empty of this size, so that a statistics slot or output
+    voxel the kernel leaves unwritten is not found holding an earlier, identical run's correct value."""
+    blocks = [torch.full((numel,), float("nan"), dtype=dtype, device=_dev()) for _ in range(4)]
+    torch.cuda.synchronize()
+    del blocks
+
+
+def _fwd(dtype, c1, c2, cout, n, size, dil=1, k=3, views=False, real_cin=None, out_slice=False, x3=None, chunk=None,
+         with_bias=True, tile_stats=False, out_base=None, want_stats=True):
     """conv3d on integer operands: y bit-equal after rounding to the storage type, the tile statistics summed over the tiles
     equal to the reference's sums (sum of y on the dense operands; sum of y^2 on the dense operands where their reference meets
-    the bound, otherwise on a second, thinned operand set).  -> [(y, stats)] of the runs."""
+    the bound, otherwise on a second, thinned operand set).  tile_stats: the statistics are compared per tile instead
+    (assert_tile_stats_exact, sum of y and of y^2), on the dense operands alone -- their per-tile bound is asserted, not worked
+    around.  out_base (an element count): the dense output is a view that far into a flat buffer full of 7s (0: a prefilled
+    tensor), so that a tile nobody writes is seen.  -> [(y, stats)] of the runs."""
     from brats21_amd import ops
     dev = _dev()
-    dense = R.fwd_case(c1, c2, cout, n, size, dil, k, real_cin=real_cin)
-    runs = [(dense, R.stats_exact_ok(dense[4]))]
+    dense = R.fwd_case(c1, c2, cout, n, size, dil, k, with_bias=with_bias, real_cin=real_cin)
+    runs = [(dense, tile_stats or R.stats_exact_ok(dense[4]))]
     if not runs[0][1]:
-        runs.append((R.fwd_case(c1, c2, cout, n, size, dil, k, thin=True, real_cin=real_cin), True))
+        runs.append((R.fwd_case(c1, c2, cout, n, size, dil, k, thin=True, with_bias=with_bias, real_cin=real_cin), True))
     outs = []
     for (x, x2, w, bias, y_ref), squares in runs:
         xd = _dv(x, dtype, c1 + 16 if views else None, 8)
@@ -330,13 +342,26 @@ def _fwd(dtype, c1, c2, cout, n, size, dil=1, k=3, views=False, real_cin=None, o
             if out_slice:
                 wide = torch.full((n, *size, cout + 48), 7.0, dtype=dtype, device=dev)
                 out = wide[..., 16:16 + cout]
-            y, stats = ops.conv3d(xd, wpk, cout, k, dil, bias=bias.to(dev), want_stats=True, x2=x2d, out=out)
+            elif out_base is not None:
+                flat = torch.full((out_base + y_ref.numel() + 8,), 7.0, dtype=dtype, device=dev)
+                out = flat[out_base:out_base + y_ref.numel()].view(n, *size, cout)
+            if tile_stats and want_stats:
+                _poison(n * ops.tiles_per_sample(*size) * cout * 2)
+            y, stats = ops.conv3d(xd, wpk, cout, k, dil, bias=bias.to(dev) if with_bias else None, want_stats=want_stats, x2=x2d, out=out)
         torch.cuda.synchronize()
         R.assert_exact(y, y_ref, dtype, what=f"y {c1}+{c2}->{cout} k{k} d{dil}")
-        R.assert_stats_exact(stats, y_ref, squares=squares, what="tile statistics")
+        if not want_stats:
+            assert stats is None
+        elif tile_stats:
+            R.assert_tile_stats_exact(stats, y_ref, squares=True, what="tile statistics")
+        else:
+            R.assert_stats_exact(stats, y_ref, squares=squares, what="tile statistics")
         if out_slice:
             assert float(wide[..., :16].float().min()) == 7.0 and float(wide[..., 16 + cout:].float().max()) == 7.0
             assert float(wide[..., :16].float().max()) == 7.0 and float(wide[..., 16 + cout:].float().min()) == 7.0
+        elif out_base is not None:
+            assert y.data_ptr() == flat.data_ptr() + out_base * flat.element_size()
+            assert bool((flat[:out_base].float() == 7.0).all()) and bool((flat[out_base + y_ref.numel():].float() == 7.0).all())
         outs.append((y, stats))
     return outs
 
@@ -405,11 +430,28 @@ def test_vs8_form_forward_and_input_gradient(dtype, cin, cin2, cout, n, size, vs
 
 @pytest.mark.parametrize("dtype", [BF, FH])
 def test_first_layer_and_cout48_kernels(dtype):
-    """The persistent first-layer kernel (8 -> 48, dense output) and the same call into a channel slice (the tile kernel); the
-    Cout = 48 kernels on a two-source ragged volume with the 4x8x16-tile switch on."""
+    """The persistent first-layer kernel (8 -> 48, dense output) and the same call into a channel slice (the 4x8x16-tile kernel with
+    an 8-channel chunk); the Cout = 48 kernels on a two-source ragged volume with the 4x8x16-tile switch on.  2 x (32, 64, 64) is
+    1024 tiles, below the 2048 from which the library takes either first-layer kernel by itself: the pair runs with the
+    threshold switched to 8, and the launch counters say which form ran (one launch per operand set).  The walk shapes of
+    the persistent kernel are the business of tests/test_first_layer_gpu.py."""
     from brats21_amd import ops
-    new = _fwd(dtype, 8, 0, 48, 2, (32, 64, 64), real_cin=4)
-    old = _fwd(dtype, 8, 0, 48, 2, (32, 64, 64), real_cin=4, out_slice=True)
+    forms = (ops.CONV_FORM_FIRST, ops.CONV_FORM_VS8, ops.CONV_FORM_TILE)
+
+    def count():
+        return [ops.conv_form_launches(dtype, f) for f in forms]
+    old_min, old_vs8 = ops.set_first_min_tiles(8), ops.set_vs8(1)
+    try:
+        c0 = count()
+        new = _fwd(dtype, 8, 0, 48, 2, (32, 64, 64), real_cin=4)
+        c1 = count()
+        old = _fwd(dtype, 8, 0, 48, 2, (32, 64, 64), real_cin=4, out_slice=True)
+        c2 = count()
+    finally:
+        ops.set_vs8(old_vs8)
+        ops.set_first_min_tiles(old_min)
+    assert [b - a for a, b in zip(c0, c1)] == [len(new), 0, 0], "the dense output must take the persistent first-layer kernel"
+    assert [b - a for a, b in zip(c1, c2)] == [0, len(old), 0], "the channel slice must take the 4x8x16-tile kernel"
     assert len(new) == len(old) and all(torch.equal(a[0], b[0].contiguous()) for a, b in zip(new, old))
     old = ops.set_vs8(1)
     try:

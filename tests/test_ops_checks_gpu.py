@@ -72,7 +72,7 @@ def test_the_stand_in_splits_the_abi_by_the_stream_parameter():
     assert launch < every and len(launch) > 50
     assert {"brats_conv3d_fwd", "brats_cbam_pool", "brats_staple_iterate", "brats_dconv_run"} <= launch
     assert not launch & {"brats_conv3d_chunk", "brats_conv3d_packed_bytes", "brats_gn_ws_doubles", "brats_conv3d_set_kp",
-                         "brats_conv3d_pre_ok", "brats_abi_version", "brats_last_error"}
+                         "brats_conv3d_set_first_min_tiles", "brats_conv3d_form_launches", "brats_conv3d_pre_ok", "brats_abi_version", "brats_last_error"}
 
 
 # ------------------------------------------------------------------------------------------ arguments and their corruptions
@@ -324,7 +324,7 @@ NO_LAUNCH = {"conv3d_wgrad_f8_ok": lambda: ops.conv3d_wgrad_f8_ok(_act(), _act()
              "head_fold_ok": lambda: ops.head_fold_ok(_f(K, C, 1, 1, 1), "relu", None)}
 NO_TENSOR = {name: "takes no tensor" for name in (
     "KernelTimer", "split_precision", "x3_active", "x3_mode", "is16", "new_act", "conv_chunk", "invalidate_packed_weights", "pack_generation",
-    "keep_packed", "PackPlan", "use_plan", "plan_for", "set_kp", "set_vs8", "set_x3_wgrad_fused", "split_granule", "tiles_per_sample",
+    "keep_packed", "PackPlan", "use_plan", "plan_for", "set_kp", "set_vs8", "set_first_min_tiles", "conv_form_launches", "set_x3_wgrad_fused", "split_granule", "tiles_per_sample",
     "conv_pre_ok", "set_f8_min_size", "conv_f8_chunk", "conv_bstats_ok", "set_upsample_bwd_fused", "CbamSaved", "RrcnnSaved", "probe_box")}
 NAMES = ["ncdhw_to_ndhwc", "ndhwc_to_ncdhw", "pack_weights", "pack_weights_f8", "pack_weights_direct", "pack_weights_narrow", "conv3d", "Pending",
          "conv3d_narrow", "absmax", "conv3d(x2, split)", "conv3d_f8(x2)", "conv3d_f8", "conv3d_wgrad", "conv3d_wgrad_shift", "conv3d_wgrad_f8",

@@ -610,13 +610,19 @@ def test_conv3d_first_layer_weight_gradient_vs_torch(dtype, n, size):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("n,size,with_bias", [(2, (32, 64, 64), True), (1, (64, 64, 128), False), (1, (36, 52, 240), True)])
+@pytest.mark.parametrize("n,size,with_bias", [(2, (32, 64, 64), True), (1, (64, 64, 128), False), (1, (36, 52, 240), True),
+                                                (1, (68, 60, 272), True)])
 def test_conv3d_first_layer_kernel(dtype, n, size, with_bias):
-    """The first layer (4 modalities padded to 8 channels -> 48, networks/equiunet2020.py:424) on the persistent kernel of
-    csrc/conv_igemm_first.hpp (weights in registers for the whole launch, output tile through LDS into 1 KB contiguous stores):
-    (i) bit-identical outputs to the 4x8x16-tile kernel, which the same call takes when the output is a channel slice of a wider
-    buffer (same packed weights, same K order, f32 accumulation from the bias), tile statistics equal to 1e-5; every face of
-    the volume is a boundary tile, the third case has 13 and 15 tiles per row (odd counts for the persistent walk);
+    """The first layer (4 modalities padded to 8 channels -> 48, networks/equiunet2020.py:424) under the library's own rule: from
+    2048 tiles of 4x4x16 voxels on, a dense output takes the persistent kernel of csrc/conv_igemm_first.hpp (weights in registers for
+    the whole launch, output tile through LDS into 1 KB contiguous stores) and a channel slice of a wider buffer the 4x8x16-tile
+    kernel; below, both take the 4x4x16-tile kernel.  1 x (64, 64, 128) -- exactly 2048 tiles, an even walk: four tiles for every
+    workgroup of a 256-CU device -- and 1 x (68, 60, 272) -- 4335 tiles, an odd count, eight or nine per workgroup, the last XCD's
+    slice one short -- reach the persistent kernel; 2 x (32, 64, 64) has 1024 tiles and 1 x (36, 52, 240) has 1755 (13 and 15 tiles
+    per row), so their two runs are the tile kernel twice.  The launch counters assert which form each side took.  (The persistent
+    kernel's ragged walks, on small volumes under brats_conv3d_set_first_min_tiles, are in tests/test_first_layer_gpu.py, bit for bit.)
+    (i) bit-identical outputs of the two runs (same packed weights, same K order, f32 accumulation from the bias), tile statistics
+    equal to 1e-5; every face of the volume is a boundary tile;
     (ii) against torch's CPU f32 convolution."""
     from brats21_amd import ops
     dev = _dev()
@@ -629,9 +635,24 @@ def test_conv3d_first_layer_kernel(dtype, n, size, with_bias):
     w8[:, :4] = w
     wpk = ops.pack_weights(w8.to(dev), dtype, ops.PACK_FWD)
     bd = b.to(dev) if with_bias else None
-    y_new, s_new = ops.conv3d(xin, wpk, 48, 3, 1, bias=bd, want_stats=True)              # dense output: the new kernel
-    wide = torch.zeros(n, *size, 96, dtype=dtype, device=dev)
-    y_old, s_old = ops.conv3d(xin, wpk, 48, 3, 1, bias=bd, want_stats=True, out=wide[..., 16:64])  # slice: the tile kernel
+    forms = (ops.CONV_FORM_FIRST, ops.CONV_FORM_VS8, ops.CONV_FORM_TILE)
+
+    def count():
+        return [ops.conv_form_launches(dtype, f) for f in forms]
+    reaches = n * ops.tiles_per_sample(*size) >= 2048
+    assert reaches == (size in ((64, 64, 128), (68, 60, 272)))
+    old_vs8 = ops.set_vs8(1)  # (an 8-channel layer's packed weights do not depend on it)
+    try:
+        c0 = count()
+        y_new, s_new = ops.conv3d(xin, wpk, 48, 3, 1, bias=bd, want_stats=True)              # dense output
+        c1 = count()
+        wide = torch.zeros(n, *size, 96, dtype=dtype, device=dev)
+        y_old, s_old = ops.conv3d(xin, wpk, 48, 3, 1, bias=bd, want_stats=True, out=wide[..., 16:64])  # channel slice
+        c2 = count()
+    finally:
+        ops.set_vs8(old_vs8)
+    assert [q - p for p, q in zip(c0, c1)] == ([1, 0, 0] if reaches else [0, 0, 1]), "dense output: persistent kernel from 2048 tiles on"
+    assert [q - p for p, q in zip(c1, c2)] == ([0, 1, 0] if reaches else [0, 0, 1]), "channel slice: 4x8x16-tile kernel from 2048 tiles on"
     assert torch.equal(y_new, y_old.contiguous())
     assert torch.allclose(s_new, s_old, rtol=1e-5, atol=1e-4)
     torch.set_num_threads(16)
