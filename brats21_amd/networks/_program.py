@@ -1,6 +1,7 @@
-"""What the two network programs (equiunet.py, equiunet_assp.py) share: the module base with the precision / fold switches and the
-forward() body, the per-pass context their unit programs take as first argument, the plan + split-precision scoping of their
-autograd Functions, and the backward of the 1x1x1 heads."""
+"""What the network programs (equiunet.py, equiunet_assp.py, att_equiunet.py and the U-Net family of unet.py / r2unet.py) share: the
+module base with the precision / fold switches and the forward() body, the per-pass context their unit programs take as first
+argument, the one autograd Function that runs a network's forward / backward program methods inside the plan + split-precision
+scoping, and the backward of the 1x1x1 heads."""
 import os
 
 import torch
@@ -11,12 +12,14 @@ from .._lib import BratsHipError
 
 
 class _PackedWeightsModule(nn.Module):
-    """Base of EquiUnet / EquiUnetASSPEvo.  Keeps ops' no_grad packed-weight cache honest: the cache is dropped on every train() /
+    """Base of every network.  A network supplies its programs as two methods, _program_fwd(ctx, cx, x0) -> tuple of logits and
+    _program_bwd(ctx, cx, *douts), which leaves the parameter gradients in cx.grads (_ProgramFn).  Keeps ops' no_grad packed-weight cache honest: the cache is dropped on every train() /
     eval() transition and on every grad-enabled forward, so weights changed without a version bump (``p.data.copy_`` of the
     reference's Ranger2020, learning/optimizer.py:243,253) are never served stale to a later evaluation."""
 
     PRECISIONS = ("auto", "bf16", "fp16", "fp32", "x3", "fp16x3", "bf16x3", "x3fwd", "x3bwd")
     _cpu_hint = ""  # tail of the "GPU only" message
+    _cpad = None    # channels the network input is zero-padded to; None: input_cpad decides (R2Unet sets its own)
 
     @property
     def precision(self):
@@ -137,8 +140,8 @@ class _PackedWeightsModule(nn.Module):
                                       f"(got {list(features)})")
         self.inplanes = int(inplanes)
 
-    def _run(self, fn, x):
-        """forward(x) of both networks; fn: the network's autograd Function."""
+    def _run(self, x):
+        """forward(x) of every network."""
         if not x.is_cuda:
             raise BratsHipError(f"brats21_amd.{self.name} runs on the GPU only (no CPU fallback){self._cpu_hint}")
         if x.dim() != 5 or x.shape[1] != self.inplanes or any(s % 8 for s in x.shape[2:]):
@@ -152,7 +155,7 @@ class _PackedWeightsModule(nn.Module):
         self._weights_may_have_changed()
         if self.training and self.pack_plan and torch.is_grad_enabled():
             ops.plan_for(self, x.device)  # all layers' weights (forward + dgrad layouts) packed by one launch
-        outs = fn.apply(self, x.float(), self._dtype(), *self.parameters())
+        outs = _ProgramFn.apply(self, x.float(), self._dtype(), *self.parameters())
         if refinement:  # networks/equiunet2020.py:490-498: the first element is the list [refined, out]
             return ([outs[0], outs[1]], list(outs[2:])) if self.deep_supervision else [outs[0], outs[1]]
         if self.deep_supervision:
@@ -274,8 +277,8 @@ def input_cpad(inplanes, dtype):
 
 
 def _fn_forward(program, ctx, model, x, dtype, params, cpad=None):
-    """forward() of a network's autograd Function around its forward program(ctx, cx, x0) -> tuple of logits.  cpad: the channels
-    the network input is zero-padded to where the program wants other than input_cpad's."""
+    """_ProgramFn.forward around the network's forward program(ctx, cx, x0) -> tuple of logits.  cpad: the channels the network
+    input is zero-padded to where the network wants other than input_cpad's."""
     # training: the module packed all layers' weights up front (ops.plan_for); pack_weights() then returns views
     ctx.plan = ops._PLANS.get(model) if (model.training and model.pack_plan) else None
     ctx.x3 = model._x3_modes() if dtype == torch.float32 else (None, None)
@@ -297,14 +300,26 @@ def _fn_forward(program, ctx, model, x, dtype, params, cpad=None):
 
 
 def _fn_backward(program, ctx, douts):
-    """backward() of a network's autograd Function around its backward program(ctx, cx, *douts), which leaves the parameter
-    gradients in cx.grads."""
+    """_ProgramFn.backward around the network's backward program(ctx, cx, *douts), which leaves the parameter gradients in
+    cx.grads."""
     cx = ctx.cx
     with ops.use_plan(ctx.plan), ops.split_precision(ctx.x3[1]):
         cx.x3s = ops.x3_mode() == ops.X3F and cx.dtype == torch.float32  # (the BACKWARD split decides about the dy scales)
         program(ctx, cx, *douts)
     ctx.cx = None
     return (None, None, None) + tuple(cx.grads.get(i) for i in range(ctx.nparams))
+
+
+class _ProgramFn(torch.autograd.Function):
+    """The autograd Function of every network: model's own programs."""
+
+    @staticmethod
+    def forward(ctx, model, x, dtype, *params):
+        return _fn_forward(model._program_fwd, ctx, model, x, dtype, params, cpad=model._cpad)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        return _fn_backward(ctx.cx.m._program_bwd, ctx, douts)
 
 
 def _heads_bwd(ctx, cx, douts, fold):

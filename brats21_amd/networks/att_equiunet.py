@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ._program import _PackedWeightsModule, _fn_backward, _fn_forward
+from ._program import _PackedWeightsModule
 from .cbam import CBAM, MAX_CHANNELS
 from .equiunet import (ConvBnRelu, UBlock, _blk, _cgr_bwd, _cgr_fwd, _ConvParams, _decoder_bwd, _decoder_fwd, _head, _plus)
 
@@ -58,54 +58,6 @@ def _gate_bwd(cx, cbam, dout, d_pooled=None):
     for p, g in zip(params, grads[1:]):
         cx.put(p, g)
     return grads[0]
-
-
-class _AttEquiUnetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x, dtype, *params):
-        return _fn_forward(_AttEquiUnetFn._forward, ctx, model, x, dtype, params)
-
-    @staticmethod
-    def backward(ctx, *douts):
-        return _fn_backward(_AttEquiUnetFn._backward, ctx, douts)
-
-    @staticmethod
-    def _forward(ctx, cx, x0):
-        m = cx.m
-        cgr = functools.partial(_cgr_fwd, cx)
-
-        def level(enc, t, pool=False):
-            # unit 1 runs lazy into unit 2; unit 2's output is materialised (the gate reads it three times), then the gate
-            c1, c2 = _blk(enc.UBlock)
-            return _gate_fwd(cx, enc.CBAM, cgr(c2, cgr(c1, t, lazy=True)), pool=pool)
-
-        down1, p1 = level(m.encoder1, x0, pool=True)
-        down2, p2 = level(m.encoder2, p1, pool=True)
-        down3, p3 = level(m.encoder3, p2, pool=True)
-        down4 = level(m.encoder4, p3)
-        bottom = level(m.bottom, down4)
-        bottom_2 = _gate_fwd(cx, m.bottom_2[1], cgr(m.bottom_2[0], down4, x2=bottom))
-        # the decoder and the heads are EquiUnet's; the deep heads read the gated bottom / bottom_2
-        return tuple(_decoder_fwd(ctx, cx, down1, down2, down3, down4, bottom, bottom_2))
-
-    @staticmethod
-    def _backward(ctx, cx, *douts):
-        m = cx.m
-        cbw = functools.partial(_cgr_bwd, cx)
-        gbw = functools.partial(_gate_bwd, cx)
-
-        def level(enc, dout, d_pooled=None, need_dx=True):
-            c1, c2 = _blk(enc.UBlock)
-            return cbw(c1, cbw(c2, gbw(enc.CBAM, dout, d_pooled), bst=c1), need_dx=need_dx)
-
-        d_skip1, d_skip2, d_skip3, d_b2, d_deep_bottom = _decoder_bwd(ctx, cx, douts)
-        d_skip4, d_bot = cbw(m.bottom_2[0], gbw(m.bottom_2[1], d_b2))
-        d_down4 = d_skip4 + level(m.bottom, _plus(d_bot, d_deep_bottom))
-        d_p3 = level(m.encoder4, d_down4)
-        d_p2 = level(m.encoder3, d_skip3, d_p3)
-        d_p1 = level(m.encoder2, d_skip2, d_p2)
-        level(m.encoder1, d_skip1, d_p1, need_dx=False)
-        ctx.bufs = None
 
 
 class AttEquiUnet(_PackedWeightsModule):
@@ -168,4 +120,40 @@ class AttEquiUnet(_PackedWeightsModule):
                                       "precision='bf16', 'fp32' or an x3 mode)")
         if self.conv_fp8:
             raise NotImplementedError("brats21_amd.AttEquiUnet with the e4m3 convolution path (conv_fp8) is not implemented")
-        return self._run(_AttEquiUnetFn, x)
+        return self._run(x)
+
+    def _program_fwd(self, ctx, cx, x0):
+        m = cx.m
+        cgr = functools.partial(_cgr_fwd, cx)
+
+        def level(enc, t, pool=False):
+            # unit 1 runs lazy into unit 2; unit 2's output is materialised (the gate reads it three times), then the gate
+            c1, c2 = _blk(enc.UBlock)
+            return _gate_fwd(cx, enc.CBAM, cgr(c2, cgr(c1, t, lazy=True)), pool=pool)
+
+        down1, p1 = level(m.encoder1, x0, pool=True)
+        down2, p2 = level(m.encoder2, p1, pool=True)
+        down3, p3 = level(m.encoder3, p2, pool=True)
+        down4 = level(m.encoder4, p3)
+        bottom = level(m.bottom, down4)
+        bottom_2 = _gate_fwd(cx, m.bottom_2[1], cgr(m.bottom_2[0], down4, x2=bottom))
+        # the decoder and the heads are EquiUnet's; the deep heads read the gated bottom / bottom_2
+        return tuple(_decoder_fwd(ctx, cx, down1, down2, down3, down4, bottom, bottom_2))
+
+    def _program_bwd(self, ctx, cx, *douts):
+        m = cx.m
+        cbw = functools.partial(_cgr_bwd, cx)
+        gbw = functools.partial(_gate_bwd, cx)
+
+        def level(enc, dout, d_pooled=None, need_dx=True):
+            c1, c2 = _blk(enc.UBlock)
+            return cbw(c1, cbw(c2, gbw(enc.CBAM, dout, d_pooled), bst=c1), need_dx=need_dx)
+
+        d_skip1, d_skip2, d_skip3, d_b2, d_deep_bottom = _decoder_bwd(ctx, cx, douts)
+        d_skip4, d_bot = cbw(m.bottom_2[0], gbw(m.bottom_2[1], d_b2))
+        d_down4 = d_skip4 + level(m.bottom, _plus(d_bot, d_deep_bottom))
+        d_p3 = level(m.encoder4, d_down4)
+        d_p2 = level(m.encoder3, d_skip3, d_p3)
+        d_p1 = level(m.encoder2, d_skip2, d_p2)
+        level(m.encoder1, d_skip1, d_p1, need_dx=False)
+        ctx.bufs = None

@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import PACK_DGRAD, PACK_FWD, BratsHipError
-from ._program import _PackedWeightsModule, _fn_backward, _fn_forward, _heads_bwd, _inherit_amax, input_cpad
+from ._program import _PackedWeightsModule, _heads_bwd, _inherit_amax, input_cpad
 
 
 # ------------------------------------------------------------------------------------------ parameter holders
@@ -523,6 +523,46 @@ def _plus(a, b):
     return a if b is None else a + b
 
 
+def _top_head_fwd(ctx, cx, last, u1, head):
+    """The last unit of the decoder on its input u1, and the output head on it -> (logits, the unit's stored activation or None);
+    sets ctx.top_fused / ctx.out_shape / ctx.heads = [the output head's entry] for _top_head_bwd."""
+    m = cx.m
+    # the last layer's activation up1 feeds only the output head: where the kernels for it are built, the head reads
+    # the raw convolution output and applies GroupNorm + act on load (ops.gn_head), the backward recomputes what it
+    # needs (ops.gn_act_bwd_head) -- up1 (2 x 403 MB written + read at 2 x 48 x 128^3) is never stored
+    kact, slope_t = _unit_act(last, cx.act)
+    nk = head.weight.shape[0]
+    fuse_top = (m.fold_head_fwd and cx.drop is None and not last.batch_norm and slope_t is None and kact in ("relu", "leakyrelu")
+                and nk <= 4 and (not cx.will_bwd or (m.fold_head_bwd and ops.head_fold_ok(head.weight, kact, slope_t))))
+    if fuse_top:
+        y1 = _cgr_fwd(cx, last, u1, no_act=True)
+        up1 = None
+        logits = ops.gn_head(y1, cx.recs[last][5], head.weight, head.bias, kact)
+    else:
+        up1 = _cgr_fwd(cx, last, u1)
+        logits = ops.head(up1, head.weight, head.bias, 1)
+    ctx.top_fused = fuse_top
+    ctx.out_shape = tuple(logits.shape)
+    ctx.heads = [(head, up1, 1)]
+    return logits, up1
+
+
+def _top_head_bwd(ctx, cx, c1, c2, head, douts):
+    """Backward of all heads (ctx.heads, _heads_bwd) and of the decoder's last block (c1, c2) under the output head
+    (_top_head_fwd) -> (what the backward of c1 returns, dsrc)."""
+    m = cx.m
+    # the output head on up1: folded into the GroupNorm backward of the last layer where that is built
+    top, dsrc = _heads_bwd(ctx, cx, douts, m.fold_head_bwd and cx.drop is None and not c2.batch_norm
+                           and ops.head_fold_ok(head.weight, *_unit_act(c2, cx.act)))
+    if top is not None:
+        d_c1 = _cgr_bwd(cx, c2, None, head=top, bst=c1)
+    else:
+        up1 = ctx.heads[0][1]
+        d_up1 = dsrc.get(up1.data_ptr())
+        d_c1 = _cgr_bwd(cx, c2, d_up1 if d_up1 is not None else torch.zeros_like(up1), bst=c1)
+    return _cgr_bwd(cx, c1, d_c1), dsrc
+
+
 def _decoder_fwd(ctx, cx, down1, down2, down3, down4, bottom, bottom_2):
     """The decoder and the heads behind bottom_2 (networks/equiunet2020.py:481-498; AttEquiUnet's program hands in its gated
     tensors) -> [logits, deep heads...]; ctx.bufs / ctx.heads / ctx.top_fused are what _decoder_bwd reads."""
@@ -535,24 +575,8 @@ def _decoder_fwd(ctx, cx, down1, down2, down3, down4, bottom, bottom_2):
     up3 = cgr(m.decoder3.ConvBnRelu2, cgr(m.decoder3.ConvBnRelu1, down3, x2=up(bottom_2), lazy=True))
     up2 = cgr(m.decoder2.ConvBnRelu2, cgr(m.decoder2.ConvBnRelu1, down2, x2=up(up3), lazy=True))
     u1 = cgr(m.decoder1.ConvBnRelu1, down1, x2=up(up2), lazy=True)
-    # the last layer's activation up1 feeds only the output head: where the kernels for it are built, the head reads
-    # the raw convolution output and applies GroupNorm + act on load (ops.gn_head), the backward recomputes what it
-    # needs (ops.gn_act_bwd_head) -- up1 (2 x 403 MB written + read at 2 x 48 x 128^3) is never stored
-    last = m.decoder1.ConvBnRelu2
-    kact, slope_t = _unit_act(last, cx.act)
-    nk = m.outconv.weight.shape[0]
-    fuse_top = (m.fold_head_fwd and cx.drop is None and not last.batch_norm and slope_t is None and kact in ("relu", "leakyrelu")
-                and nk <= 4 and (not cx.will_bwd or (m.fold_head_bwd and ops.head_fold_ok(m.outconv.weight, kact, slope_t))))
-    if fuse_top:
-        y1 = cgr(last, u1, no_act=True)
-        up1 = None
-        outs = [ops.gn_head(y1, cx.recs[last][5], m.outconv.weight, m.outconv.bias, kact)]
-    else:
-        up1 = cgr(last, u1)
-        outs = [ops.head(up1, m.outconv.weight, m.outconv.bias, 1)]
-    ctx.top_fused = fuse_top
-    ctx.out_shape = tuple(outs[0].shape)
-    ctx.heads = [(m.outconv, up1, 1)]
+    logits, up1 = _top_head_fwd(ctx, cx, m.decoder1.ConvBnRelu2, u1, m.outconv)
+    outs = [logits]
     if _deep_heads_on(m):
         for hd, src, sc in ((m.deep_bottom[0], bottom, 8), (m.deep_bottom2[0], bottom_2, 8), (m.deep3[0], up3, 4),
                             (m.deep2[0], up2, 2)):
@@ -566,18 +590,13 @@ def _decoder_bwd(ctx, cx, douts):
     """Backward of _decoder_fwd -> (d_skip1, d_skip2, d_skip3, the whole gradient of bottom_2, the deep head's gradient of bottom or
     None)."""
     m = cx.m
-    _, _, _, _, bottom, bottom_2, up3, up2, up1 = ctx.bufs
+    _, _, _, _, bottom, bottom_2, up3, up2, _ = ctx.bufs
     cbw = functools.partial(_cgr_bwd, cx)
-    c1, c2 = _blk(m.decoder1)
-    # the output head on up1: folded into the GroupNorm backward of the last layer where that is built
-    top, dsrc = _heads_bwd(ctx, cx, douts, m.fold_head_bwd and cx.drop is None and not c2.batch_norm
-                           and ops.head_fold_ok(m.outconv.weight, *_unit_act(c2, cx.act)))
+    (d_skip1, d_u1), dsrc = _top_head_bwd(ctx, cx, *_blk(m.decoder1), m.outconv, douts)
 
     def extra(t):
         return dsrc.get(t.data_ptr())
 
-    d_c1 = cbw(c2, None, head=top, bst=c1) if top is not None else cbw(c2, extra(up1) if extra(up1) is not None else torch.zeros_like(up1), bst=c1)
-    d_skip1, d_u1 = cbw(c1, d_c1)
     # (the deep head's gradient of the same activation is added inside the adjoint's launch: the sum of the two stored tensors)
     d_up2 = ops.upsample_bwd(d_u1, 2, add=extra(up2))
     c1, c2 = _blk(m.decoder2)
@@ -587,61 +606,6 @@ def _decoder_bwd(ctx, cx, douts):
     d_skip3, d_u3 = cbw(c1, cbw(c2, d_up3, bst=c1))
     return d_skip1, d_skip2, d_skip3, ops.upsample_bwd(d_u3, 2, add=extra(bottom_2)), extra(bottom)
 
-
-class _EquiUnetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x, dtype, *params):
-        return _fn_forward(_EquiUnetFn._forward, ctx, model, x, dtype, params)
-
-    @staticmethod
-    def backward(ctx, *douts):
-        return _fn_backward(_EquiUnetFn._backward, ctx, douts)
-
-    @staticmethod
-    def _forward(ctx, cx, x0):
-        m = cx.m
-        cgr = functools.partial(_cgr_fwd, cx)
-        # encoder (networks/equiunet2020.py:469-475); every tensor is dense NDHWC, the decoder convolutions
-        # read the virtual concat [skip | up-sampled] from two pointers (no torch.cat, no strided slices)
-        # (the last layer of a level writes its activation -- the skip connection -- and the max-pooled tensor in one pass;
-        #  lazy: the activation between the two units of a block has ONE reader, the block's second convolution)
-        down1, p1 = cgr(m.encoder1.ConvBnRelu2, cgr(m.encoder1.ConvBnRelu1, x0, lazy=True), pool=True)
-        down2, p2 = cgr(m.encoder2.ConvBnRelu2, cgr(m.encoder2.ConvBnRelu1, p1, lazy=True), pool=True)
-        down3, p3 = cgr(m.encoder3.ConvBnRelu2, cgr(m.encoder3.ConvBnRelu1, p2, lazy=True), pool=True)
-        down4 = cgr(m.encoder4.ConvBnRelu2, cgr(m.encoder4.ConvBnRelu1, p3, lazy=True))
-        # bottom (:477-478): dilated block, then conv over cat[down4, bottom]
-        bottom = cgr(m.bottom.ConvBnRelu2, cgr(m.bottom.ConvBnRelu1, down4, lazy=True), lazy=not _deep_heads_on(m))
-        bottom_2 = cgr(m.bottom_2, down4, x2=bottom)
-        # decoder (:481-486)
-        outs = _decoder_fwd(ctx, cx, down1, down2, down3, down4, bottom, bottom_2)
-        if m.refinement:  # (networks/equiunet2020.py:490-491: out = [refunet(out), out])
-            outs.insert(0, _ref_fwd(ctx, cx, outs[0]))
-        return tuple(outs)
-
-    @staticmethod
-    def _backward(ctx, cx, *douts):
-        m = cx.m
-        down1, down2, down3 = ctx.bufs[:3]
-        cbw = functools.partial(_cgr_bwd, cx)
-
-        level_bwd = functools.partial(_level_bwd, cx)
-        if m.refinement:  # the stage runs first: (d_refined, d_out, deep...) -> (the whole gradient of out, deep...)
-            douts = (_ref_bwd(ctx, cx, douts[0], douts[1]),) + tuple(douts[2:])
-
-        d_skip1, d_skip2, d_skip3, d_b2, d_deep_bottom = _decoder_bwd(ctx, cx, douts)
-        d_skip4, d_bot = cbw(m.bottom_2, d_b2)
-        d_bottom = _plus(d_bot, d_deep_bottom)
-        c1, c2 = _blk(m.bottom)
-        d_down4 = d_skip4 + cbw(c1, cbw(c2, d_bottom, bst=c1))
-        c1, c2 = _blk(m.encoder4)
-        d_p3 = cbw(c1, cbw(c2, d_down4, bst=c1))
-        c1, c2 = _blk(m.encoder3)
-        d_p2 = cbw(c1, level_bwd(c2, down3, d_p3, d_skip3, bst=c1))
-        c1, c2 = _blk(m.encoder2)
-        d_p1 = cbw(c1, level_bwd(c2, down2, d_p2, d_skip2, bst=c1))
-        c1, c2 = _blk(m.encoder1)
-        cbw(c1, level_bwd(c2, down1, d_p1, d_skip1, bst=c1), need_dx=False)
-        ctx.bufs = None
 
 # ------------------------------------------------------------------------------------------ module
 class EquiUnet(_PackedWeightsModule):
@@ -705,4 +669,48 @@ class EquiUnet(_PackedWeightsModule):
                 nn.init.constant_(mod.bias.data, 0.0)
 
     def forward(self, x):
-        return self._run(_EquiUnetFn, x)
+        return self._run(x)
+
+    def _program_fwd(self, ctx, cx, x0):
+        m = cx.m
+        cgr = functools.partial(_cgr_fwd, cx)
+        # encoder (networks/equiunet2020.py:469-475); every tensor is dense NDHWC, the decoder convolutions
+        # read the virtual concat [skip | up-sampled] from two pointers (no torch.cat, no strided slices)
+        # (the last layer of a level writes its activation -- the skip connection -- and the max-pooled tensor in one pass;
+        #  lazy: the activation between the two units of a block has ONE reader, the block's second convolution)
+        down1, p1 = cgr(m.encoder1.ConvBnRelu2, cgr(m.encoder1.ConvBnRelu1, x0, lazy=True), pool=True)
+        down2, p2 = cgr(m.encoder2.ConvBnRelu2, cgr(m.encoder2.ConvBnRelu1, p1, lazy=True), pool=True)
+        down3, p3 = cgr(m.encoder3.ConvBnRelu2, cgr(m.encoder3.ConvBnRelu1, p2, lazy=True), pool=True)
+        down4 = cgr(m.encoder4.ConvBnRelu2, cgr(m.encoder4.ConvBnRelu1, p3, lazy=True))
+        # bottom (:477-478): dilated block, then conv over cat[down4, bottom]
+        bottom = cgr(m.bottom.ConvBnRelu2, cgr(m.bottom.ConvBnRelu1, down4, lazy=True), lazy=not _deep_heads_on(m))
+        bottom_2 = cgr(m.bottom_2, down4, x2=bottom)
+        # decoder (:481-486)
+        outs = _decoder_fwd(ctx, cx, down1, down2, down3, down4, bottom, bottom_2)
+        if m.refinement:  # (networks/equiunet2020.py:490-491: out = [refunet(out), out])
+            outs.insert(0, _ref_fwd(ctx, cx, outs[0]))
+        return tuple(outs)
+
+    def _program_bwd(self, ctx, cx, *douts):
+        m = cx.m
+        down1, down2, down3 = ctx.bufs[:3]
+        cbw = functools.partial(_cgr_bwd, cx)
+
+        level_bwd = functools.partial(_level_bwd, cx)
+        if m.refinement:  # the stage runs first: (d_refined, d_out, deep...) -> (the whole gradient of out, deep...)
+            douts = (_ref_bwd(ctx, cx, douts[0], douts[1]),) + tuple(douts[2:])
+
+        d_skip1, d_skip2, d_skip3, d_b2, d_deep_bottom = _decoder_bwd(ctx, cx, douts)
+        d_skip4, d_bot = cbw(m.bottom_2, d_b2)
+        d_bottom = _plus(d_bot, d_deep_bottom)
+        c1, c2 = _blk(m.bottom)
+        d_down4 = d_skip4 + cbw(c1, cbw(c2, d_bottom, bst=c1))
+        c1, c2 = _blk(m.encoder4)
+        d_p3 = cbw(c1, cbw(c2, d_down4, bst=c1))
+        c1, c2 = _blk(m.encoder3)
+        d_p2 = cbw(c1, level_bwd(c2, down3, d_p3, d_skip3, bst=c1))
+        c1, c2 = _blk(m.encoder2)
+        d_p1 = cbw(c1, level_bwd(c2, down2, d_p2, d_skip2, bst=c1))
+        c1, c2 = _blk(m.encoder1)
+        cbw(c1, level_bwd(c2, down1, d_p1, d_skip1, bst=c1), need_dx=False)
+        ctx.bufs = None

@@ -14,7 +14,7 @@ import torch.nn as nn
 from .. import ops
 from .._lib import PACK_DGRAD, PACK_FWD
 from .equiunet import _ConvParams
-from ._program import _Ctx, _PackedWeightsModule, _fn_backward, _fn_forward, _heads_bwd, _inherit_amax  # noqa: F401  (_Ctx: tests)
+from ._program import _Ctx, _PackedWeightsModule, _heads_bwd, _inherit_amax  # noqa: F401  (_Ctx: tests)
 
 
 # ------------------------------------------------------------------------------------------ parameter holders
@@ -286,17 +286,58 @@ def _block_bwd(cx, rec, do, need_dx=True, head=None, pool=None):
     return _conv_evo_bwd(cx, r1, dz1, need_dx)
 
 
-class _AsspFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x, dtype, *params):
-        return _fn_forward(_AsspFn._forward, ctx, model, x, dtype, params)
+# ------------------------------------------------------------------------------------------ module
+class EquiUnetASSPEvo(_PackedWeightsModule):
+    """Constructor signature of networks/equiunet2021.py:230-231."""
+    name = "EquiUnetASSPEvo"
 
-    @staticmethod
-    def backward(ctx, *douts):
-        return _fn_backward(_AsspFn._backward, ctx, douts)
+    def __init__(self, inplanes, num_classes, features, norm_layer=None, act="relu", deep_supervision=False, dropout=0,
+                 refinement=False):
+        super().__init__()
+        warnings.warn("norm layer and activation specified will not be used ! only EVO !!")
+        if refinement:
+            raise NotImplementedError("equiunet_assp_evo_ref raises AttributeError in the reference too (SURVEY App. B)")
+        self._check_shape_limits(inplanes, num_classes, features, 16)
+        print(f"EquiUnetASSP features: {features}")
+        self.deep_supervision = deep_supervision
+        self.act = act.upper()
+        self.features = list(features)
+        self._init_switches(pack_plan="1")
+        f = self.features
+        self.encoder1 = ConvEvoBlockCorrected(inplanes, f[0])
+        self.encoder2 = ConvEvoBlockCorrected(2 * f[0], f[1])
+        self.encoder3 = ConvEvoBlockCorrected(2 * f[1], f[2])
+        self.encoder4 = ConvEvoBlockCorrected(2 * f[2], f[3])
+        self.bridge1 = ConvEvo(f[0], f[0] // 2)
+        self.bridge2 = ConvEvo(f[1], f[1] // 2)
+        self.bridge3 = ConvEvo(f[2], f[2] // 2)
+        self.aspp = SimpleASPPEVO(f[3], f[3] // 4)
+        self.upconv3 = ConvEvo(f[3], f[3] // 4)
+        self.decoder3 = ConvEvoBlockCorrected(f[2], f[2])
+        self.upconv2 = ConvEvo(f[2], f[2] // 4)
+        self.decoder2 = ConvEvoBlockCorrected(f[1], f[1])
+        self.upconv1 = ConvEvo(f[1], f[1] // 4)
+        self.decoder1 = ConvEvoBlockCorrected(f[0], f[0])
+        self.out_conv = _ConvParams(f[0], num_classes, 1, bias=True)
+        if deep_supervision:
+            self.deep3 = nn.ModuleList([_ConvParams(f[2], num_classes, 1, bias=True)])
+            self.deep2 = nn.ModuleList([_ConvParams(f[1], num_classes, 1, bias=True)])
+        # (the reference leaves torch's default init here: init_weights is commented out, :287)
+        # --dropout p: nn.Dropout behind both EvoNorms of a block and behind every ConvEvo's but the ASPP's (networks/equiunet2021.py:
+        # 200,203,219; :178).  Dropout streams: a block owns ids (u, u + 1), a ConvEvo one id.
+        self._init_dropout(dropout)
+        ids, nxt = {}, 0
+        for mod in self.modules():
+            if isinstance(mod, ConvEvoBlockCorrected):
+                ids[mod], nxt = nxt, nxt + 2
+            elif isinstance(mod, ConvEvo):
+                ids[mod], nxt = nxt, nxt + 1
+        self._unit_ids = ids
 
-    @staticmethod
-    def _forward(ctx, cx, x0):
+    def forward(self, x):
+        return self._run(x)
+
+    def _program_fwd(self, ctx, cx, x0):
         m, dtype, uid = cx.m, cx.dtype, cx.drop_of  # (uid: dropout stream of a ConvEvo unit; the ASPP's has p = 0, networks/equiunet2021.py:178)
         f = m.features
         n, d, h, w, _ = x0.shape
@@ -361,8 +402,7 @@ class _AsspFn(torch.autograd.Function):
         ctx.bufs = (down1, down2, down3, up3, up2, up1)
         return tuple(outs)
 
-    @staticmethod
-    def _backward(ctx, cx, *douts):
+    def _program_bwd(self, ctx, cx, *douts):
         R, m = ctx.recs, cx.m
         f = m.features
         h0, h1, h2 = f[0] // 2, f[1] // 2, f[2] // 2
@@ -395,55 +435,3 @@ class _AsspFn(torch.autograd.Function):
         d_p1 = level_bwd(R["rb2"], down2, d_p2, _conv_evo_bwd(cx, R["rbr2"], dcat2[..., :h1]))
         level_bwd(R["rb1"], down1, d_p1, _conv_evo_bwd(cx, R["rbr1"], dcat1[..., :h0]), need_dx=False)
         ctx.recs = ctx.bufs = None
-
-
-# ------------------------------------------------------------------------------------------ module
-class EquiUnetASSPEvo(_PackedWeightsModule):
-    """Constructor signature of networks/equiunet2021.py:230-231."""
-    name = "EquiUnetASSPEvo"
-
-    def __init__(self, inplanes, num_classes, features, norm_layer=None, act="relu", deep_supervision=False, dropout=0,
-                 refinement=False):
-        super().__init__()
-        warnings.warn("norm layer and activation specified will not be used ! only EVO !!")
-        if refinement:
-            raise NotImplementedError("equiunet_assp_evo_ref raises AttributeError in the reference too (SURVEY App. B)")
-        self._check_shape_limits(inplanes, num_classes, features, 16)
-        print(f"EquiUnetASSP features: {features}")
-        self.deep_supervision = deep_supervision
-        self.act = act.upper()
-        self.features = list(features)
-        self._init_switches(pack_plan="1")
-        f = self.features
-        self.encoder1 = ConvEvoBlockCorrected(inplanes, f[0])
-        self.encoder2 = ConvEvoBlockCorrected(2 * f[0], f[1])
-        self.encoder3 = ConvEvoBlockCorrected(2 * f[1], f[2])
-        self.encoder4 = ConvEvoBlockCorrected(2 * f[2], f[3])
-        self.bridge1 = ConvEvo(f[0], f[0] // 2)
-        self.bridge2 = ConvEvo(f[1], f[1] // 2)
-        self.bridge3 = ConvEvo(f[2], f[2] // 2)
-        self.aspp = SimpleASPPEVO(f[3], f[3] // 4)
-        self.upconv3 = ConvEvo(f[3], f[3] // 4)
-        self.decoder3 = ConvEvoBlockCorrected(f[2], f[2])
-        self.upconv2 = ConvEvo(f[2], f[2] // 4)
-        self.decoder2 = ConvEvoBlockCorrected(f[1], f[1])
-        self.upconv1 = ConvEvo(f[1], f[1] // 4)
-        self.decoder1 = ConvEvoBlockCorrected(f[0], f[0])
-        self.out_conv = _ConvParams(f[0], num_classes, 1, bias=True)
-        if deep_supervision:
-            self.deep3 = nn.ModuleList([_ConvParams(f[2], num_classes, 1, bias=True)])
-            self.deep2 = nn.ModuleList([_ConvParams(f[1], num_classes, 1, bias=True)])
-        # (the reference leaves torch's default init here: init_weights is commented out, :287)
-        # --dropout p: nn.Dropout behind both EvoNorms of a block and behind every ConvEvo's but the ASPP's (networks/equiunet2021.py:
-        # 200,203,219; :178).  Dropout streams: a block owns ids (u, u + 1), a ConvEvo one id.
-        self._init_dropout(dropout)
-        ids, nxt = {}, 0
-        for mod in self.modules():
-            if isinstance(mod, ConvEvoBlockCorrected):
-                ids[mod], nxt = nxt, nxt + 2
-            elif isinstance(mod, ConvEvo):
-                ids[mod], nxt = nxt, nxt + 1
-        self._unit_ids = ids
-
-    def forward(self, x):
-        return self._run(_AsspFn, x)

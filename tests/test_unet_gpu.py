@@ -192,6 +192,18 @@ def test_fp16_train_step_is_finite():
     assert bool(torch.isfinite(losses).all()) and all(bool(torch.isfinite(p).all()) for p in params)
 
 
+def test_every_parameter_gradient_is_handed_over_exactly_once():
+    """What data-parallel buckets depend on: one backward calls model._grad_sink once for each of the 76 parameter indices (17 units
+    of four, four heads of two), with the gradient autograd then stores, and for no other."""
+    m = R.build().cuda().train()
+    seen = []
+    m._grad_sink = lambda i, g: seen.append((i, g))
+    _step(m, R.image().cuda(), R.target().cuda())
+    params = list(m.parameters())
+    assert sorted(i for i, _ in seen) == list(range(76)) == list(range(len(params)))
+    assert all(g.shape == params[i].shape and torch.equal(g, params[i].grad) for i, g in seen)
+
+
 def test_sliding_window_is_the_stitched_windows():
     """A 24 x 32 x 40 volume, 16 x 24 x 32 window, overlap 0.5, constant blend, f32: against d1 of the same model run window by
     window and averaged in torch.  Window starts, restated: interval = window * 0.5 = (8, 12, 16); per axis the starts 0 and one
