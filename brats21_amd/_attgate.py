@@ -160,14 +160,84 @@ def _saved(sv, params, dout, what):
     return a_x, a_g, d, ps, fi, ci
 
 
-def attgate_bwd(dout, saved, params, need_dg=True, need_dx=True):
+# The fused dx + un-pooling pass (brats_attgate_dx_unpool) is taken from this many bytes of the skip tensor on; below, finish() runs
+# its two parents.  0: always -- at the three sizes of DESIGN.md's table the fused pass is never slower than the pair
+DX_UNPOOL_MIN_BYTES = 0
+
+
+class AttGatePending:
+    """The last pass of attgate_bwd, deferred (attgate_bwd(defer_dx=True) returns one in place of dx): dx = dout * alpha + t with
+    alpha = sigmoid(a q + b) from the plane q [N * V] and the table st1 [8] of the forward, t = W_x^T dx1raw.  Holds dout and t (each
+    of x's size) until finish()."""
+    __slots__ = ("dout", "t", "q", "st1")
+
+    def __init__(self, dout, t, q, st1):
+        self.dout, self.t, self.q, self.st1 = dout, t, q, st1
+
+    def finish(self, skip=None, d_pooled=None, out=None):
+        """-> dx; with skip (the gate's input x, which a 2x2x2 max pool reads too) and d_pooled (that pool's output gradient): the
+        skip tensor's whole gradient maxpool2_bwd(skip, d_pooled, dx_skip=dx).  Where skip carries a recorded arg-max plane
+        (skip._pool_argmax) that is ONE pass, brats_attgate_dx_unpool, and dx is never stored; otherwise brats_attgate_dx followed
+        by the pooling backward: the same bits.  out: where to write (a channel-slice view is fine; it must not overlap dout or t).
+        The pending object is spent afterwards."""
+        what = "attgate_bwd: finish"
+        d = _act(self.dout, (what, "dout"))
+        t = _act(self.t, (what, "t"), d)
+        code = _storage(d, what)
+        q, st1 = _vec(self.q, d.n * d.vox, (what, "q"), d), _vec(self.st1, 8, (what, "st1"), d)
+        _blocks(code, d.c, d, what)
+        o = _out(out, d.shape, d, (what, "out"))
+        for src, nm in ((d, "dout"), (t, "t")):
+            if out is not None and ops._overlap(o, src):
+                raise _lib.BratsHipError(f"{what}: out overlaps {nm}")
+        if (skip is None) != (d_pooled is None):
+            raise _lib.BratsHipError(f"{what}: skip and d_pooled come together")
+        l, st = _lib.lib(), ops._stream
+        idx = None
+        if skip is not None:
+            a = _act(skip, (what, "skip"), d)
+            g = _act(d_pooled, (what, "d_pooled"), d, shape=ops._even(d, what) + (d.c,))
+            idx = getattr(skip, "_pool_argmax", None)
+            if idx is not None:
+                idx = ops._argmax_plane(idx, d, (what, "skip._pool_argmax"))
+                if d.n > 65535:
+                    raise _lib.BratsHipError(f"{what}: N = {d.n} is beyond 65535 samples")
+        vw = 16 // d.t.element_size()
+        for p, nm in ((d, "dout"), (t, "t"), (o, "out")) + (((g, "d_pooled"),) if skip is not None else ()):
+            if p.pitch % vw or p.ptr % 16:  # (the kernels move 16-byte channel vectors)
+                raise _lib.BratsHipError(f"{what}: {nm} is not made of aligned 16-byte channel vectors (pitch {p.pitch}, offset {p.ptr % 16})")
+        self.dout = self.t = self.q = self.st1 = None
+        if idx is not None and d.n * d.vox * d.c * d.t.element_size() >= DX_UNPOOL_MIN_BYTES:
+            with ops._span("attgate_dx_unpool", code, d.n, d.c, d.vox):
+                _lib.check(l.brats_attgate_dx_unpool(d.ptr, d.pitch, t.ptr, t.pitch, q, st1, idx, g.ptr, g.pitch, o.ptr, o.pitch, code, d.n,
+                                                     d.c, d.d, d.h, d.w, st()), "attgate_dx_unpool")
+            return o.t
+        dx = o if skip is None else _out(None, d.shape, d, (what, "dx"))
+        with ops._span("attgate_dx", code, d.n, d.c, d.vox):
+            _lib.check(l.brats_attgate_dx(d.ptr, d.pitch, t.ptr, t.pitch, q, st1, dx.ptr, dx.pitch, code, d.n, d.vox, d.c, st()), "attgate_dx")
+        if skip is None:
+            return dx.t
+        if out is None:
+            return ops.maxpool2_bwd(skip, d_pooled, dx_skip=dx.t)
+        # (ops.maxpool2_bwd's two forms, into the caller's tensor)
+        if idx is not None:
+            _lib.check(l.brats_maxpool2_bwd_idx(idx, g.ptr, g.pitch, dx.ptr, dx.pitch, o.ptr, o.pitch, code, d.n, d.c, d.d, d.h, d.w, 0, st()),
+                       "maxpool2_bwd_idx")
+        else:
+            _lib.check(l.brats_maxpool2_bwd(a.ptr, a.pitch, None, 0, g.ptr, g.pitch, dx.ptr, dx.pitch, o.ptr, o.pitch, code, d.n, d.c, d.d, d.h,
+                                            d.w, 0, st()), "maxpool2_bwd")
+        return o.t
+
+
+def attgate_bwd(dout, saved, params, need_dg=True, need_dx=True, defer_dx=False):
     """Backward of attgate_fwd: -> (dg, dx, grads) with grads the twelve parameter gradients in state-dict order, each a finished
     sum.  Passes: brats_attgate_apply_bwd (reads dout and x: the plane dqn and the sums that are psi.1's gradients and BN_1's
     backward means), brats_attgate_psi_bwd_stats (reads g1raw, x1raw and the planes, recomputes s and p: the per-channel sums that
     are the BN and psi.0 gradients and the means of BN_g / BN_x's backward), brats_attgate_psi_bwd_apply (the same reads: writes
     dg1raw and dx1raw), the 1x1x1 weight-gradient convolutions (their bias gradients: ops.channel_dot) and input-gradient convolutions, and brats_attgate_dx (dx = dout * alpha + W_x^T
     dx1raw; dout * alpha is never stored).  A forward in eval mode (frozen statistics) runs the same passes with the batch-mean terms
-    off.  need_dg / need_dx = False skip that input gradient (None)."""
+    off.  need_dg / need_dx = False skip that input gradient (None).  defer_dx: every pass but the last runs, and dx comes back as an
+    AttGatePending whose finish() writes it -- alone, or summed with the un-pooled gradient of a pooling that read x too."""
     what = "attgate_bwd"
     sv = saved
     a_x, a_g, d, ps, fi, ci = _saved(sv, params, dout, what)
@@ -213,8 +283,7 @@ def attgate_bwd(dout, saved, params, need_dg=True, need_dx=True):
     if need_dx:
         w = params[4] if fi == ci else _pad(ps[4], ci)
         t, _ = ops.conv3d(dx1, ops.pack_weights(w, a_x.dtype, PACK_DGRAD), a_x.c, 1, 1)
-        dx = torch.empty(a_x.shape, dtype=a_x.dtype, device=dev)
-        with ops._span("attgate_dx", code, n, a_x.c, vox):
-            _lib.check(l.brats_attgate_dx(d.ptr, d.pitch, t.data_ptr(), a_x.c, q, st1, dx.data_ptr(), a_x.c, code, n, vox, a_x.c, st()),
-                       "attgate_dx")
+        dx = AttGatePending(dout, t, sv.q, sv.st1)
+        if not defer_dx:
+            dx = dx.finish()
     return dg, dx, grads

@@ -171,6 +171,15 @@ __global__ void __launch_bounds__(256) ag_bn1_kernel(const double* __restrict__ 
   }
 }
 
+// the gate term of one voxel's channel vector: v <- v alpha (+ r), alpha = sigmoid(a q + b).  ONE statement of it: the apply
+// passes and the fused dx + un-pooling pass below form the same bits
+template <int VW, bool ADD>
+DEVI void ag_gate_term(float a, float b, float qv, float* v, const float* r) {
+  const float al = ag_sigm(a * qv + b);
+#pragma unroll
+  for (int j = 0; j < VW; ++j) v[j] = ADD ? v[j] * al + r[j] : v[j] * al;
+}
+
 // ---- out = x sigmoid(a q + b) / dx = dout sigmoid(a q + b) + t: a thread owns one 16-byte channel vector and walks voxels
 template <typename T, bool ADD>
 __global__ void __launch_bounds__(256) ag_apply_kernel(const T* __restrict__ x, int xpitch, const T* __restrict__ add, int addpitch,
@@ -181,11 +190,7 @@ __global__ void __launch_bounds__(256) ag_apply_kernel(const T* __restrict__ x, 
   const int mycv = threadIdx.x % cv, myvl = threadIdx.x / cv, c0 = mycv * VW;
   if (myvl >= vl) return;
   const float a = st1[4], b = st1[5];
-  auto one = [&](size_t vox, float* v, const float* r) {
-    const float al = ag_sigm(a * q[vox] + b);
-#pragma unroll
-    for (int j = 0; j < VW; ++j) v[j] = ADD ? v[j] * al + r[j] : v[j] * al;
-  };
+  auto one = [&](size_t vox, float* v, const float* r) { ag_gate_term<VW, ADD>(a, b, q[vox], v, r); };
   const size_t stride = (size_t)gridDim.x * vl;
   size_t vox = (size_t)blockIdx.x * vl + myvl;
   for (; vox + stride < M; vox += 2 * stride) {
@@ -207,6 +212,72 @@ __global__ void __launch_bounds__(256) ag_apply_kernel(const T* __restrict__ x, 
     if constexpr (ADD) Vec<T, VW>::load(add + vox * addpitch + c0, r0);
     one(vox, v0, r0);
     Vec<T, VW>::store(out + vox * opitch + c0, v0);
+  }
+}
+
+// ---- the gate's dx and the un-pooling of the level it belongs to in one pass (R2AttUnet's skip gradients):
+//   out = ([k == argmax] d_pooled) + round_T(dout sigmoid(a q + b) + t)
+// what brats_maxpool2_bwd_idx(argmax, d_pooled, dx_skip = the output of brats_attgate_dx) writes, without the dx tensor in
+// between.  The walk is maxpool2_bwd_idx_kernel's (pool_up.hip): grid.y = sample, a thread owns one x position x one 16-byte
+// channel vector and the 2 x 2 (z, y) voxels above it; q is indexed by the batch-wide voxel n voxels + vox.  The gate term is
+// ag_gate_term's, rounded to the storage type before the sum, and the sum is written as that kernel writes it ((0 + sel) +
+// skip): the two passes' bits.
+template <typename T>
+__global__ void __launch_bounds__(256) ag_dx_unpool_kernel(const T* __restrict__ dout, int dopitch, const T* __restrict__ t, int tpitch,
+                                                           const float* __restrict__ q, const float* __restrict__ st1,
+                                                           const uint8_t* __restrict__ argmax, const T* __restrict__ dy, int dypitch,
+                                                           T* __restrict__ out, int opitch, int C, int D, int H, int W) {
+  constexpr int VW = 16 / sizeof(T);
+  const int n = blockIdx.y;
+  const int cv = C / VW;
+  int xb = blockDim.x / cv;
+  if (xb > W) xb = W;
+  const int mycv = threadIdx.x % cv, myvl = threadIdx.x / cv, c0 = mycv * VW;
+  const int Do = D / 2, Ho = H / 2, Wo = W / 2;
+  const int segs = (W + xb - 1) / xb;
+  const size_t items = (size_t)Do * Ho * segs, voxels = (size_t)D * H * W, pvoxels = (size_t)Do * Ho * Wo;
+  if (myvl >= xb) return;
+  const float a = st1[4], b = st1[5];
+  const T* db = dout + (size_t)n * voxels * dopitch + c0;
+  const T* tb = t + (size_t)n * voxels * tpitch + c0;
+  const float* qb = q + (size_t)n * voxels;
+  const T* dyb = dy + (size_t)n * pvoxels * dypitch + c0;
+  T* ob = out + (size_t)n * voxels * opitch + c0;
+  const uint8_t* ab = argmax + (size_t)n * pvoxels * C + c0;
+  for (size_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int seg = (int)(item % segs);
+    const size_t rp = item / segs;
+    const int yo = (int)(rp % Ho), zo = (int)(rp / Ho);
+    const int x = seg * xb + myvl;
+    if (x >= W) continue;
+    const size_t pvox = ((size_t)zo * Ho + yo) * Wo + (x >> 1);
+    float sk[4][VW], r[4][VW], qv[4];
+    size_t vox[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      vox[k] = ((size_t)(2 * zo + (k >> 1)) * H + (2 * yo + (k & 1))) * W + x;
+      Vec<T, VW>::load(db + vox[k] * dopitch, sk[k]);
+      Vec<T, VW>::load(tb + vox[k] * tpitch, r[k]);
+      qv[k] = qb[vox[k]];
+    }
+    uint32_t aw[VW / 4];
+#pragma unroll
+    for (int i = 0; i < VW / 4; ++i) aw[i] = ((const uint32_t*)(ab + pvox * C))[i];
+    float g[VW];
+    Vec<T, VW>::load(dyb + pvox * dypitch, g);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int kk = 2 * k + (x & 1);  // the voxel's index in the window, d, h, w order
+      ag_gate_term<VW, true>(a, b, qv[k], sk[k], r[k]);
+      float o[VW];
+#pragma unroll
+      for (int j = 0; j < VW; ++j) {
+        const int am = (aw[j >> 2] >> (8 * (j & 3))) & 0xff;
+        o[j] = 0.f + (am == kk ? g[j] : 0.f);
+        o[j] += to_f<T>(from_f<T>(sk[k][j]));
+      }
+      Vec<T, VW>::store(ob + vox[k] * opitch, o);
+    }
   }
 }
 
@@ -496,6 +567,30 @@ extern "C" int BRATS_API(brats_attgate_dx)(const void* dout, int dopitch, const 
   const int pitches[3] = {dopitch, tpitch, dxpitch};
   if (int rc = ag_check("attgate_dx", !dout || !t || !q || !st1 || !dx, dtype, N, voxels, C, pitches, 3)) return rc;
   return ag_apply_launch("attgate_dx", dout, dopitch, t, tpitch, q, st1, dx, dxpitch, dtype, N, voxels, C, (hipStream_t)s);
+}
+
+extern "C" int BRATS_API(brats_attgate_dx_unpool)(const void* dout, int dopitch, const void* t, int tpitch, const float* q,
+                                                  const float* st1, const unsigned char* argmax, const void* d_pooled, int dppitch,
+                                                  void* out, int opitch, int dtype, int N, int C, int D, int H, int W,
+                                                  brats_stream_t s) {
+  const char* name = "attgate_dx_unpool";
+  if (D <= 0 || H <= 0 || W <= 0 || ((D | H | W) & 1) || (size_t)D * H * W > (size_t)0x7fffffff)
+    BRATS_FAIL(BRATS_E_ARG, "%s: D, H, W must be positive and even, D * H * W below 2^31 (got %d, %d, %d)", name, D, H, W);
+  if (N > 65535) BRATS_FAIL(BRATS_E_ARG, "%s: N = %d is beyond 65535 samples", name, N);
+  const int pitches[4] = {dopitch, tpitch, dppitch, opitch};
+  if (int rc = ag_check(name, !dout || !t || !q || !st1 || !argmax || !d_pooled || !out, dtype, N, D * H * W, C, pitches, 4)) return rc;
+  const int vw = vec_width(dtype);
+  int xb = 256 / (C / vw);
+  if (xb > W) xb = W;
+  const size_t items = (size_t)(D / 2) * (H / 2) * ((W + xb - 1) / xb);
+  dim3 grid(stream_grid(items, 1, 8192), N);
+  with_storage(dtype, [&](auto st) {
+    using T = typename decltype(st)::type;
+    hipLaunchKernelGGL(ag_dx_unpool_kernel<T>, grid, dim3(256), 0, (hipStream_t)s, (const T*)dout, dopitch, (const T*)t, tpitch, q, st1,
+                       argmax, (const T*)d_pooled, dppitch, (T*)out, opitch, C, D, H, W);
+  });
+  BRATS_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int BRATS_API(brats_attgate_apply_bwd)(const void* dout, int dopitch, const void* x, int xpitch, const float* q,

@@ -5,8 +5,9 @@ nn.BatchNorm3d whatever ``--norm`` says (the reference hard-codes them), so the 
 eval() select batch or running statistics.  The state-dict names are the reference's 21 (its containers are nn.Sequentials:
 ``W_g.0.weight`` ... ``psi.1.num_batches_tracked``), so its checkpoints load with strict=True.
 
-The network programs that will place the gate into the decoders of AttUnet / R2AttUnet call ops.attgate_fwd / ops.attgate_bwd on
-their own NDHWC tensors; this module is the same pair behind the reference's NCDHW float32 interface.
+The network programs that place the gate into the decoders of AttUnet / R2AttUnet (networks/attunet.py) call ops.attgate_fwd /
+ops.attgate_bwd on their own NDHWC tensors, with this module as the holder of the parameters and running buffers; its forward() is
+the same pair behind the reference's NCDHW float32 interface.
 
 Built: ``act`` relu | leakyrelu | elu | swish | mish, f_g and f_l multiples of 8, any f_int >= 1, f32 / bf16 / fp16 storage
 (``.storage``).  ``prelu`` (it would add a state-dict key) and the split-precision modes raise NotImplementedError."""

@@ -6,7 +6,8 @@ The units are EquiUnet's programs (networks/equiunet.py: _cgr_fwd / _cgr_bwd) wi
 EquiUnet is the shape of the program: no bottom block, an ``UpConv`` (nearest-neighbour x2 -> one unit) in front of every decoder
 block, and deep heads that are 1x1x1 convolutions followed by NEAREST up-sampling of the logits (ops.upsample_nearest /
 ops.planes_nearest and their adjoints, csrc/nearest.hip).  That shape is the family's (_UnetFamily: R2Unet, networks/r2unet.py,
-runs it too); Unet's own part is its block, two units, and the output head folded onto the last of them.
+runs it too, and AttUnet / R2AttUnet, networks/attunet.py, with an attention gate on every skip tensor through the family's two
+gate hooks); Unet's own part is its block, two units, and the output head folded onto the last of them.
 
 Built: ``--norm group | instance``, ``--act relu | leakyrelu | elu | swish | mish``, f32 / bf16 / fp16 storage and the split-precision
 modes.  ``batch``, ``bcn``, ``none``, ``prelu`` and the e4m3 convolutions raise NotImplementedError.
@@ -18,6 +19,7 @@ import torch.nn as nn
 
 from .. import ops
 from ._program import _PackedWeightsModule
+from .attgate import AttentionBlock
 from .equiunet import (_cgr_bwd, _cgr_fwd, _ConvParams, _deep_heads_on, _level_bwd, _NormParams, _top_head_bwd,
                        _top_head_fwd)
 
@@ -64,9 +66,11 @@ class _UnetFamily(_PackedWeightsModule):
     """The U-Net family of networks/unet_family.py: four encoder blocks, three UpConv + decoder block pairs, the 1x1x1 output head
     and three deep heads with nearest up-sampling of their logits -- the constructor's common part, forward() and the forward and
     backward programs.  A member names its blocks (ENCODER, DECODER) and supplies _make_block, _block_fwd, _block_bwd,
-    _level_bwd, _top_fwd and _top_bwd."""
+    _level_bwd, _top_fwd and _top_bwd.  A member with GATED set (networks/attunet.py) gets an AttentionBlock ``Att{i}`` between
+    ``Up{i}`` and the decoder block of every level and supplies the two hooks _gate_fwd / _gate_bwd, which do nothing here."""
     _cpu_hint = "; move input/model to cuda"
     ENCODER = DECODER = ()  # attribute names of encoder blocks 1..4 / of decoder blocks 4..2
+    GATED = False
 
     def __init__(self, norm_layer, act):
         """The family's refusals; the member's own come next, then _build."""
@@ -94,6 +98,8 @@ class _UnetFamily(_PackedWeightsModule):
             setattr(self, name, self._make_block(cin, cout, norm_layer, act))
         for i, name in zip((3, 2, 1), self.DECODER):
             setattr(self, f"Up{i + 1}", UpConv(f[i], f[i - 1], norm_layer, act))
+            if self.GATED:  # (networks/unet_family.py:332-343, :430-441: f_int is the width of the level below, half of it at the top)
+                setattr(self, f"Att{i + 1}", AttentionBlock(f[i - 1], f[i - 1], f[i - 2] if i > 1 else f[0] // 2, act))
             setattr(self, name, self._make_block(f[i], f[i - 1], norm_layer, act))
         self.Conv_1x1 = _ConvParams(f[0], output_ch, 1, bias=True)
         if deep_supervision:
@@ -116,6 +122,14 @@ class _UnetFamily(_PackedWeightsModule):
         out, deeps = res  # the reference returns the flat tuple (d1, d2, d3, d4)
         return (out, *deeps) if deeps else out
 
+    def _gate_fwd(self, cx, level, g, x):
+        """The skip tensor x of decoder level `level` (4, 3, 2) as its block reads it; g: the UpConv output beside it."""
+        return x
+
+    def _gate_bwd(self, cx, level, d_skip, d_u):
+        """(d_skip, d_u) of the level's decoder block -> what _level_bwd and the UpConv's backward receive."""
+        return d_skip, d_u
+
     def _program_fwd(self, ctx, cx, x0):
         enc, dec = [getattr(self, n) for n in self.ENCODER], [getattr(self, n) for n in self.DECODER]
         block = functools.partial(self._block_fwd, cx)
@@ -130,9 +144,12 @@ class _UnetFamily(_PackedWeightsModule):
         x3, p3 = block(enc[2], p2, pool=True)
         x4 = block(enc[3], p3)
         # decoder (:194-204, :283-294): the blocks read the virtual concat [skip | up] from two pointers
-        d4_up = block(dec[0], x3, x2=up(self.Up4, x4))
-        d3_up = block(dec[1], x2, x2=up(self.Up3, d4_up))
-        outs = [self._top_fwd(ctx, cx, dec[2], x1, up(self.Up2, d3_up))]
+        u4 = up(self.Up4, x4)
+        d4_up = block(dec[0], self._gate_fwd(cx, 4, g=u4, x=x3), x2=u4)
+        u3 = up(self.Up3, d4_up)
+        d3_up = block(dec[1], self._gate_fwd(cx, 3, g=u3, x=x2), x2=u3)
+        u2 = up(self.Up2, d3_up)
+        outs = [self._top_fwd(ctx, cx, dec[2], self._gate_fwd(cx, 2, g=u2, x=x1), u2)]
         ctx.deep_scales = []
         if _deep_heads_on(self):
             # (:207-213, :298-304) 1x1x1 convolution at the source's resolution, then nearest up-sampling of the logit planes
@@ -149,12 +166,13 @@ class _UnetFamily(_PackedWeightsModule):
         # the deep heads' logit gradients at their sources' resolution, then all heads and the top of the decoder
         low = [douts[0]] + [None if d is None else ops.planes_nearest_bwd(d, sc) for d, sc in zip(douts[1:], ctx.deep_scales)]
         (d_x1, d_u), dsrc = self._top_bwd(ctx, cx, dec[2], low)
+        d_x1, d_u = self._gate_bwd(cx, 2, d_x1, d_u)
 
         def up_bwd(b, d_up, src):  # (add: the gradient a deep head produced for the same activation)
             return ops.upsample_nearest_bwd(_cgr_bwd(cx, b.units[0], d_up), 2, add=dsrc.get(src.data_ptr()))
 
-        d_x2, d_u = self._block_bwd(cx, dec[1], up_bwd(self.Up2, d_u, d3_up))
-        d_x3, d_u = self._block_bwd(cx, dec[0], up_bwd(self.Up3, d_u, d4_up))
+        d_x2, d_u = self._gate_bwd(cx, 3, *self._block_bwd(cx, dec[1], up_bwd(self.Up2, d_u, d3_up)))
+        d_x3, d_u = self._gate_bwd(cx, 4, *self._block_bwd(cx, dec[0], up_bwd(self.Up3, d_u, d4_up)))
         d_p3, _ = self._block_bwd(cx, enc[3], up_bwd(self.Up4, d_u, x4))
         d_p2 = self._level_bwd(cx, enc[2], x3, d_p3, d_x3)
         d_p1 = self._level_bwd(cx, enc[1], x2, d_p2, d_x2)

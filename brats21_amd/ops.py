@@ -2063,4 +2063,4 @@ def probe_box(device=None, mfma_ms=50.0, stream_bytes=403 << 20, modes=(0, 1)):
 
 # ------------------------------------------------------------------------------------------ additive attention gate
 # (defined in a module of its own, which imports this one: the import stands last)
-from ._attgate import AttGateSaved, attgate_bwd, attgate_fwd  # noqa: E402,F401
+from ._attgate import AttGatePending, AttGateSaved, attgate_bwd, attgate_fwd  # noqa: E402,F401

@@ -1036,7 +1036,11 @@ int brats_probe_stream(const void* src, void* dst, size_t bytes, brats_stream_t 
  *   psi_bwd_stats   : recomputes s, p; dq = a * (dqn - m1 - qhat * m2), ds = w_psi * dq * act'(s); per-workgroup partials of `sums`.
  *   psi_bwd_finalize: sums and coef = the means BN_g / BN_x's backward takes (training = 0: zeros).
  *   psi_bwd_apply   : dg1raw = scale_g * (ds - mean ds - ghat * mean ds ghat), dx1raw alike, in the storage type.
- *   dx              : dx = dout * sigmoid(a * q + b) + t, t = the input gradient of the W_x convolution. */
+ *   dx              : dx = dout * sigmoid(a * q + b) + t, t = the input gradient of the W_x convolution.
+ *   dx_unpool       : out = ([k == argmax] * d_pooled) + round(dx), dx as above rounded to the storage type: bit for bit the output of
+ *                     brats_maxpool2_bwd_idx(argmax, d_pooled, dx_skip = dx) without the dx tensor -- the gradient of a gated skip
+ *                     tensor that also feeds a 2x2x2 max pool.  argmax: one byte per pooled element [N, D/2, H/2, W/2, C], the encoding
+ *                     of brats_maxpool2_fwd; q [N * D * H * W]; D, H, W even (BRATS_E_ARG), N <= 65535; out must not overlap dout or t. */
 int brats_attgate_blocks(int dtype, int C, int N, int voxels);
 int brats_attgate_psi_fwd(const void* g1raw, int gpitch, const void* x1raw, int xpitch, const float* ss_g, const float* ss_x,
                           const float* w_psi, float* q, double* part, int dtype, int act, float slope, int N, int voxels, int C,
@@ -1060,6 +1064,9 @@ int brats_attgate_psi_bwd_apply(const void* g1raw, int gpitch, const void* x1raw
                                 int dxpitch, int dtype, int act, float slope, int N, int voxels, int C, brats_stream_t s);
 int brats_attgate_dx(const void* dout, int dopitch, const void* t, int tpitch, const float* q, const float* st1, void* dx, int dxpitch,
                      int dtype, int N, int voxels, int C, brats_stream_t s);
+int brats_attgate_dx_unpool(const void* dout, int dopitch, const void* t, int tpitch, const float* q, const float* st1,
+                            const unsigned char* argmax, const void* d_pooled, int dppitch, void* out, int opitch, int dtype, int N,
+                            int C, int D, int H, int W, brats_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,12 @@ algorithmic bytes of the pass (every tensor read or written once; X = an x-sized
 and the TB/s they give; then the whole forward and backward with the timer off, and ops.probe_box's stream rate from the same
 process, which is what the TB/s are to be read against.
 
+Then the fused pass of R2AttUnet's skip gradients, brats_attgate_dx_unpool, against its two parents in the same process and on the
+same tensors: brats_attgate_dx (reads 2X + P, writes X), brats_maxpool2_bwd_idx with dx as its skip gradient (reads X + X/8 + the
+arg-max bytes A = X/16 in bf16, writes X), the two queued behind each other inside ONE event pair, and the fused pass (reads 2X + P
++ X/8 + A, writes X).  Event pairs around the library entry points themselves (no wrapper code between the events), median [min,
+max] of `--calls` launches each.
+
     python scripts/time_attgate.py [--calls 30] [--json out.json]"""
 import argparse
 import json
@@ -62,6 +68,57 @@ def events(fn, calls, warm=3):
     return [round(float(v), 4) for v in (np.median(times), np.min(times), np.max(times))]
 
 
+def fused_rows(dev, c, s, calls):
+    """-> {row: {ms, min, max, MB, TBps}} of brats_attgate_dx_unpool and its parents at [N, s, s, s, c], bf16."""
+    from brats21_amd import _lib
+    gen = torch.Generator(device=dev).manual_seed(1)
+
+    def rn(*shape):
+        return torch.randn(shape, generator=gen, device=dev)
+    skip, dout, t = (rn(N, s, s, s, c).to(torch.bfloat16) for _ in range(3))
+    d_pooled = rn(N, s // 2, s // 2, s // 2, c).to(torch.bfloat16)
+    ops.maxpool2(skip, want_argmax=True)
+    idx, q = skip._pool_argmax, rn(N * s ** 3)
+    st1 = torch.tensor([0.0, 1.0, 1.0, 0.0, 1.3, -0.2, 0.0, 0.0], device=dev)
+    dx, out = torch.empty_like(dout), torch.empty_like(dout)
+    l, st, code, vox = _lib.lib(), ops._stream(), _lib.BF16, s ** 3
+    ptr = {k: v.data_ptr() for k, v in dict(dout=dout, t=t, q=q, st1=st1, idx=idx, dp=d_pooled, dx=dx, out=out).items()}
+
+    def run_dx():
+        _lib.check(l.brats_attgate_dx(ptr["dout"], c, ptr["t"], c, ptr["q"], ptr["st1"], ptr["dx"], c, code, N, vox, c, st), "attgate_dx")
+
+    def run_unpool():
+        _lib.check(l.brats_maxpool2_bwd_idx(ptr["idx"], ptr["dp"], c, ptr["dx"], c, ptr["out"], c, code, N, c, s, s, s, 0, st), "maxpool2_bwd_idx")
+
+    def run_pair():
+        run_dx()
+        run_unpool()
+
+    def run_fused():
+        _lib.check(l.brats_attgate_dx_unpool(ptr["dout"], c, ptr["t"], c, ptr["q"], ptr["st1"], ptr["idx"], ptr["dp"], c, ptr["out"], c, code,
+                                             N, c, s, s, s, st), "attgate_dx_unpool")
+    run_pair()
+    want = out.clone()
+    run_fused()
+    torch.cuda.synchronize()
+    if not torch.equal(out, want):
+        raise SystemExit("brats_attgate_dx_unpool does not give its parents' bits")
+    x, p = N * vox * c * 2, N * vox * 4
+    a = x // 16  # one arg-max byte per pooled element
+    traffic = {"attgate_dx": 3 * x + p, "maxpool2_bwd_idx(dx_skip)": 2 * x + x // 8 + a, "dx + unpool, one event pair": 5 * x + p + x // 8 + a,
+               "attgate_dx_unpool": 3 * x + p + x // 8 + a}
+    rows = {}
+    for name, fn in (("attgate_dx", run_dx), ("maxpool2_bwd_idx(dx_skip)", run_unpool), ("dx + unpool, one event pair", run_pair),
+                     ("attgate_dx_unpool", run_fused)):
+        med, lo, hi = events(fn, calls)
+        rows[name] = {"ms": med, "min": lo, "max": hi, "MB": round(traffic[name] / 1e6, 1), "TBps": round(traffic[name] / med / 1e9, 2)}
+        print(f"  {name:32s} {med:8.4f} ms  [{lo:.4f}, {hi:.4f}]  {rows[name]['MB']:8.1f} MB  {rows[name]['TBps']:5.2f} TB/s", flush=True)
+    rows["sum_of_parents_ms"] = round(rows["attgate_dx"]["ms"] + rows["maxpool2_bwd_idx(dx_skip)"]["ms"], 4)
+    print(f"  sum of the parents' medians {rows['sum_of_parents_ms']:.4f} ms; fused / sum "
+          f"{rows['attgate_dx_unpool']['ms'] / rows['sum_of_parents_ms']:.3f}", flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=30)
@@ -104,6 +161,8 @@ def main():
         print(f"  whole forward {fwd[0]:.4f} ms [{fwd[1]:.4f}, {fwd[2]:.4f}], whole backward {bwd[0]:.4f} ms [{bwd[1]:.4f}, {bwd[2]:.4f}]", flush=True)
         res["sizes"][f"{c}_{fi}_{s}"] = {"bytes": unit, "passes": rows, "forward_ms": fwd, "backward_ms": bwd}
         del params, g, x, dout, saved
+        torch.cuda.empty_cache()
+        res["sizes"][f"{c}_{fi}_{s}"]["dx_unpool"] = fused_rows(dev, c, s, a.calls)
         torch.cuda.empty_cache()
     res["box"] = {k: v for k, v in ops.probe_box(dev, modes=()).items() if k != "probe"}
     print("box:", res["box"])
